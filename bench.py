@@ -9,6 +9,12 @@ batch that is already resident in HBM.  Workload = BASELINE.json configs[1]: 100
 GPU, max_len 23, time_dense_size 128, n_units 256 (LSTM), Adam(1e-4, beta1 .5, clipnorm 5).  Weak scaling
 (global batch 256*N).  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the line can carry: rooflines
+(--no-roofline), the other precisions / batch sizes / configurations and the predict path (--no-secondary), the oracle parity check
+(--no-parity), the CPU baseline (--no-cpu-baseline), and for N>1 the pre-flight exchange check and the `data_parallel` self-proof.
+--dump-outputs DIR writes what the last timed step left for its caller (loss, softmax, weights, gradients, BatchNorm moving statistics)
+as float32 .npy files; the same arguments draw the same synthetic batch and initial weights every run.
+
 The timed path is the product only (crnn_mi355x over libcrnn_mi355x.so: weights from crnn_mi355x.init, synthetic batch
 generated here); `oracle/` is imported by the `cpu_baseline` leg alone, where it IS the thing being timed.
 """
@@ -806,6 +812,25 @@ def timed_steps(eng, batch, opt, steps, warmup, it0=0):
     return time.perf_counter() - t0, float(loss.mean().item())
 
 
+DUMP_Y_PRED_BYTES = 16 << 20    # with the fixed-size weights and gradients (12.5 MB each) the dump stays under 64 MB at any batch
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the last timed train step left for its caller, one float32 .npy per array: `loss` (per-sample CTC cost, B),
+    `y_pred` (the step's training-mode softmax, B x T x C), `params` (the flat weights after the optimizer step), `grads` (the step's flat
+    gradient), `bn_mean` / `bn_var` (BatchNorm moving statistics after the step's update).  Past 16 MB `y_pred` is a fixed, seeded sample of
+    its images, in ascending order, and `y_pred_rows` names them."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {k: getattr(eng, k).float().cpu().numpy() for k in ("loss", "y_pred", "params", "grads", "bn_mean", "bn_var")}
+    y = out["y_pred"]
+    if y.nbytes > DUMP_Y_PRED_BYTES:
+        n = max(1, DUMP_Y_PRED_BYTES // y[0].nbytes)
+        rows = np.sort(np.random.RandomState(0).choice(y.shape[0], n, replace=False))
+        out["y_pred"], out["y_pred_rows"] = y[rows], rows.astype(np.float32)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def collective_transport_info(dist):
     """What the gradient exchange ran over, for the record (rank 0): backend, RCCL version, the NCCL_* / RCCL_* / HSA_* environment, visible GPUs
     and the number of xGMI links rocm-smi reports between them (0 on a single-GPU box or when the tool is missing).  Informational: never raises."""
@@ -854,12 +879,17 @@ def main():
     ap.add_argument("--max-len", type=int, default=23, help="label capacity; 21 for the IAM shape")
     ap.add_argument("--gru", action="store_true", help="GRU recurrence (what the reference's train.py really builds, SURVEY F3) instead of "
                     "the LSTM BASELINE.json names")
+    ap.add_argument("--full", action="store_true", help="after the headline: rooflines, secondary timings, parity and CPU baseline (each "
+                    "can be left out with its --no-* option), and for N>1 the pre-flight and data-parallel self-proof")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="BASELINE.md's protocol for the CPU leg: 5 warm-up + 20 timed steps (about 2.5 minutes)")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity object (oracle forward of 16 images: a few seconds of CPU)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the fp32 parity-mode and batch-64 timings")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU
@@ -908,7 +938,7 @@ def main():
     opt = Adam(lr=1e-4, beta_1=0.5, beta_2=0.999, clipnorm=5)
     allreduce = GradAllReduce(eng, dist, world) if world > 1 else None
     preflight = None
-    if world > 1:
+    if world > 1 and args.full:
         # (round 6) Before anything is timed: the gradient exchange in its blocking form and in its overlapped two-bucket form must leave the same averaged gradient on
         # every rank -- a transport or stream-ordering problem of the asynchronous schedule shows here, by name, instead of as a silently different loss curve.
         def grads_after(ar):
@@ -973,9 +1003,11 @@ def main():
         dt = float(tt.item())
     last_loss, giveups = eng.loss_and_status().tolist()
     eng.raise_if_rnn_gave_up(giveups)       # a persistent recurrence that lost its co-residency would have produced garbage silently
+    if args.dump_outputs and rank == 0:     # (before anything below runs more launches on the engine's buffers)
+        dump_outputs(eng, args.dump_outputs)
 
     dp_proof = None
-    if dist is not None:
+    if dist is not None and args.full:
         # Self-proof of the N-rank run (after the timed region): the process group's own world size and backend, identical replicas
         # (max |difference| of a parameter checksum vector gathered from every rank: 0.0 when the all-reduce + same Adam step kept the
         # weights bit-identical), and how much of the gradient exchange is exposed (the same steps without the all-reduce, timed the
@@ -1023,7 +1055,7 @@ def main():
         }
         if dp_proof is not None:
             res["data_parallel"] = dp_proof
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             res["roofline"] = depthwise_roofline(eng)
             res["gemm_roofline"] = pointwise_gemm_roofline(eng)
             dbr = depthwise_bwd_roofline(eng)
@@ -1039,7 +1071,7 @@ def main():
                 dfr = depthwise_fp32_cold(B)
                 if dfr is not None:
                     res["dw_fp32_roofline"] = dfr
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             adam = lambda: Adam(lr=1e-4, beta_1=0.5, beta_2=0.999, clipnorm=5)
 
             def leg(batch, steps, warm, reps=1, **kw):
@@ -1112,11 +1144,11 @@ def main():
                                   workload="configs[1] with the GRU recurrence the reference trains (train.py:119, utils.py:80-82)")
                 # BASELINE configs[4]: predict path (predict.py:166-171), batch 1024, beam width 10
                 res["predict"] = predict_leg(1024, iters=20, precision=args.precision, cpu_sample=0 if args.no_cpu_baseline else 32)
-        if world == 1 and not args.no_parity and args.imgh == 100:
+        if args.full and world == 1 and not args.no_parity and args.imgh == 100:
             # CTC-loss / logit / arg-max parity of the benchmarked configuration against the oracle (the metric's second half)
             res["parity"] = parity_check(B, 16, ("fp32", "fp32_two_plane_forward", "bf16s") if args.precision == "bf16s" else
                                          ("fp32", args.precision) if args.precision != "fp32" else ("fp32", "fp32_two_plane_forward"), gru=args.gru)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.cpu_baseline_full)
         # The contract in the one object the driver's record keeps whole (`config`): whether the 1e-3 / bit-exact tolerance holds in the parity mode
         # and in the benchmarked mode, and the rates of the modes / batches the metric string names beside the headline.  None = leg not run.

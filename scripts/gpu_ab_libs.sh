@@ -7,6 +7,6 @@ cp crnn-ocr-lite_amd/libcrnn_mi355x.so /tmp/libcrnn_product.so
 for rep in 1 2; do
 for n in "$@"; do
   if [ $n = product ]; then cp /tmp/libcrnn_product.so crnn-ocr-lite_amd/libcrnn_mi355x.so; else cp scripts/_trace/libcrnn_$n.so crnn-ocr-lite_amd/libcrnn_mi355x.so; fi
-  echo -n "$n: "; timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary ${BENCH_ARGS:---no-roofline} 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d.get('roofline',{}).get('frac'), d.get('roofline',{}).get('in_step_effective',{}).get('frac'))"
+  echo -n "$n: "; timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary ${BENCH_ARGS:---no-roofline} 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d.get('roofline',{}).get('frac'), d.get('roofline',{}).get('in_step_effective',{}).get('frac'))"
 done; done
 cp /tmp/libcrnn_product.so crnn-ocr-lite_amd/libcrnn_mi355x.so

@@ -3,7 +3,7 @@
 #   bash scripts/gpu_visit.sh TAG STEP [STEP ...]
 # steps (each writes gpurun_out/TAG_<step>.*; a step's failure does not stop the others):
 #   tests:<pytest -k expr>   the GPU tests selected by the expression ("tests:" alone = the whole -m gpu suite)
-#   bench[:args]             bench.py (default line) with extra args
+#   bench[:args]             bench.py --full (every leg of the line) with extra args
 #   dws | dbs | probe        depthwise forward / backward micro-benchmarks (product library + scripts/_trace variants), access-pattern probe
 #   prof:name[:args]         rocprofv3 --kernel-trace --stats of bench.py (short run) -> step timeline + kernel stats
 #   pmc:name:COUNTERS[:args] rocprofv3 --pmc pass (counters comma separated, no trace domains beside --kernel-trace) of bench.py
@@ -18,7 +18,7 @@ export PYTHONPATH=$ROOT:$ROOT/crnn-ocr-lite_amd:$ROOT/tests
 cd $ROOT
 SUM=$OUT/${TAG}_summary.txt
 : > $SUM
-BENCH_SHORT="--steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-parity"
+BENCH_SHORT="--steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary --no-parity"
 for step in "$@"; do
   kind=${step%%:*}; rest=${step#*:}; [ "$rest" = "$step" ] && rest=""
   t0=$(date +%s)
@@ -32,7 +32,7 @@ for step in "$@"; do
       [ -f $OUT/rccl_skip_reason.txt ] && cat $OUT/rccl_skip_reason.txt >> $SUM ;;
     bench)
       n=$(echo "$rest" | tr -c 'a-zA-Z0-9' '_' | cut -c1-40)
-      timeout 1500 python bench.py $(echo $rest | tr ':' ' ') > $OUT/${TAG}_bench_${n:-default}.json 2> $OUT/${TAG}_bench_${n:-default}.err
+      timeout 1500 python bench.py --full $(echo $rest | tr ':' ' ') > $OUT/${TAG}_bench_${n:-default}.json 2> $OUT/${TAG}_bench_${n:-default}.err
       echo "bench[$rest] exit $?: $(cut -c1-150 $OUT/${TAG}_bench_${n:-default}.json)" >> $SUM ;;
     dws) for wd in ${rest:-32}; do timeout 300 python scripts/dws_bench.py 256 $wd 2>/dev/null | grep -v amdgpu; done > $OUT/${TAG}_dw_fwd_stream_bench.txt; echo "dws exit $?" >> $SUM ;;
     dbs) timeout 300 python scripts/dbs_bench.py 2>/dev/null | grep -v amdgpu > $OUT/${TAG}_dw_bwd_stream_bench.txt; echo "dbs exit $?" >> $SUM ;;

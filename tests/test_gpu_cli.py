@@ -88,7 +88,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16",
-           "--no-roofline"]
+           "--full", "--no-roofline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -184,7 +184,7 @@ def test_bench_eight_ranks_on_one_gpu_over_gloo():
     port = 29300 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "8",
-           "--no-roofline"]
+           "--full", "--no-roofline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     if out.returncode != 0:
         _dp_log("bench_world8_failure.log", out)
@@ -249,6 +249,38 @@ def test_bench_self_launches_its_ranks():
     assert len(lines) == 1, out.stdout[-2000:]
     res = json.loads(lines[0])
     assert res["n_gpus"] == 2 and res["config"]["global_batch"] == 32 and res["value"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` times exactly --steps steps and prints the headline alone (every other leg is behind --full);
+    --dump-outputs writes the last timed step's outputs as float32 arrays, and two runs with the same arguments start from the same inputs."""
+    import json
+    import subprocess
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, PKG]))
+    runs = []
+    for name in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16",
+                              "--dump-outputs", str(tmp_path / name)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs.append(json.loads(lines[0]))
+    res = runs[0]
+    assert res["metric"] == "text-line images/sec (train step)" and res["unit"] == "images/sec" and res["higher_is_better"] is True
+    assert res["dtype"] == "bf16" and res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0
+    assert abs(res["value"] - 16 * 1e3 / res["ms_per_step"]) <= 0.01 * res["value"]
+    for leg in ("roofline", "gemm_roofline", "parity", "parity_mode", "bs64", "fit", "predict", "cpu_baseline", "data_parallel"):
+        assert leg not in res, leg
+    dumps = []
+    for name in ("a", "b"):
+        d = {f[:-4]: np.load(str(tmp_path / name / f)) for f in os.listdir(str(tmp_path / name))}
+        assert sorted(d) == ["bn_mean", "bn_var", "grads", "loss", "params", "y_pred"]
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in d.values())
+        assert d["loss"].shape == (16,) and d["y_pred"].shape == (16, 52, 38) and d["params"].shape == d["grads"].shape
+        assert np.allclose(d["y_pred"].sum(-1), 1.0, atol=1e-3) and abs(float(d["loss"].mean()) - res["config"]["final_loss"]) < 1e-3
+        dumps.append(d)
+    for k in ("loss", "params", "bn_mean"):
+        assert np.allclose(dumps[0][k], dumps[1][k], rtol=1e-3, atol=1e-5), k
 
 
 def test_train_cli_two_ranks_keep_identical_weights(tmp_path):

@@ -298,6 +298,34 @@ def test_bench_counter_traffic_lookup_and_contract_fields():
         assert 'cf["%s"]' % key in src, key
 
 
+def test_bench_dump_outputs_writes_float32_arrays_and_samples_a_large_softmax(tmp_path):
+    """bench.py --dump-outputs, host logic only: one float32 .npy per output of the step; a softmax past 16 MB is replaced by a fixed, seeded
+    sample of its images (the same rows every run, listed in y_pred_rows), so the dump stays under 64 MB."""
+    import importlib.util, types
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(native.HEADER), "..", "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    rs = np.random.RandomState(0)
+    n_params = 3282865
+    arrays = {"loss": rs.rand(2200), "y_pred": rs.rand(2200, 52, 38), "params": rs.rand(n_params), "grads": rs.rand(n_params),
+              "bn_mean": rs.rand(3000), "bn_var": rs.rand(3000)}
+    eng = types.SimpleNamespace(**{k: torch.from_numpy(v.astype(np.float32)) for k, v in arrays.items()})
+    for d in ("a", "b"):
+        bench.dump_outputs(eng, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(["loss.npy", "y_pred.npy", "y_pred_rows.npy", "params.npy", "grads.npy", "bn_mean.npy", "bn_var.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float32 for v in got.values())
+    rows = got["y_pred_rows"].astype(np.int64)
+    assert len(rows) < 2200 and np.all(np.diff(rows) > 0) and got["y_pred"].nbytes <= 16 << 20
+    assert np.array_equal(got["y_pred"], arrays["y_pred"].astype(np.float32)[rows])
+    for k in ("loss", "params", "grads", "bn_mean", "bn_var"):
+        assert np.array_equal(got[k], arrays[k].astype(np.float32)), k
+    for f in files:        # a second dump of the same state is identical, sample included
+        assert np.array_equal(np.load(tmp_path / "b" / f), got[f[:-4]]), f
+
+
 def test_model_surface_weights_roundtrip_without_gpu(tmp_path):
     init_model = U.CRNN(num_classes=38, shape=(100, 32, 1), max_string_len=23, time_dense_size=128, n_units=256)
     model = init_model.get_model()
