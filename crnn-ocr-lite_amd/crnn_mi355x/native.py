@@ -32,7 +32,6 @@ FLAG_DW_TILE_KERNEL = 32       # CRNN_FLAG_DW_TILE_KERNEL
 FLAG_RNN_LINEAR_CLUSTERS = 64  # CRNN_FLAG_RNN_LINEAR_CLUSTERS
 FLAG_NO_BN_STATS_FUSION = 128  # CRNN_FLAG_NO_BN_STATS_FUSION
 FLAG_F32_MFMA_GEMMS = 256      # CRNN_FLAG_F32_MFMA_GEMMS
-FLAG_DEFERRED_SUMS = 512       # CRNN_FLAG_DEFERRED_SUMS
 FLAG_BN2_DW_FUSION = 1024      # CRNN_FLAG_BN2_DW_FUSION (opt-in)
 FLAG_BN2_STATS_FUSION = 2048   # CRNN_FLAG_BN2_STATS_FUSION (opt-in)
 FLAG_BLOCK1_KERNELS = 16384    # CRNN_FLAG_BLOCK1_KERNELS
@@ -41,7 +40,6 @@ FLAG_THREE_PLANE_BACKWARD = 65536   # CRNN_FLAG_THREE_PLANE_BACKWARD (parity mod
 FLAG_TWO_PLANE_FORWARD = 131072     # CRNN_FLAG_TWO_PLANE_FORWARD (parity mode, opt-in)
 FLAG_NO_GRADIENT_PLANES = 262144   # CRNN_FLAG_NO_GRADIENT_PLANES (parity mode: BatchNorm-2's input gradients stay fp32 tensors)
 FLAG_NO_POOL_ARGMAX_Q = 524288     # CRNN_FLAG_NO_POOL_ARGMAX_Q (pooled blocks: the backward's statistics pass scans the windows again)
-FLAG_WEIGHT_PLANES = 32768     # CRNN_FLAG_WEIGHT_PLANES (parity mode, opt-in)
 FLAG_NO_BN2_DW_FUSION = 4096   # CRNN_FLAG_NO_BN2_DW_FUSION (fp32 tensors: the two fusions above are the default)
 RNN_XCD_LOCAL = 0x100          # CRNN_RNN_XCD_LOCAL (or-ed into the uw argument of crnn_lstm_*_persist)
 

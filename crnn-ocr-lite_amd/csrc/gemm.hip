@@ -43,9 +43,6 @@ struct GemmParams {
   // a ReLU6(BatchNorm(d)); bnpart [tilesM][2][N] = per-tile column sums of gy and gy * xhat, gy = C where 0 < d * scale + shift < 6,
   // xhat = (d - mean) / sqrt(var + eps); bnD [M][ldd] fp32 = d, bnstate = [mean | var | scale | shift] x N
   const float* bnD; int ldd; const float* bnstate; float* bnpart;
-  // three-plane kernel: an operand handed over as its three bf16 planes (crnn_split3_planes; plane pl of element i at Xpl[pl * xpls + i], the leading
-  // dimension of the fp32 operand it stands for) -- null: split from fp32 while staging
-  const unsigned short* Apl; const unsigned short* Bpl; long apls, bpls;
 #ifdef CRNN_GEMM_EXP
   unsigned long long* trace;   // ablation build only: s_memrealtime stamps of workgroup 300, thread 0
   int exp;         // ablation build only (scripts/gemm_ablate.py): 1 no C stores, 2 no MFMA, 4 B loaded once, 8 A loaded once
@@ -445,7 +442,7 @@ extern "C" int crnn_pwconv_fwd(const void* a, const void* w, void* q, long M, in
   const float* cs = out_bnstate ? out_bnstate + 2L * N : nullptr; const float* ch = out_bnstate ? out_bnstate + 3L * N : nullptr;
   if (bf16_products == 2 || bf16_products == 3)   // fp32 tensors: 2 = fp32-accurate three-plane bf16 products (crnn_gemm_f32x3), 3 = two planes (crnn_gemm_f32x2)
     return gemm_bf16_impl(mode, a, w, q, (int)M, N, K, K, ldw, N, nullptr, 0, 0, 0, nullptr, 0, dt_a, dt_w, dt_q, stat_partials, stream, cs, ch,
-                          nullptr, nullptr, true, nullptr, nullptr, bf16_products == 2 ? 3 : 2);
+                          nullptr, nullptr, true, nullptr, bf16_products == 2 ? 3 : 2);
   if (bf16_products)
     return gemm_bf16_impl(mode, a, w, q, (int)M, N, K, K, ldw, N, nullptr, 0, 0, 0, nullptr, 0, dt_a, dt_w, dt_q, stat_partials, stream, cs, ch);
   if (dt_a != CRNN_F32 || dt_w != CRNN_F32 || dt_q != CRNN_F32) return CRNN_ERR_ARG;
@@ -483,21 +480,13 @@ extern "C" int crnn_pwconv_bnrelu6_fwd_f32x2(const float* d, const float* in_bns
                                              float* stat_partials, hipStream_t stream) {
   if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
   return gemm_bf16_impl(0, d, w, q, (int)M, N, K, K, N, N, nullptr, 0, 0, 0, nullptr, 0, CRNN_F32, CRNN_F32, CRNN_F32, stat_partials, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true, nullptr, nullptr, 2);
+                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true, nullptr, 2);
 }
 extern "C" int crnn_pwconv_bnrelu6_wgrad_f32x2(const float* d, const float* in_bnstate, const float* g, float* dw, long M, int N, int K,
                                                float* scratch, size_t scratch_bytes, hipStream_t stream) {
   if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
   return gemm_bf16_impl(2, d, g, dw, K, N, (int)M, K, N, N, nullptr, 0, 0, 0, scratch, scratch_bytes, CRNN_F32, CRNN_F32, CRNN_F32, nullptr, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true, nullptr, nullptr, 2);
-}
-// ... with the weights as planes (crnn_split3_planes of w, plane stride w_plane_stride elements; null: the entry point above)
-extern "C" int crnn_pwconv_bnrelu6_fwd_f32x3_pl(const float* d, const float* in_bnstate, const float* w, const void* w_planes, long w_plane_stride, float* q,
-                                                long M, int N, int K, float* stat_partials, hipStream_t stream) {
-  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
-  const X3Planes pl{nullptr, 0, (const unsigned short*)w_planes, w_plane_stride};
-  return gemm_bf16_impl(0, d, w, q, (int)M, N, K, K, N, N, nullptr, 0, 0, 0, nullptr, 0, CRNN_F32, CRNN_F32, CRNN_F32, stat_partials, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true, nullptr, w_planes ? &pl : nullptr);
+                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true, nullptr, 2);
 }
 extern "C" int crnn_pwconv_bnrelu6_wgrad_f32x3(const float* d, const float* in_bnstate, const float* g, float* dw, long M, int N, int K,
                                                float* scratch, size_t scratch_bytes, hipStream_t stream) {

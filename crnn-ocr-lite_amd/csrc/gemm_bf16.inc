@@ -912,59 +912,6 @@ __device__ __forceinline__ void x3p_store_km(unsigned char* Xs, int plane_bytes,
     }
   }
 }
-// Operand handed over as its three bf16 planes (crnn_split3_planes: plane pl of element i at X[pl * ps + i], the words split3_pair forms): the same
-// items as x3p_load_rm / x3p_load_km, 8 bytes per plane instead of 16 of fp32, and nothing to split -- the LDS stage is the one the fp32 operand
-// would give, bit for bit.  Whole tiles only.
-template <int ROWS>
-__device__ __forceinline__ void x3p_loadp_rm(const unsigned short* __restrict__ X, long ps, int ld, int row0, int k0, int st, uint2 (&raw)[3 * X3P_RAW(ROWS)]) {
-#pragma unroll
-  for (int it = 0; it < X3P_ITEMS(ROWS); ++it) {
-    const int idx = st + it * X3P_STAGERS, row = idx / X3P_K4, k4 = idx % X3P_K4;
-    if ((ROWS * X3P_K4) % X3P_STAGERS != 0 && idx >= ROWS * X3P_K4) continue;   // (never stored)
-    const unsigned short* p = X + (long)(row0 + row) * ld + k0 + 4 * k4;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) raw[3 * it + pl] = *reinterpret_cast<const uint2*>(p + pl * ps);
-  }
-}
-template <int ROWS>
-__device__ __forceinline__ void x3p_storep_rm(unsigned char* Xs, int plane_bytes, int st, const uint2 (&raw)[3 * X3P_RAW(ROWS)]) {
-#pragma unroll
-  for (int it = 0; it < X3P_ITEMS(ROWS); ++it) {
-    const int idx = st + it * X3P_STAGERS, row = idx / X3P_K4, k4 = idx % X3P_K4;
-    if ((ROWS * X3P_K4) % X3P_STAGERS != 0 && idx >= ROWS * X3P_K4) continue;
-    unsigned char* d = Xs + (row * PLD + 4 * k4) * 2;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<uint2*>(d + pl * plane_bytes) = raw[3 * it + pl];
-  }
-}
-template <int ROWS>
-__device__ __forceinline__ void x3p_loadp_km(const unsigned short* __restrict__ X, long ps, int ld, int row0, int k0, int st, uint2 (&raw)[3 * X3P_RAW(ROWS)]) {
-#pragma unroll
-  for (int it = 0; it < X3P_KITEMS(ROWS); ++it) {
-    const int idx = st + it * X3P_STAGERS, kp = idx / (ROWS / 4), c4 = idx % (ROWS / 4);
-    if (X3P_KTOT(ROWS) % X3P_STAGERS != 0 && idx >= X3P_KTOT(ROWS)) continue;   // (never stored)
-    const unsigned short* p = X + (long)(k0 + 2 * kp) * ld + row0 + 4 * c4;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      raw[6 * it + 2 * pl] = *reinterpret_cast<const uint2*>(p + pl * ps);
-      raw[6 * it + 2 * pl + 1] = *reinterpret_cast<const uint2*>(p + pl * ps + ld);
-    }
-  }
-}
-template <int ROWS>
-__device__ __forceinline__ void x3p_storep_km(unsigned char* Xs, int plane_bytes, int st, const uint2 (&raw)[3 * X3P_RAW(ROWS)]) {
-#pragma unroll
-  for (int it = 0; it < X3P_KITEMS(ROWS); ++it) {
-    const int idx = st + it * X3P_STAGERS, kp = idx / (ROWS / 4), c4 = idx % (ROWS / 4);
-    if (X3P_KTOT(ROWS) % X3P_STAGERS != 0 && idx >= X3P_KTOT(ROWS)) continue;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      unsigned short* d = reinterpret_cast<unsigned short*>(Xs + pl * plane_bytes);
-      *reinterpret_cast<uint2*>(&d[(2 * kp) * KLD(ROWS) + 4 * c4]) = raw[6 * it + 2 * pl];
-      *reinterpret_cast<uint2*>(&d[(2 * kp + 1) * KLD(ROWS) + 4 * c4]) = raw[6 * it + 2 * pl + 1];
-    }
-  }
-}
 // fragment of a stage: the 8 bf16 (k = 16 ks + 8 half .. +7) of row r0 + l31
 template <bool KM, int ROWS>
 __device__ __forceinline__ bf16x8 x3p_frag(const unsigned char* Xs, int r0, int ks, int half, int l31) {
@@ -975,16 +922,12 @@ __device__ __forceinline__ bf16x8 x3p_frag(const unsigned char* Xs, int r0, int 
 // ATR: the A operand the planes are formed from is ReLU6(A * ascale[ch] + ashift[ch]) (GemmParams::ascale / ashift; ch = the reduction index in mode 0, the A
 // row in mode 2), applied by the staging waves to the raw fp32 items before the split -- the BatchNorm + ReLU6 between a depthwise and a pointwise
 // convolution in the parity mode, the very arithmetic of bn_act_pool_drop_kernel, without the activated tensor in HBM.
-// APL / BPL: that operand arrives as its three bf16 planes (GemmParams::Apl / Bpl) instead of fp32 (whole tiles; not with ATR on A).
 // NPL = 2: two planes per operand and the three products hi*hi + hi*mid + mid*hi -- 16 significant bits per factor (relative error of a product
 // <= 3 * 2^-18, fp32 accumulation): half the MFMA work and two thirds of the LDS traffic of the three-plane form.
-template <int BN, bool A_KM, bool B_KM, bool FULL, bool BNB = false, bool ATR = false, bool APL = false, bool BPL = false, int NPL = 3>
+template <int BN, bool A_KM, bool B_KM, bool FULL, bool BNB = false, bool ATR = false, int NPL = 3>
 __global__ __launch_bounds__(256 + X3P_STAGERS) __attribute__((amdgpu_waves_per_eu(X3P_WGS * (256 + X3P_STAGERS) / 256)))
 void gemm_x3p_kernel(GemmParams p) {
   static_assert(NPL == 2 || NPL == 3, "two or three planes");
-  static_assert(!(APL || BPL) || NPL == 3, "plane operands hold three planes");
-  static_assert(!(APL || BPL) || FULL, "plane operands: whole tiles");
-  static_assert(!(APL && ATR), "the producer prologue works on the fp32 items");
   constexpr int BM = 128;
   constexpr int WAVES_N = (BN == 128) ? 2 : 1;
   constexpr int WM = (BN == 128) ? 64 : 32;
@@ -1027,21 +970,19 @@ void gemm_x3p_kernel(GemmParams p) {
   if (wave >= 4) {
     // ------------------------------------------------------------------ staging waves
     const int st = tid - 256;
-    using RawA = std::conditional_t<APL, uint2[3 * X3P_RAW(BM)], float4[X3P_RAW(BM)]>;
-    using RawB = std::conditional_t<BPL, uint2[3 * X3P_RAW(BN)], float4[X3P_RAW(BN)]>;
+    using RawA = float4[X3P_RAW(BM)];
+    using RawB = float4[X3P_RAW(BN)];
     RawA rawA[2]; RawB rawB[2];
     auto load = [&](int s, RawA& dA, RawB& dB) {
       s = s < nst ? s : (nst > 0 ? nst - 1 : 0);                                 // past the end: the last stage again (never stored)
       const int k0 = kbeg + s * PBK;
       const bool full = FULL && nst > 0;
-      if constexpr (APL) { if constexpr (A_KM) x3p_loadp_km<BM>(p.Apl, p.apls, p.lda, m0, k0, st, dA); else x3p_loadp_rm<BM>(p.Apl, p.apls, p.lda, m0, k0, st, dA); }
-      else if constexpr (A_KM) x3p_load_km<BM>(p.A, p.lda, m0, p.M, k0, kend, p.vecA, full, st, dA);
+      if constexpr (A_KM) x3p_load_km<BM>(p.A, p.lda, m0, p.M, k0, kend, p.vecA, full, st, dA);
       else x3p_load_rm<BM>(p.A, p.lda, m0, p.M, k0, kend, p.vecA, full, st, dA);
 #if X3P_EXP & 128
       { for (int i = 0; i < X3P_RAW(BN); ++i) dB[i] = make_float4(0.f, 0.f, 0.f, 0.f); return; }   // experiment: B neither loaded, split nor stored
 #endif
-      if constexpr (BPL) { if constexpr (B_KM) x3p_loadp_km<BN>(p.Bpl, p.bpls, p.ldb, n0, k0, st, dB); else x3p_loadp_rm<BN>(p.Bpl, p.bpls, p.ldb, n0, k0, st, dB); }
-      else if constexpr (B_KM) x3p_load_km<BN>(p.B, p.ldb, n0, p.N, k0, kend, p.vecB, full, st, dB);
+      if constexpr (B_KM) x3p_load_km<BN>(p.B, p.ldb, n0, p.N, k0, kend, p.vecB, full, st, dB);
       else x3p_load_rm<BN>(p.B, p.ldb, n0, p.N, k0, kend, p.vecB, full, st, dB);
     };
     float kmsc[4] = {0.f, 0.f, 0.f, 0.f}, kmsh[4] = {0.f, 0.f, 0.f, 0.f};          // ATR, mode 2: scale / shift of this thread's four A rows (channels)
@@ -1111,8 +1052,7 @@ void gemm_x3p_kernel(GemmParams p) {
           }
           x3p_store_km<BM, NPL>(base, A_PL, st, tA);
         }
-      } else
-      if constexpr (APL) { if constexpr (A_KM) x3p_storep_km<BM>(base, A_PL, st, dA); else x3p_storep_rm<BM>(base, A_PL, st, dA); }
+      }
       else if constexpr (A_KM) x3p_store_km<BM, NPL>(base, A_PL, st, dA); else x3p_store_rm<BM, NPL>(base, A_PL, st, dA);
 #if X3P_EXP & 128
       return;
@@ -1127,8 +1067,7 @@ void gemm_x3p_kernel(GemmParams p) {
         return;
       }
 #endif
-      if constexpr (BPL) { if constexpr (B_KM) x3p_storep_km<BN>(base + 3 * A_PL, B_PL, st, dB); else x3p_storep_rm<BN>(base + 3 * A_PL, B_PL, st, dB); }
-      else if constexpr (B_KM) x3p_store_km<BN, NPL>(base + NPL * A_PL, B_PL, st, dB); else x3p_store_rm<BN, NPL>(base + NPL * A_PL, B_PL, st, dB);
+      if constexpr (B_KM) x3p_store_km<BN, NPL>(base + NPL * A_PL, B_PL, st, dB); else x3p_store_rm<BN, NPL>(base + NPL * A_PL, B_PL, st, dB);
     };
     if (nst > 0) {
       load(0, rawA[0], rawB[0]); load(1, rawA[1], rawB[1]);
@@ -1220,16 +1159,13 @@ void gemm_x3p_kernel(GemmParams p) {
 // the storage of A, B and C (CRNN_F32 | CRNN_BF16); leading dimensions are in elements of the respective type.
 static bool xcd_split_off() { return crnn_knob("CRNN_XSPLIT", 1) == 0; }
 struct BnBwdEpilogue { const float* d; int ldd; const float* bnstate; float* partials; };   // GemmParams::bnD .. bnpart
-// operands of the three-plane kernel that arrive as planes (a / b null: that operand is split from fp32 while staging)
-struct X3Planes { const unsigned short* a; long as; const unsigned short* b; long bs; };
 static int gemm_bf16_impl(int mode, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb,
                           int ldc, const float* bias, int act, int accumulate, int permP, float* scratch,
                           size_t scratch_bytes, int dtA, int dtB, int dtC, float* stats, hipStream_t stream,
                           const float* cscale = nullptr, const float* cshift = nullptr, const float* ascale = nullptr,
-                          const float* ashift = nullptr, bool x3 = false, const BnBwdEpilogue* bnb = nullptr, const X3Planes* pl = nullptr, int nplanes = 3) {
+                          const float* ashift = nullptr, bool x3 = false, const BnBwdEpilogue* bnb = nullptr, int nplanes = 3) {
   if (M <= 0 || N <= 0 || K <= 0) return CRNN_ERR_ARG;
-  if (pl && !x3) return CRNN_ERR_ARG;
-  if (nplanes != 3 && (nplanes != 2 || !x3 || pl)) return CRNN_ERR_ARG;
+  if (nplanes != 3 && (nplanes != 2 || !x3)) return CRNN_ERR_ARG;
   if (bnb && (bias || act || accumulate || permP || stats || cscale || ascale || dtC != CRNN_F32 || !bnb->d || !bnb->bnstate || !bnb->partials)) return CRNN_ERR_ARG;
   if (x3 && (dtA != CRNN_F32 || dtB != CRNN_F32)) return CRNN_ERR_ARG;   // three-plane products: fp32 operands
   if (x3 && ascale && (mode == 1 || (mode == 0 && K > TR_TAB) || bnb)) return CRNN_ERR_UNSUPPORTED;   // producer prologue of the three-plane kernel: modes 0 and 2
@@ -1242,7 +1178,6 @@ static int gemm_bf16_impl(int mode, const void* A, const void* B, void* C, int M
   { const char* e = getenv("CRNN_GEMM_TRACE"); p.trace = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
 #endif
   p.stats = stats; p.cscale = cscale; p.cshift = cshift; p.ascale = ascale; p.ashift = ashift;
-  p.Apl = pl ? pl->a : nullptr; p.apls = pl ? pl->as : 0; p.Bpl = pl ? pl->b : nullptr; p.bpls = pl ? pl->bs : 0;
   p.bnD = bnb ? bnb->d : nullptr; p.ldd = bnb ? bnb->ldd : 0; p.bnstate = bnb ? bnb->bnstate : nullptr; p.bnpart = bnb ? bnb->partials : nullptr;
   if ((ascale != nullptr) != (ashift != nullptr)) return CRNN_ERR_ARG;
   p.A = (const float*)A; p.B = (const float*)B; p.C = (float*)C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
@@ -1295,9 +1230,6 @@ static int gemm_bf16_impl(int mode, const void* A, const void* B, void* C, int M
   const bool full = (M % 128 == 0) && (N % BN == 0) && (K % HBK == 0) && p.vecA && p.vecB && p.vecC && crnn_knob("CRNN_GEMM_FULL", 1);
   // the BatchNorm-backward statistics live in the unguarded epilogue of an unsplit product: whole tiles, 16-byte accesses to d and the state
   if (bnb && (!full || nsplit > 1 || (bnb->ldd & 3) || ((uintptr_t)bnb->d & 15) || ((uintptr_t)bnb->bnstate & 15))) return CRNN_ERR_UNSUPPORTED;
-  // plane operands: whole tiles, 8-byte plane items (the unsplit kernel's 16-byte rule on the fp32 operand covers ld and the extents)
-  const bool apl = p.Apl != nullptr, bpl = p.Bpl != nullptr;
-  if ((apl || bpl) && (!full || (apl && (((uintptr_t)p.Apl & 7) || (p.apls & 3))) || (bpl && (((uintptr_t)p.Bpl & 7) || (p.bpls & 3))))) return CRNN_ERR_UNSUPPORTED;
 #define LAUNCH(BNV, AK, BKM, ABF, BBF) do { if (full) hipLaunchKernelGGL((gemm_bf16_kernel<BNV, AK, BKM, ABF, BBF, false, true>), grid, block, 0, stream, pk); \
                                             else hipLaunchKernelGGL((gemm_bf16_kernel<BNV, AK, BKM, ABF, BBF>), grid, block, 0, stream, pk); } while (0)
 #define LAUNCH_BN(AK, BKM, ABF, BBF) do { if (BN == 128) LAUNCH(128, AK, BKM, ABF, BBF); else LAUNCH(64, AK, BKM, ABF, BBF); } while (0)
@@ -1317,42 +1249,37 @@ static int gemm_bf16_impl(int mode, const void* A, const void* B, void* C, int M
   // producer-wave kernel (768 threads, two 32-k stages in LDS); -DCRNN_X3_INWAVE keeps the in-wave pipeline above for scripts/gemm_x3_trace.py
 #define LAUNCH_X3P(BNV, AK, BKM, FL, NPLV) do { constexpr int ldsr = 2 * NPLV * ((AK ? PBK * KLD(128) * 2 : 128 * PLD * 2) + (BKM ? PBK * KLD(BNV) * 2 : BNV * PLD * 2)); \
     constexpr int ldsp = ldsr > 36 * 1024 ? ldsr : 36 * 1024;   /* (the epilogue's staging tile reuses the stages: <= 34.8 KiB) */ \
-    CRNN_LDS_ATTR((gemm_x3p_kernel<BNV, AK, BKM, FL, false, false, false, false, NPLV>), ldsp); \
-    hipLaunchKernelGGL((gemm_x3p_kernel<BNV, AK, BKM, FL, false, false, false, false, NPLV>), grid, dim3(256 + X3P_STAGERS), ldsp, stream, pk); } while (0)
+    CRNN_LDS_ATTR((gemm_x3p_kernel<BNV, AK, BKM, FL, false, false, NPLV>), ldsp); \
+    hipLaunchKernelGGL((gemm_x3p_kernel<BNV, AK, BKM, FL, false, false, NPLV>), grid, dim3(256 + X3P_STAGERS), ldsp, stream, pk); } while (0)
 #define LAUNCH_X3PN(BNV, AK, BKM, FL) do { if (nplanes == 2) LAUNCH_X3P(BNV, AK, BKM, FL, 2); else LAUNCH_X3P(BNV, AK, BKM, FL, 3); } while (0)
 #define LAUNCH_X3PM(AK, BKM) do { if (BN == 128) { if (full) LAUNCH_X3PN(128, AK, BKM, true); else LAUNCH_X3PN(128, AK, BKM, false); } \
                                   else { if (full) LAUNCH_X3PN(64, AK, BKM, true); else LAUNCH_X3PN(64, AK, BKM, false); } } while (0)
   if (bnb) {      // (x3, mode 1, whole tiles: checked above)
     if (!x3 || mode != 1) return CRNN_ERR_UNSUPPORTED;
     constexpr int l128 = 2 * 3 * (128 * PLD * 2 + 128 * PLD * 2), l64 = 2 * 3 * (128 * PLD * 2 + 64 * PLD * 2);
-#define LAUNCH_X3PB(APLV, BPLV, NPLV) do { \
-    if (BN == 128) { CRNN_LDS_ATTR((gemm_x3p_kernel<128, false, false, true, true, false, APLV, BPLV, NPLV>), l128 / 3 * NPLV); \
-                     hipLaunchKernelGGL((gemm_x3p_kernel<128, false, false, true, true, false, APLV, BPLV, NPLV>), grid, dim3(256 + X3P_STAGERS), l128 / 3 * NPLV, stream, pk); } \
-    else { CRNN_LDS_ATTR((gemm_x3p_kernel<64, false, false, true, true, false, APLV, BPLV, NPLV>), l64 / 3 * NPLV); \
-           hipLaunchKernelGGL((gemm_x3p_kernel<64, false, false, true, true, false, APLV, BPLV, NPLV>), grid, dim3(256 + X3P_STAGERS), l64 / 3 * NPLV, stream, pk); } } while (0)
+#define LAUNCH_X3PB(NPLV) do { \
+    if (BN == 128) { CRNN_LDS_ATTR((gemm_x3p_kernel<128, false, false, true, true, false, NPLV>), l128 / 3 * NPLV); \
+                     hipLaunchKernelGGL((gemm_x3p_kernel<128, false, false, true, true, false, NPLV>), grid, dim3(256 + X3P_STAGERS), l128 / 3 * NPLV, stream, pk); } \
+    else { CRNN_LDS_ATTR((gemm_x3p_kernel<64, false, false, true, true, false, NPLV>), l64 / 3 * NPLV); \
+           hipLaunchKernelGGL((gemm_x3p_kernel<64, false, false, true, true, false, NPLV>), grid, dim3(256 + X3P_STAGERS), l64 / 3 * NPLV, stream, pk); } } while (0)
     static_assert(l64 / 3 * 2 >= 128 * (64 + 4) * 4 && l128 / 3 * 2 >= 64 * (128 + 4) * 4, "the epilogue's staging tile fits the two-plane stages");
-    if (nplanes == 2) LAUNCH_X3PB(false, false, 2);
-    else if (apl && bpl) LAUNCH_X3PB(true, true, 3); else if (bpl) LAUNCH_X3PB(false, true, 3); else if (apl) return CRNN_ERR_UNSUPPORTED; else LAUNCH_X3PB(false, false, 3);
+    if (nplanes == 2) LAUNCH_X3PB(2); else LAUNCH_X3PB(3);
 #undef LAUNCH_X3PB
   } else
   if (x3 && ascale) {   // modes 0 / 2 with the producer prologue (+ 4 KiB of LDS for mode 0's channel table)
-#define LAUNCH_X3PT(BNV, AK, BKM, FL, BPLV, NPLV) do { constexpr int ldsr = 2 * NPLV * ((AK ? PBK * KLD(128) * 2 : 128 * PLD * 2) + (BKM ? PBK * KLD(BNV) * 2 : BNV * PLD * 2)); \
+#define LAUNCH_X3PT(BNV, AK, BKM, FL, NPLV) do { constexpr int ldsr = 2 * NPLV * ((AK ? PBK * KLD(128) * 2 : 128 * PLD * 2) + (BKM ? PBK * KLD(BNV) * 2 : BNV * PLD * 2)); \
     constexpr int ldst = (ldsr > 36 * 1024 ? ldsr : 36 * 1024) + (AK ? 0 : 2 * TR_TAB * 4);   /* (the epilogue's staging tile reuses the stages: <= 34.8 KiB) */ \
     static_assert(!(NPLV == 2 && !AK) || ldsr >= 36 * 1024, "mode 0: the channel table sits right behind the stages"); \
-    CRNN_LDS_ATTR((gemm_x3p_kernel<BNV, AK, BKM, FL, false, true, false, BPLV, NPLV>), ldst); \
-    hipLaunchKernelGGL((gemm_x3p_kernel<BNV, AK, BKM, FL, false, true, false, BPLV, NPLV>), grid, dim3(256 + X3P_STAGERS), ldst, stream, pk); } while (0)
-#define LAUNCH_X3PTM(AK, BKM) do { \
-    if (nplanes == 2) { if (BN == 128) { if (full) LAUNCH_X3PT(128, AK, BKM, true, false, 2); else LAUNCH_X3PT(128, AK, BKM, false, false, 2); } \
-                        else { if (full) LAUNCH_X3PT(64, AK, BKM, true, false, 2); else LAUNCH_X3PT(64, AK, BKM, false, false, 2); } } \
-    else if (BN == 128) { if (bpl) LAUNCH_X3PT(128, AK, BKM, true, true, 3); else if (full) LAUNCH_X3PT(128, AK, BKM, true, false, 3); else LAUNCH_X3PT(128, AK, BKM, false, false, 3); } \
-    else { if (bpl) LAUNCH_X3PT(64, AK, BKM, true, true, 3); else if (full) LAUNCH_X3PT(64, AK, BKM, true, false, 3); else LAUNCH_X3PT(64, AK, BKM, false, false, 3); } } while (0)
-    if (apl) return CRNN_ERR_UNSUPPORTED;
+    CRNN_LDS_ATTR((gemm_x3p_kernel<BNV, AK, BKM, FL, false, true, NPLV>), ldst); \
+    hipLaunchKernelGGL((gemm_x3p_kernel<BNV, AK, BKM, FL, false, true, NPLV>), grid, dim3(256 + X3P_STAGERS), ldst, stream, pk); } while (0)
+#define LAUNCH_X3PTN(BNV, AK, BKM, FL) do { if (nplanes == 2) LAUNCH_X3PT(BNV, AK, BKM, FL, 2); else LAUNCH_X3PT(BNV, AK, BKM, FL, 3); } while (0)
+#define LAUNCH_X3PTM(AK, BKM) do { if (BN == 128) { if (full) LAUNCH_X3PTN(128, AK, BKM, true); else LAUNCH_X3PTN(128, AK, BKM, false); } \
+                                   else { if (full) LAUNCH_X3PTN(64, AK, BKM, true); else LAUNCH_X3PTN(64, AK, BKM, false); } } while (0)
     if (mode == 0) LAUNCH_X3PTM(false, true); else LAUNCH_X3PTM(true, true);
 #undef LAUNCH_X3PTM
+#undef LAUNCH_X3PTN
 #undef LAUNCH_X3PT
   } else
-  if (x3 && (apl || bpl)) return CRNN_ERR_UNSUPPORTED;   // (plane operands: the two fused forms above)
-  else
 #ifdef CRNN_X3_INWAVE
   if (x3 && nplanes != 3) return CRNN_ERR_UNSUPPORTED;
   else if (x3) { if (mode == 0) LAUNCH_X3M(false, true); else if (mode == 1) LAUNCH_X3M(false, false); else LAUNCH_X3M(true, true); }
@@ -1407,23 +1334,12 @@ extern "C" int crnn_gemm_f32x3_bnstats(const float* dq, const float* W, float* d
   return gemm_bf16_impl(1, dq, W, da, (int)M, N, K, K, K, N, nullptr, 0, 0, 0, nullptr, 0, CRNN_F32, CRNN_F32, CRNN_F32, nullptr, stream, nullptr, nullptr,
                         nullptr, nullptr, true, &e);
 }
-// ... with operands that were split once instead of per tile: W_planes (and, optionally, dq_planes) from crnn_split3_planes, the plane stride given per
-// operand.  Null planes: that operand is split from fp32 while staging, as above.  The LDS stages are the same words either way: bit-identical results.
-extern "C" int crnn_gemm_f32x3_bnstats_pl(const float* dq, const void* dq_planes, long dq_plane_stride, const float* W, const void* W_planes,
-                                          long W_plane_stride, float* da, long M, int N, int K, const float* d, const float* bnstate, float* stat_partials,
-                                          hipStream_t stream) {
-  CRNN_TRY(crnn_gemm_f32x3_bnstats_supported(M, N, K));
-  const BnBwdEpilogue e{d, N, bnstate, stat_partials};
-  const X3Planes pl{(const unsigned short*)dq_planes, dq_plane_stride, (const unsigned short*)W_planes, W_plane_stride};
-  return gemm_bf16_impl(1, dq, W, da, (int)M, N, K, K, K, N, nullptr, 0, 0, 0, nullptr, 0, CRNN_F32, CRNN_F32, CRNN_F32, nullptr, stream, nullptr, nullptr,
-                        nullptr, nullptr, true, &e, (dq_planes || W_planes) ? &pl : nullptr);
-}
 // crnn_gemm_f32x3 with two planes per operand (hi*hi + hi*mid + mid*hi: 16 significant bits per factor): same contract
 extern "C" int crnn_gemm_f32x2(int mode, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb,
                                int ldc, const float* bias, int act, int accumulate, int permP, float* scratch,
                                size_t scratch_bytes, hipStream_t stream) {
   return gemm_bf16_impl(mode, A, B, C, M, N, K, lda, ldb, ldc, bias, act, accumulate, permP, scratch, scratch_bytes, CRNN_F32, CRNN_F32, CRNN_F32,
-                        nullptr, stream, nullptr, nullptr, nullptr, nullptr, true, nullptr, nullptr, 2);
+                        nullptr, stream, nullptr, nullptr, nullptr, nullptr, true, nullptr, 2);
 }
 // Two-plane form of crnn_gemm_f32x3_bnstats: operands split into two bf16 planes, products hi*hi + hi*mid + mid*hi (16 significant bits per factor,
 // fp32 accumulation; relative error of a product <= 3 * 2^-18): half the MFMA work.  The parity mode's default for the BACKWARD GEMMs of the conv stack.
@@ -1432,11 +1348,10 @@ extern "C" int crnn_gemm_f32x2_bnstats(const float* dq, const float* W, float* d
   CRNN_TRY(crnn_gemm_f32x3_bnstats_supported(M, N, K));
   const BnBwdEpilogue e{d, N, bnstate, stat_partials};
   return gemm_bf16_impl(1, dq, W, da, (int)M, N, K, K, K, N, nullptr, 0, 0, 0, nullptr, 0, CRNN_F32, CRNN_F32, CRNN_F32, nullptr, stream, nullptr, nullptr,
-                        nullptr, nullptr, true, &e, nullptr, 2);
+                        nullptr, nullptr, true, &e, 2);
 }
 // The three bf16 planes of n fp32 values (n % 4 == 0, x 16-byte and planes 8-byte aligned, plane_stride % 4 == 0 elements): plane pl of x[i] at
-// planes[pl * plane_stride + i] -- the words the three-plane kernel's staging waves form (split3_pair), so a GEMM fed with them computes what it
-// computes from x, bit for bit.
+// planes[pl * plane_stride + i] -- the words the three-plane kernel's staging waves form (split3_pair).
 __global__ __launch_bounds__(256) void split3_planes_kernel(const float4* __restrict__ x, uint2* __restrict__ planes, long n4, long ps4) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;

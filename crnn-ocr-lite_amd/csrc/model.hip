@@ -160,8 +160,6 @@ bool rnn_persist(const crnn_config* c) {
   return (c->gru ? crnn_gru_persist_supported(c->units, rnn_dtu(c)) : crnn_lstm_persist_supported(c->units, rnn_dtu(c))) == 0;
 }
 
-size_t deferred_scratch_bytes(const crnn_config* cfg, const Dims& d);   // (defined with the deferred second stages below)
-
 // uw argument of the persistent recurrences: automatic workgroup size, XCD-local clusters unless the linear map is asked for.
 // Measured at B = 256, u = 256 (profiles/r03_lstm_cache_policy.txt): with the XCD-local map and, once a cluster has verified that its
 // members share an XCD, plain exchange stores the LSTM forward takes 98 us per layer (linear map + write-through stores: 131) and the
@@ -262,31 +260,20 @@ Plan make_plan(const crnn_config* c) {
     P.add("keep9", (TB * 2 * d.u / 8 + 3) / 4);   // keep bytes of the Dropout(.2) under dense2 (written by the forward's dropout pass, read by the one-pass backward)
   }
   P.add("pbf", make_layout(c).total, CRNN_BF16);   // bf16 shadow of the parameter buffer (GEMM B operands in the bf16 modes)
-  if (!c->mfma_bf16) {   // parity mode: bf16 planes of the pointwise-conv weights (CRNN_FLAG_WEIGHT_PLANES, weight_planes below); 3 planes x the b2_pw .. b7_pw span
-    const Layout L = make_layout(c);
-    P.add("p3", 3 * (L.off("b7_pw") + pad4((long)d.bc[6] * d.bc[7]) - L.off("b2_pw")), CRNN_BF16);
-  }
   P.add("coef", 2 * 1024);
   P.add("fold", 32 * 2 * 1024);   // chunk sums of long BatchNorm partial lists (crnn_bn_finalize_folded)
   P.add("gemm_scratch", 16L * 1024 * 1024);   // 64 MiB of split-reduction partials (main stream)
   P.add("gemm_scratch2", 16L * 1024 * 1024);  // the same for the side stream of the backward
   P.add("partials2", lmax((long)crnn_colreduce_chunks(TB) * lmax(d.G, lmax(d.tds, d.C)), 1024));
-  if (c->mfma_bf16 && (c->flags & CRNN_FLAG_DEFERRED_SUMS) && !(c->flags & CRNN_FLAG_GEMM_TILE_KERNELS))
-    P.add("wgrad_scratch", (long)(deferred_scratch_bytes(c, d) / sizeof(float)) + 64);   // partial tiles of the deferred weight-gradient second stages
   if (rnn_persist(c)) P.add("rnnx", (long)((crnn_lstm_persist_xbuf_bytes(d.T, d.B, d.u, rnn_dtu(c)) + 3) / 4));   // h_t / dz_t exchange tiles
   return P;
 }
 
 const size_t kGemmScratchBytes = 64UL * 1024 * 1024;
 
-// Second stages of the streaming weight gradients, collected over a backward stage and run as one launch (crnn_wgrad_sum_batch): each
-// deferred first stage keeps its partial tiles in its own piece of the "wgrad_scratch" workspace tensor until the flush.
-struct Deferred { std::vector<crnn_sum_job> jobs; size_t used = 0, cap = 0; float* base = nullptr; };
-
 struct Ctx {
   const crnn_config* cfg; Dims d; Layout L; Plan P;
   const float* params; float* grads; float* ws; hipStream_t s;
-  Deferred* def = nullptr;   // null: every second stage right after its first stage
   const float* p(const std::string& n) const { return params + L.off(n); }
   float* g(const std::string& n) const { return grads + L.off(n); }
   float* w(const std::string& n) const { return ws + P.off(n); }
@@ -350,27 +337,6 @@ bool wres3_on(const crnn_config* cfg, int reduction) {
 }
 // ... as crnn_pwconv_fwd's product selector for a forward conv of the stack (3 = two planes)
 int pw_products_fwd(const crnn_config* cfg) { return (pw_products(cfg) == 2 && conv_planes(cfg, false) == 2) ? 3 : pw_products(cfg); }
-// Parity mode with three-plane GEMMs, CRNN_FLAG_WEIGHT_PLANES (opt-in): the pointwise weights of blocks 2..7 are split into their bf16 planes ONCE, at
-// the start of the forward pass (crnn_split3_planes over the b2_pw .. b7_pw span of the parameter buffer -> workspace tensor "p3"), instead of by
-// every tile of the forward and data-gradient GEMMs that stages them (a tile of 128 rows re-splits the whole weight matrix).  Same words in LDS:
-// bit-identical.  Not the default: the staging waves pay more for three 8-byte loads per item than for the split arithmetic (include/crnn_mi355x.h).
-// `stride` = elements between planes; null: no planes for this weight.
-struct WeightPlanes { long lo = 0, n = 0; };
-WeightPlanes weight_planes_span(const Ctx& c) {
-  WeightPlanes s;
-  if (pw_products(c.cfg) != 2 || !(c.cfg->flags & CRNN_FLAG_WEIGHT_PLANES) || c.P.off("p3") < 0) return s;
-  s.lo = c.L.off("b2_pw"); s.n = c.L.off("b7_pw") + pad4((long)c.d.bc[6] * c.d.bc[7]) - s.lo;
-  if (((uintptr_t)(c.params + s.lo) & 15) || (s.n & 3)) s.n = 0;
-  return s;
-}
-const void* weight_planes(const Ctx& c, const float* w, long* stride, bool backward) {
-  *stride = 0;
-  if (conv_planes(c.cfg, backward) != 3) return nullptr;        // (the planes tensor holds three planes)
-  const WeightPlanes s = weight_planes_span(c);
-  *stride = s.n;
-  if (!s.n || w < c.params + s.lo || w >= c.params + s.lo + s.n || ((w - c.params - s.lo) & 3)) return nullptr;
-  return reinterpret_cast<const bf16_t*>(c.ws + c.P.off("p3")) + (w - c.params - s.lo);
-}
 // GEMM with explicit operand / result storage types (storage mode 2); falls back to the plain entry points otherwise
 int gemm_t(const Ctx& c, int mode, const float* A, int dtA, const float* B, int dtB, float* C, int dtC, int M, int N, int K, int lda,
            int ldb, int ldc, const float* bias = nullptr, int act = 0, int acc = 0, int perm = 0, int planes = 3) {
@@ -433,35 +399,6 @@ const float* keep_bytes(const Ctx& c, int i) { return c.cfg->dropout ? c.w("dm" 
 int gemm32(const Ctx& c, int mode, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
            const float* bias = nullptr, int act = 0, int acc = 0, int perm = 0) {
   return crnn_gemm_f32(mode, A, B, C, M, N, K, lda, ldb, ldc, bias, act, acc, perm, c.scratch(), kGemmScratchBytes, c.s);
-}
-
-int flush_deferred(const Ctx& c) {
-  if (!c.def || c.def->jobs.empty()) return CRNN_OK;
-  const int rc = crnn_wgrad_sum_batch(c.def->jobs.data(), (int)c.def->jobs.size(), c.s);
-  c.def->jobs.clear(); c.def->used = 0;
-  return rc;
-}
-// a piece of the deferred scratch for `bytes` of partial tiles (null: not deferring, or it can never fit); flushes first when full
-float* deferred_scratch(const Ctx& c, size_t bytes, int* rc) {
-  *rc = CRNN_OK;
-  if (!c.def || bytes == 0 || bytes > c.def->cap) return nullptr;
-  if (c.def->used + bytes > c.def->cap || (int)c.def->jobs.size() >= CRNN_SUM_BATCH_MAX) { *rc = flush_deferred(c); if (*rc) return nullptr; }
-  float* ptr = c.def->base + c.def->used / sizeof(float);
-  c.def->used += (bytes + 255) & ~(size_t)255;
-  return ptr;
-}
-// bytes of deferred scratch one backward stage needs at most (make_plan)
-size_t deferred_scratch_bytes(const crnn_config* cfg, const Dims& d) {
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const long TB = (long)d.T * d.B, K1 = (long)(d.T - 1) * d.B;
-  const int Nh = cfg->gru ? 2 * d.u : d.G;
-  size_t top = 0, bottom = 0;
-  for (int l = 1; l <= 2; ++l) {
-    const int din = l == 1 ? d.tds : d.u;
-    top += 2 * al(crnn_pwconv_wgrad_stream_scratch_bytes(TB, d.G, din)) + 2 * al(crnn_pwconv_wgrad_stream_scratch_bytes(K1, Nh, d.u));
-  }
-  for (int i = 2; i <= 7; ++i) bottom += al(crnn_pwconv_wgrad_stream_scratch_bytes((long)d.B * d.bh[i] * d.bw[i], d.bc[i], d.bc[i - 1]));
-  return top > bottom ? top : bottom;
 }
 
 int colsum(const Ctx& c, const float* x, long M, int C, int ld, float* out) {
@@ -636,8 +573,6 @@ extern "C" int crnn_forward_ex(const crnn_config* cfg, const float* params, cons
     }
   }
   if (cfg->mfma_bf16) CRNN_TRY(crnn_convert_f32_to_bf16(params, c.ws + c.P.off("pbf"), c.L.total, stream));
-  { const WeightPlanes wp = weight_planes_span(c);   // parity mode, opt-in: the pointwise weights' bf16 planes, once per step
-    if (wp.n) CRNN_TRY(crnn_split3_planes(params + wp.lo, c.ws + c.P.off("p3"), wp.n, wp.n, stream)); }
   // ---- spatial transformer (utils.py:247-258) + ZeroPadding2D (utils.py:63)
   if (cfg->stn && loc_net_fused(cfg, d) && aligned16(c.p("stn_c1_k"), c.p("stn_c2_k"), c.p("stn_c1_b"), c.p("stn_c2_b")) &&
       aligned16(c.w("c1"), c.w("pool2"), c.w("flat"))) {
@@ -790,15 +725,14 @@ extern "C" int crnn_forward_ex(const crnn_config* cfg, const float* params, cons
       if (blk1) CRNN_TRY(crnn_pw1_bn_fwd(dd, s1, c.p(bp + "_pw"), qq, M, co, parts, dtq, stream));                      // block 1: outer product of relu6(BN(d))
       else if (ci == 1 && dtd == CRNN_F32) CRNN_TRY(crnn_pw1_fwd(aa, c.p(bp + "_pw"), qq, M, co, parts, dtq, stream));
       else if (fuse_x3) {
-        long wps = 0; const void* wpl = weight_planes(c, c.p(bp + "_pw"), &wps, false);
-        int rc = wpl ? crnn_pwconv_bnrelu6_fwd_f32x3_pl(dd, s1, c.p(bp + "_pw"), wpl, wps, qq, M, co, ci, parts, stream) : CRNN_ERR_UNSUPPORTED;
+        int rc = CRNN_ERR_UNSUPPORTED;
         // round 6: the weights' planes resident in registers, the pixel rows streamed once (gemm_wres3.hip) where that kernel wins: K <= 256
         // (at K = 512 the planes of a 128-channel slice do not fit a CU's registers next to the accumulators: the tile kernel stays)
-        if (rc == CRNN_ERR_UNSUPPORTED && wres3_on(cfg, ci) && crnn_gemm_wres3_supported(M, co, ci) == CRNN_OK) {
+        if (wres3_on(cfg, ci) && crnn_gemm_wres3_supported(M, co, ci) == CRNN_OK) {
           rc = crnn_pwconv_bnrelu6_fwd_wres3(dd, s1, c.p(bp + "_pw"), qq, M, co, ci, conv_planes(cfg, false), parts, stream);
           if (rc == CRNN_OK) stat_rows = crnn_gemm_wres3_stat_rows(M, co, ci);
         }
-        if (rc == CRNN_ERR_UNSUPPORTED)      // (no planes, or ragged tiles: split while staging)
+        if (rc == CRNN_ERR_UNSUPPORTED)      // the tile kernel, splitting the weights while staging
           rc = conv_planes(cfg, false) == 2 ? crnn_pwconv_bnrelu6_fwd_f32x2(dd, s1, c.p(bp + "_pw"), qq, M, co, ci, parts, stream)
                                             : crnn_pwconv_bnrelu6_fwd_f32x3(dd, s1, c.p(bp + "_pw"), qq, M, co, ci, parts, stream);
         CRNN_TRY(rc);
@@ -992,15 +926,6 @@ static int rnn_bwd_chain(const Ctx& c, int layer, const float* hf, const float* 
 // rules hold (gemm_wgrad.hip, fp32 operands rounded to bf16 on the way in like the tile GEMM does), else the tile GEMM
 static int gemm_tn(const Ctx& c, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc) {
   if (c.cfg->mfma_bf16 && !(c.cfg->flags & CRNN_FLAG_GEMM_TILE_KERNELS)) {
-    const size_t need = c.def ? crnn_pwconv_wgrad_stream_scratch_bytes(K, N, M) : 0;
-    int rc0 = CRNN_OK;
-    if (float* sc = deferred_scratch(c, need, &rc0)) {      // first stage now, the fixed-order sum with the stage's other second stages
-      crnn_sum_job job;
-      const int rc = crnn_gemm_tn_stream_defer(A, lda, B, ldb, C, ldc, M, N, K, sc, need, &job, c.s);
-      if (rc == CRNN_OK) { c.def->jobs.push_back(job); return CRNN_OK; }
-      if (rc != CRNN_ERR_UNSUPPORTED) return rc;
-    }
-    CRNN_TRY(rc0);
     const int rc = crnn_gemm_tn_stream(A, lda, B, ldb, C, ldc, M, N, K, c.scratch(), kGemmScratchBytes, c.s);
     if (rc != CRNN_ERR_UNSUPPORTED) return rc;
   }
@@ -1117,17 +1042,7 @@ namespace {
 // microseconds each and leave the GPU almost idle; the GEMMs fill it.  Only the aux stream touches the split-reduction
 // scratch and the reduction partials between the fork and the join, and every gradient tensor still has a single
 // writer in a fixed order, so the result is bit-identical to the serial schedule.
-// deferred second stages: serial schedule only (a side stream's first stages could not share one flush), bf16 modes with the streaming kernels
-void deferred_setup(const Ctx& c0, Ctx& c, Deferred& def, hipStream_t aux) {
-  c = c0;
-  const long off = c0.P.off("wgrad_scratch");
-  if (aux || off < 0) return;
-  def.base = c0.ws + off; def.cap = (size_t)(c0.P.cnt("wgrad_scratch") - 64) * sizeof(float);
-  c.def = &def;
-}
-
-int backward_top(const Ctx& c0, const int* labels, const int* input_length, const int* label_length, float* loss, uint64_t seed, hipStream_t aux) {
-  Deferred def; Ctx c; deferred_setup(c0, c, def, aux);
+int backward_top(const Ctx& c, const int* labels, const int* input_length, const int* label_length, float* loss, uint64_t seed, hipStream_t aux) {
   const crnn_config* cfg = c.cfg; float* grads = c.grads; hipStream_t stream = c.s;
   const Dims& d = c.d;
   const int B = d.B, T = d.T, TB = T * B, u = d.u;
@@ -1183,7 +1098,7 @@ int backward_top(const Ctx& c0, const int* labels, const int* input_length, cons
   if (rc1 != CRNN_OK && rc1 != CRNN_ERR_UNSUPPORTED) return rc1;
   if (rc1 != CRNN_OK)
     CRNN_TRY(gemm_t(c, 1, c.w("gbm"), CRNN_F32, c.p("dense1_w"), CRNN_F32, gA, c.gdt(), TB, d.feat, d.tds, d.tds, d.tds, d.feat, nullptr, 0, 0, 0, conv_planes(cfg, true)));
-  return flush_deferred(c);                             // every gradient of this stage is final (a data-parallel host exchanges them now)
+  return CRNN_OK;
 }
 
 // aux != nullptr: the pointwise weight-gradient GEMM of every block runs on the side stream next to the rest of the block's
@@ -1191,8 +1106,7 @@ int backward_top(const Ctx& c0, const int* labels, const int* input_length, cons
 // matrix cores and most of the vector-memory path idle).  The GEMM reads the BatchNorm-2 input gradient of its block, so the
 // gradient buffers rotate over three allocations and the main stream waits for GEMM i before the buffer it reads is written
 // again (by the depthwise stage of block i-1).  One writer per gradient tensor, fixed order: bit-identical to the serial schedule.
-int backward_bottom(const Ctx& c0, const float* x, uint64_t seed, hipStream_t aux) {
-  Deferred def; Ctx c; deferred_setup(c0, c, def, aux);
+int backward_bottom(const Ctx& c, const float* x, uint64_t seed, hipStream_t aux) {
   const crnn_config* cfg = c.cfg; hipStream_t stream = c.s;
   const Dims& d = c.d;
   const int B = d.B;
@@ -1220,7 +1134,7 @@ int backward_bottom(const Ctx& c0, const float* x, uint64_t seed, hipStream_t au
     // planes (the bytes of the fp32 tensor) by the BatchNorm backward, so that neither GEMM splits it: the data gradient runs from the planes by LDS-DMA
     // with the weight planes resident (gemm_pres.hip), the weight gradient's IO waves copy them (gemm_wgrad3.hip).  Same words, same products.
     const bool dq_planes = !fused_bf && pw_products(cfg) == 2 && conv_planes(cfg, true) == 2 && dtq == CRNN_F32 && dtd == CRNN_F32 && fuse_dw_bn_x3(cfg, dtd, dtq, ci) &&
-                           !(cfg->flags & (CRNN_FLAG_GEMM_TILE_KERNELS | CRNN_FLAG_NO_BN_STATS_FUSION | CRNN_FLAG_NO_GRADIENT_PLANES | CRNN_FLAG_WEIGHT_PLANES)) &&
+                           !(cfg->flags & (CRNN_FLAG_GEMM_TILE_KERNELS | CRNN_FLAG_NO_BN_STATS_FUSION | CRNN_FLAG_NO_GRADIENT_PLANES)) &&
                            (kBlocks[i - 1].ph * kBlocks[i - 1].pw == 1 || crnn_knob("CRNN_DQPL_POOL", 1)) &&
                            crnn_gemm_pres_supported(M, ci, co, 2) == CRNN_OK && crnn_pwconv_wgrad_planes_stream_supported(M, co, ci) == CRNN_OK &&
                            crnn_pwconv_wgrad_planes_stream_scratch_bytes(M, co, ci) <= kGemmScratchBytes &&
@@ -1258,18 +1172,8 @@ int backward_bottom(const Ctx& c0, const float* x, uint64_t seed, hipStream_t au
       if (side) CRNN_TRY(fj.fork());
       if (fuse_dw_bn(cfg, dtd, dtq, ci)) {  // the activated tensor was never written: re-form it from d while staging (as the forward did)
         int rc = CRNN_ERR_UNSUPPORTED;        // pixel-streaming kernel (gemm_wgrad.hip) where its shape rules hold, else the tile GEMM
-        if (!(cfg->flags & CRNN_FLAG_GEMM_TILE_KERNELS) && crnn_pwconv_wgrad_stream_supported(M, co, ci) == CRNN_OK) {
-          const size_t need = cw.def ? crnn_pwconv_wgrad_stream_scratch_bytes(M, co, ci) : 0;
-          int rc0 = CRNN_OK;
-          if (float* sc = deferred_scratch(cw, need, &rc0)) {
-            crnn_sum_job job;
-            rc = crnn_pwconv_bnrelu6_wgrad_stream_defer(c.w("d" + p), c.w("bn1s" + p), gB, c.g(bp + "_pw"), M, co, ci, sc, need, &job, cw.s);
-            if (rc == CRNN_OK) cw.def->jobs.push_back(job);
-          }
-          CRNN_TRY(rc0);
-          if (rc == CRNN_ERR_UNSUPPORTED)
-            rc = crnn_pwconv_bnrelu6_wgrad_stream(c.w("d" + p), c.w("bn1s" + p), gB, c.g(bp + "_pw"), M, co, ci, cw.scratch(), kGemmScratchBytes, cw.s);
-        }
+        if (!(cfg->flags & CRNN_FLAG_GEMM_TILE_KERNELS) && crnn_pwconv_wgrad_stream_supported(M, co, ci) == CRNN_OK)
+          rc = crnn_pwconv_bnrelu6_wgrad_stream(c.w("d" + p), c.w("bn1s" + p), gB, c.g(bp + "_pw"), M, co, ci, cw.scratch(), kGemmScratchBytes, cw.s);
         if (rc == CRNN_ERR_UNSUPPORTED)
           rc = crnn_pwconv_bnrelu6_wgrad(c.w("d" + p), c.w("bn1s" + p), gB, c.g(bp + "_pw"), M, co, ci, cw.scratch(), kGemmScratchBytes, cw.s);
         CRNN_TRY(rc);
@@ -1310,16 +1214,14 @@ int backward_bottom(const Ctx& c0, const float* x, uint64_t seed, hipStream_t au
       // parity mode: the three-plane GEMM's epilogue takes the statistics pass of the depthwise BatchNorm's backward (it holds the finished da tile)
       if (rc == CRNN_ERR_UNSUPPORTED && !fused_bf && pw_products(cfg) == 2 && dtq == CRNN_F32 && dtd == CRNN_F32 &&
           !(cfg->flags & CRNN_FLAG_NO_BN_STATS_FUSION) && crnn_gemm_f32x3_bnstats_supported(M, ci, co) == CRNN_OK) {
-        long wps = 0; const void* wpl = weight_planes(c, c.p(bp + "_pw"), &wps, true);
         int w3_rows = 0;
-        if (wres3_on(cfg, co) && !wpl && crnn_gemm_wres3_supported(M, ci, co) == CRNN_OK) {   // round 6: W^T planes resident, dq streamed once (gemm_wres3.hip)
+        if (wres3_on(cfg, co) && crnn_gemm_wres3_supported(M, ci, co) == CRNN_OK) {   // round 6: W^T planes resident, dq streamed once (gemm_wres3.hip)
           rc = crnn_gemm_wres3_bnstats(gB, c.p(bp + "_pw"), gA, M, ci, co, conv_planes(cfg, true), c.w("d" + p), c.w("bn1s" + p), c.w("partials"), stream);
           if (rc == CRNN_OK) { w3_rows = crnn_gemm_wres3_stat_rows(M, ci, co); }
         }
         if (rc != CRNN_ERR_UNSUPPORTED) {}
         else if (conv_planes(cfg, true) == 2) rc = crnn_gemm_f32x2_bnstats(gB, c.p(bp + "_pw"), gA, M, ci, co, c.w("d" + p), c.w("bn1s" + p), c.w("partials"), stream);
-        else rc = crnn_gemm_f32x3_bnstats_pl(gB, nullptr, 0, c.p(bp + "_pw"), wpl, wps, gA, M, ci, co, c.w("d" + p), c.w("bn1s" + p), c.w("partials"), stream);
-        if (rc == CRNN_ERR_UNSUPPORTED && wpl) rc = crnn_gemm_f32x3_bnstats(gB, c.p(bp + "_pw"), gA, M, ci, co, c.w("d" + p), c.w("bn1s" + p), c.w("partials"), stream);
+        else rc = crnn_gemm_f32x3_bnstats(gB, c.p(bp + "_pw"), gA, M, ci, co, c.w("d" + p), c.w("bn1s" + p), c.w("partials"), stream);
         bn1_stats_rows = (rc == CRNN_OK) ? (w3_rows ? w3_rows : crnn_gemm_f32x3_bnstats_rows(M)) : 0;
       }
       if (rc == CRNN_ERR_UNSUPPORTED) rc = gemm_t(c, 1, gB, dtq, c.p(bp + "_pw"), CRNN_F32, gA, dtd, (int)M, ci, co, co, co, ci, nullptr, 0, 0, 0, conv_planes(cfg, true));
@@ -1378,7 +1280,6 @@ int backward_bottom(const Ctx& c0, const float* x, uint64_t seed, hipStream_t au
     if (i > 1 || cfg->stn) CRNN_TRY(crnn_dwconv3x3_fwd_ex(gB, c.p(bp + "_dw"), gA, nullptr, B, H, W, ci, 1, dtd, stream));
   }
   CRNN_TRY(fj.join());                                   // every weight gradient is complete in the main stream's order
-  CRNN_TRY(flush_deferred(c));
   // ---- spatial transformer
   if (cfg->stn) {
     CRNN_TRY(crnn_sampler_bwd(x, c.w("theta"), gA, c.w("dtheta"), B, d.H0, d.W0, 2, stream));

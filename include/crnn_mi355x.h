@@ -88,13 +88,7 @@ typedef struct {
                                          bit-identical, the weight gradient and the statistics the same sums in another order) */
 #define CRNN_FLAG_NO_POOL_ARGMAX_Q 524288 /* the pooled blocks (3, 5): the statistics pass of BatchNorm-2's backward re-reads the whole pre-BatchNorm tensor and finds each
                                          window's arg-max again (rounds 1-5) instead of reading the value the forward saved per window (round 6: bit-identical sums) */
-#define CRNN_FLAG_WEIGHT_PLANES 32768    /* opt-in, parity mode: the pointwise GEMMs read bf16 planes of their weights split once per step (crnn_split3_planes +
-                                         the *_pl entry points) instead of splitting the fp32 weights in every tile that stages them; bit-identical.
-                                         Measured (profiles/r04_x3_planes_bench.txt): forward -2 %, data gradient +12 % -- three 8-byte loads per item
-                                         cost the staging waves more than the split arithmetic they save; step time unchanged.  Not the default */
-#define CRNN_FLAG_DEFERRED_SUMS 512      /* opt-in: second stage of every streaming weight gradient batched at the end of its backward stage
-                                         (crnn_wgrad_sum_batch: 2 launches instead of 13 per step) instead of right after its first stage;
-                                         bit-identical; measured neutral (6.583 vs 6.584 ms: the second stages are bandwidth, not launch latency) */
+/* bits 512 and 32768 are unassigned (retired schedules) and must not be reused; like any unassigned bit, they are ignored if set */
 #define CRNN_FLAG_F32_MFMA_GEMMS 256    /* parity mode (mfma_bf16 = 0): conv-stack / dense / RNN-projection GEMMs on v_mfma_f32_32x32x2_f32 (crnn_gemm_f32:
                                          an fmaf chain bit for bit) instead of three-plane bf16 products (crnn_gemm_f32x3: fp32-level accuracy, six bf16
                                          MFMAs per k-step, 1.2-1.7x faster per GEMM); results agree to fp32 round-off */
@@ -251,9 +245,6 @@ int crnn_pwconv_bnrelu6_wgrad(const void* d, const float* in_bnstate, const void
  * tensor is never written.  w [K][N] fp32, K <= 512; results equal the unfused sequence bit for bit; -3 outside the kernel's shape rules. */
 int crnn_pwconv_bnrelu6_fwd_f32x3(const float* d, const float* in_bnstate, const float* w, float* q, long M, int N, int K, float* stat_partials,
                                   crnn_stream_t stream);
-/* ... with the weights as planes (crnn_split3_planes of w [K][N]; null: the entry point above).  Whole tiles only (-3 otherwise). */
-int crnn_pwconv_bnrelu6_fwd_f32x3_pl(const float* d, const float* in_bnstate, const float* w, const void* w_planes, long w_plane_stride, float* q, long M,
-                                     int N, int K, float* stat_partials, crnn_stream_t stream);
 int crnn_pwconv_bnrelu6_wgrad_f32x3(const float* d, const float* in_bnstate, const float* g, float* dw, long M, int N, int K, float* scratch,
                                     size_t scratch_bytes, crnn_stream_t stream);
 /* Round 6: the same forward product and the data gradient with the WEIGHTS' PLANES RESIDENT IN REGISTERS (gemm_wres3.hip; replaces Keras' Conv2D(1x1)
@@ -601,15 +592,10 @@ int crnn_pwconv_bnrelu6_fwd_f32x2(const float* d, const float* in_bnstate, const
                                   crnn_stream_t stream);
 int crnn_pwconv_bnrelu6_wgrad_f32x2(const float* d, const float* in_bnstate, const float* g, float* dw, long M, int N, int K, float* scratch,
                                     size_t scratch_bytes, crnn_stream_t stream);
-/* The three bf16 planes of n fp32 values, formed once instead of by every GEMM tile that stages them: plane pl of x[i] at planes[pl * plane_stride + i]
- * (bf16 words; n % 4 == 0, plane_stride % 4 == 0 and >= n, x 16-byte and planes 8-byte aligned) -- the very words the three-plane kernel's staging waves
- * form, so the *_pl entry points below return what their fp32-operand forms return, bit for bit.  With CRNN_FLAG_WEIGHT_PLANES the parity-mode step splits the
- * pointwise-conv weights this way at the start of the forward pass. */
+/* The three bf16 planes of n fp32 values: plane pl of x[i] at planes[pl * plane_stride + i] (bf16 words; n % 4 == 0, plane_stride % 4 == 0 and >= n,
+ * x 16-byte and planes 8-byte aligned) -- the very words the three-plane kernel's staging waves form.  The reference for the plane format that
+ * crnn_gemm_pres_bnstats and crnn_bn_bwd_planes_ex / crnn_bn_bwd_apply_planes_ex use (the first two planes are the two-plane format). */
 int crnn_split3_planes(const float* x, void* planes, long n, long plane_stride, crnn_stream_t stream);
-/* crnn_gemm_f32x3_bnstats with operands given as planes (null planes: split from the fp32 operand while staging).  W_planes: planes of W [N][K];
- * dq_planes: planes of dq [M][K] (only together with W_planes).  The fp32 pointers stay required (alignment rules, fallback). */
-int crnn_gemm_f32x3_bnstats_pl(const float* dq, const void* dq_planes, long dq_plane_stride, const float* W, const void* W_planes, long W_plane_stride,
-                               float* da, long M, int N, int K, const float* d, const float* bnstate, float* stat_partials, crnn_stream_t stream);
 /* Inference forward of a pointwise convolution on the same kernel with the BatchNorm + ReLU6 that follows folded into the MFMA waves'
  * epilogue: y[M][N] (bf16) = ReLU6((a . wT^T) * scale[n] + shift[n]), out_bnstate = [mean|var|scale|shift] (crnn_bn_infer_state).
  * Bit-identical to crnn_pwconv_fwd(..., out_bnstate, ...) on bf16 tensors.  Same shape rules as crnn_gemm_wres_bf16. */
@@ -665,17 +651,6 @@ int crnn_gemm_tn_bf16_stream(const void* A, int lda, const void* B, int ldb, flo
 int crnn_dense_fwd_stream_supported(long M, int N, long K);
 int crnn_dense_fwd_stream(const void* X, const void* WT, const float* bias, float* Y, long M, int N, long K, int lda, int ldw, int relu, int permP,
                           float drop_rate, uint64_t seed, uint32_t layer, crnn_stream_t stream);
-/* Deferred second stages.  The two streaming weight-gradient entries above are stage 1 (partial tiles into `scratch`) + stage 2 (a fixed-order
- * sum into the gradient, ~5 us of dependent launch each, 13 per train step).  The *_defer forms run stage 1 only and describe stage 2 in
- * *job; crnn_wgrad_sum_batch runs up to CRNN_SUM_BATCH_MAX of them in ONE launch -- the same sums in the same order, bit-identical
- * gradients.  Each deferred call needs its own scratch until the batch has run (crnn_pwconv_wgrad_stream_scratch_bytes). */
-#define CRNN_SUM_BATCH_MAX 16
-typedef struct { const float* partials; float* out; long total; int nsplit, N, ldc; } crnn_sum_job;
-int crnn_pwconv_bnrelu6_wgrad_stream_defer(const void* d, const float* in_bnstate, const void* g, float* dw, long M, int N, int K,
-                                           float* scratch, size_t scratch_bytes, crnn_sum_job* job, crnn_stream_t stream);
-int crnn_gemm_tn_stream_defer(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, long K, float* scratch,
-                              size_t scratch_bytes, crnn_sum_job* job, crnn_stream_t stream);
-int crnn_wgrad_sum_batch(const crnn_sum_job* jobs, int n, crnn_stream_t stream);
 /* Input gradient of a Bidirectional layer's input projections in one streaming launch: Y[M][N] (fp32, row stride ldy) = A0[M][K] . W0[N][K]^T
  * (+ A1 . W1^T when A1 != NULL), A fp32 (rounded to bf16 on the way in), W bf16; one workgroup per 64-row stripe keeps its result in the
  * MFMA waves' registers over the whole reduction.  Supported (else -3): M % 64 == 0, N in {128, 256}, K % 64 == 0, leading dimensions

@@ -2035,41 +2035,6 @@ def test_split3_planes_are_the_three_bf16_terms_of_each_value(n, extra):
     assert L().crnn_split3_planes(P(x), P(pl), n, st + 2, S()) == -2
 
 
-@pytest.mark.parametrize("M,K,N", [(128 * 40, 128, 256), (128 * 6, 512, 512), (128 * 3, 256, 64), (128 * 200, 64, 128), (128 * 9, 64, 64)])
-def test_three_plane_gemms_read_operands_split_beforehand(M, K, N):
-    """The *_pl entry points (weights -- and the incoming gradient -- handed over as bf16 planes from crnn_split3_planes instead of being split by
-    every tile that stages them) must return the very bits of their fp32-operand forms: forward product + BatchNorm statistics
-    (crnn_pwconv_bnrelu6_fwd_f32x3_pl), data gradient + BatchNorm-backward statistics (crnn_gemm_f32x3_bnstats_pl with the weight planes alone and
-    with both operands as planes).  Plane strides with slack, both tile widths; ragged shapes are refused (-3: the caller falls back)."""
-    rs = np.random.RandomState(M % 1000 + N + K + 11)
-    d = dev((rs.normal(size=(M, K)) * 1.5 + 0.4).astype(np.float32)); w = dev((rs.normal(size=(K, N)) * 0.1).astype(np.float32))
-    st = dev(np.concatenate([rs.normal(size=K), rs.uniform(0.5, 2.0, size=K), rs.normal(size=K) * 0.3 + 1.0, rs.normal(size=K) * 0.5 + 0.5]).astype(np.float32))
-    rows = L().crnn_pwconv_stat_rows(M)
-    q0, q1 = zeros(M, N), torch.full((M + 2, N), 7.0, device="cuda"); p0, p1 = zeros(rows, 2, N), zeros(rows, 2, N)
-    ok(L().crnn_pwconv_bnrelu6_fwd_f32x3(P(d), P(st), P(w), P(q0), M, N, K, P(p0), S()))
-    wpl, ws = _planes_of(w, K * N + 64)
-    for rep in range(2):
-        ok(L().crnn_pwconv_bnrelu6_fwd_f32x3_pl(P(d), P(st), P(w), P(wpl), ws, P(q1), M, N, K, P(p1), S()))
-    assert torch.equal(q1[:M], q0) and bool((q1[M:] == 7.0).all()), "forward differs: max %g" % float((q1[:M] - q0).abs().max())
-    assert torch.equal(p1, p0) and float(q0.abs().max()) > 0
-    if K % 64 == 0:
-        # data gradient of the same conv: da [M][K] = dq [M][N] . W [K][N]^T  (the entry point's N = conv K, its K = conv N)
-        dq = dev(rs.normal(size=(M, N)).astype(np.float32))
-        bnstate = st                                               # [mean | var | scale | shift] of the conv's K input channels
-        assert L().crnn_gemm_f32x3_bnstats_supported(M, K, N) == 0
-        r = L().crnn_gemm_f32x3_bnstats_rows(M)
-        da0, da1, da2 = zeros(M, K), zeros(M, K), zeros(M, K); s0, s1, s2 = zeros(r * 2 * K), zeros(r * 2 * K), zeros(r * 2 * K)
-        ok(L().crnn_gemm_f32x3_bnstats(P(dq), P(w), P(da0), M, K, N, P(d), P(bnstate), P(s0), S()))
-        ok(L().crnn_gemm_f32x3_bnstats_pl(P(dq), None, 0, P(w), P(wpl), ws, P(da1), M, K, N, P(d), P(bnstate), P(s1), S()))
-        assert torch.equal(da1, da0) and torch.equal(s1, s0), "weight planes: data gradient differs: max %g" % float((da1 - da0).abs().max())
-        qpl, qs = _planes_of(dq)
-        ok(L().crnn_gemm_f32x3_bnstats_pl(P(dq), P(qpl), qs, P(w), P(wpl), ws, P(da2), M, K, N, P(d), P(bnstate), P(s2), S()))
-        assert torch.equal(da2, da0) and torch.equal(s2, s0), "both operands as planes: data gradient differs: max %g" % float((da2 - da0).abs().max())
-        assert L().crnn_gemm_f32x3_bnstats_pl(P(dq), P(qpl), qs, P(w), None, 0, P(da2), M, K, N, P(d), P(bnstate), P(s2), S()) == -3
-    # ragged tiles: refused
-    assert L().crnn_pwconv_bnrelu6_fwd_f32x3_pl(P(d), P(st), P(w), P(wpl), ws, P(q1), M - 3, N, K, P(p1), S()) == -3
-
-
 @pytest.mark.parametrize("M,K,N", [(128 * 40, 128, 256), (128 * 6, 512, 512), (128 * 3 + 5, 256, 64), (128 * 200, 64, 128), (1000, 64, 128)])
 def test_two_plane_gemms_carry_sixteen_bits_per_factor(M, K, N):
     """The f32x2 entry points (two bf16 planes per operand, products hi*hi + hi*mid + mid*hi, fp32 accumulation: the parity mode's backward GEMMs) against
