@@ -31,6 +31,8 @@ def build_parser():
     parser.add_argument('--imgW', type=int, default=32)
     parser.add_argument('--workers', type=int, default=0,
                         help='image decoding processes feeding the generator (0 = the reference\'s single-threaded loader)')
+    parser.add_argument('--device_ingest', action='store_true',
+                        help='build the batches on the GPU: pages go up as uint8 with a box table, one kernel crops, pads and normalises')
     return parser
 
 
@@ -59,7 +61,10 @@ def main(argv=None):
             fnames = fnames[int(len(fnames) * args.train_portion):]
     if args.num_instances is not None:
         fnames = fnames[np.random.randint(0, len(fnames), min(args.num_instances, len(fnames)))]
-    reader = U.Readf(img_size=img_size, normed=True, batch_size=args.batch_size, transform_p=0., classes=classes, max_len=args.max_len, workers=args.workers)
+    if args.device_ingest:
+        reader = U.DeviceReadf(img_size=img_size, normed=True, batch_size=args.batch_size, transform_p=0., classes=classes, max_len=args.max_len, workers=args.workers)
+    else:
+        reader = U.Readf(img_size=img_size, normed=True, batch_size=args.batch_size, transform_p=0., classes=classes, max_len=args.max_len, workers=args.workers)
     length = len(fnames)
     bboxs = {}
     if args.boxes is not None:

@@ -197,6 +197,32 @@ int crnn_ctc_greedy_decode(const float* y, const int* input_len, int* out, int* 
 int crnn_ctc_beam_decode(const float* y, const int* input_len, int* out, int* out_len, float* scores, int B, int T,
                          int C, int beam_width, int merge_repeated, crnn_stream_t stream);
 
+/* ---- input side: word crops of page images -> the batch crnn_forward reads (reference utils.py:364-416, open_img + norm) ---- */
+/* One crop.  The page is a row-major uint8 image at byte `page_off` of the arena; the crop is page[r0:r1, c0:c1] (hc x wc), rotated so that the
+ * text direction becomes axis 0: rot(i, j) = page[r0 + hc - 1 - j, c0 + i], shape (wc, hc).  upscale: wc <= imgh/2 and hc <= imgw/2 -- the content is
+ * rot resized to (int(wc*1.5), int(hc*1.5)) and rounded to uint8 first.  The content sits at (b0, b1) of a (p0, p1) image filled with the crop's modal
+ * grey value (the host makes the padding's placement decisions, random ones included: crnn_mi355x.ingest.plan_crop); that image is inverted when its
+ * values > 127 outnumber the others and is then resized to (imgh, imgw).  The scale factors are n_in / (double)n_out, computed by the caller: the device
+ * divides nothing. */
+typedef struct {
+  long page_off;                 /* byte offset of the page's first pixel in the arena */
+  int rows, cols, stride;        /* page size and row stride in bytes (stride >= cols) */
+  int r0, r1, c0, c1;            /* 0 <= r0 < r1 <= rows, 0 <= c0 < c1 <= cols */
+  int b0, b1, p0, p1;            /* content offset and padded size along axis 0 (time) and axis 1 */
+  int upscale;                   /* 1 exactly when wc <= imgh/2 and hc <= imgw/2 */
+  double up_scale0, up_scale1;   /* upscale: wc / (double)int(wc*1.5), hc / (double)int(hc*1.5); else ignored */
+  double out_scale0, out_scale1; /* p0 / (double)imgh, p1 / (double)imgw */
+} crnn_crop_item;
+/* out [batch][imgh][imgw] fp32 = table[open_img(crop)] for the n items, zeros for rows n..batch-1; one launch, one workgroup per image, bit-identical to
+ * crnn_mi355x.data.open_img + norm (float64 bilinear taps, no fused multiply-add).  arena (device, uint8): every page of the batch; table (device, 256 fp32):
+ * grey value -> network input, e.g. (v - mean) / std; out_u8 (device, [batch][imgh][imgw] uint8, or NULL): the pixels before the table.
+ * items is the table in HOST memory -- the one host-read argument of this header: it is validated before anything is launched -- and items_dev the copy of
+ * the same n entries in device memory that the kernel reads (the caller uploads it along with the arena; the kernel clamps every read into the page and the
+ * arena on its own).  CRNN_ERR_ARG (-2), with nothing launched: n < 0 or n > batch, a null pointer, a page outside the arena, an empty box or one outside
+ * its page, an inconsistent upscale flag / content placement / scale.  CRNN_ERR_UNSUPPORTED (-3): int(imgh/2*1.5) * int(imgw/2*1.5) > 48 KB of LDS. */
+int crnn_ingest_crops(const void* arena, long arena_bytes, const crnn_crop_item* items, const crnn_crop_item* items_dev, int n, int batch, int imgh, int imgw,
+                      const float* table, float* out, void* out_u8, crnn_stream_t stream);
+
 /* ---- individual operators (unit-tested one by one; the drivers above chain them) --------------------------- */
 /* mode 0: C=A[M,K]*B[K,N]; 1: C=A[M,K]*Bt[N,K]^T; 2: C=At[K,M]^T*B[K,N].  bias[N]|NULL, act 0|1(relu),
  * accumulate: C+=, permP: out_row=(m%P)*(M/P)+m/P (0=off), scratch: split-reduction partials (may be NULL) */
