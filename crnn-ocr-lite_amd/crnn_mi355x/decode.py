@@ -23,16 +23,19 @@ class DecodeCTCPred:
     def labels_to_text(self, labels):
         return labels_to_text(labels, self.inverse_classes)
 
-    def decode_labels(self, result):
-        """(N,T,C) softmax -> (N,T) int labels padded with -1 (device kernels; one launch per chunk)."""
+    def decode_labels(self, result, device=False):
+        """(N,T,C) softmax -> (N,T) int labels padded with -1 (device kernels; one launch per chunk).  A device tensor is decoded where it
+        is; an ndarray is uploaded chunk by chunk.  device=True: -> (labels (N,T), lengths (N,)) int32 DEVICE tensors, nothing copied back
+        (what metrics.device_edit_distances reads)."""
         import torch
         from . import engine, native
         if self.beam_width < self.top_paths:
             self.beam_width = self.top_paths
         y = result if torch.is_tensor(result) else torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32))
-        out = []
+        out, lens = [], []
         for lo in range(0, y.shape[0], 4096):
-            chunk = y[lo:lo + 4096].cuda().contiguous()
+            chunk = y[lo:lo + 4096]
+            chunk = (chunk if chunk.is_cuda else chunk.cuda()).contiguous()
             if self.greedy:
                 B, T, C = chunk.shape
                 lab = torch.empty((B, T), dtype=torch.int32, device=chunk.device)
@@ -41,7 +44,12 @@ class DecodeCTCPred:
                                                                  engine._stream()), "greedy")
             else:
                 lab, ln, _ = engine.beam_decode(chunk, self.beam_width, self.merge_repeated)
-            out.append(lab.cpu().numpy())
+            out.append(lab if device else lab.cpu().numpy())
+            lens.append(ln)
+        if device:
+            if not out:
+                return torch.zeros((0, 0), dtype=torch.int32, device="cuda"), torch.zeros(0, dtype=torch.int32, device="cuda")
+            return (out[0], lens[0]) if len(out) == 1 else (torch.cat(out, 0), torch.cat(lens, 0))
         return np.concatenate(out, 0) if out else np.zeros((0, 0), np.int32)
 
     def decode(self, result):

@@ -568,6 +568,48 @@ class Model:
             outs.append(self.predict_on_batch(x))
         return np.concatenate(outs, 0)
 
+    def score_generator(self, generator, steps, decoder, length=None):
+        """Validation without the host in the middle: per batch the forward (learning_phase=0), `decoder`'s beam or greedy kernel on the
+        device output and the edit distance of the decoded rows against the batch's `the_labels` (csrc/score.hip; blank and -1 skipped on
+        both sides) -> metrics.Score.  Only the label rows and three integers per pair come back, in one copy per batch; no softmax map leaves
+        the device.  Batch k+1 is drawn from the generator while batch k runs, as fit_generator does.  `length`: number of real pairs -- the
+        stale rows of the generator's short tail batch are dropped, as predict.py does with `[:length]`.  Works over Readf and DeviceReadf.
+        Raises ValueError unless every class decodes to one distinct character (metrics.check_label_metric): only then is the distance over
+        labels the distance over texts that edit_distance / normalized_edit_distance report."""
+        import torch
+        from .metrics import Score, check_label_metric, device_edit_distances
+        check_label_metric(decoder.inverse_classes)
+        blank = len(decoder.inverse_classes)
+        rows, cols = [], None
+        batch = next(generator) if steps > 0 else None
+        for k in range(steps):
+            x, lab, _, _ = self._unpack(batch)
+            if lab is None:
+                raise ValueError("score_generator needs the generator's 'the_labels'")
+            eng = self._engine(len(x))
+            # Readf re-yields the arrays it keeps filling: the truth is copied (and converted to int32) before the generator is advanced
+            truth = lab.to(eng.device, dtype=torch.int32) if torch.is_tensor(lab) else torch.from_numpy(np.array(lab, dtype=np.int32)).to(eng.device)
+            truth = truth.reshape(len(x), -1)
+            y = eng.forward(x, train=False)
+            labels, _ = decoder.decode_labels(y, device=True)
+            dist, plen, tlen = device_edit_distances(labels, truth, (blank, -1))
+            status = eng._rnn_giveups if eng._rnn_giveups is not None else torch.zeros(1, dtype=torch.int32, device=eng.device)
+            packed = torch.cat([labels.reshape(-1), dist, plen, tlen, status.reshape(-1)])
+            cols = labels.shape[1]
+            if k + 1 < steps:
+                batch = next(generator)               # host decoding / device ingest of batch k+1 while batch k runs
+            packed = packed.cpu().numpy()             # the one host synchronisation of the batch
+            eng.raise_if_rnn_gave_up(packed[-1])
+            n = len(x)
+            rows.append((packed[:n * cols].reshape(n, cols), packed[n * cols:n * cols + n], packed[n * cols + n:n * cols + 2 * n],
+                         packed[n * cols + 2 * n:n * cols + 3 * n]))
+        if not rows:
+            return Score(np.zeros((0, 0), np.int32), [], [], [])
+        parts = [np.concatenate(p, 0) for p in zip(*rows)]
+        if length is not None:
+            parts = [p[:length] for p in parts]
+        return Score(*parts)
+
 
 def init_predictor(model):
     """utils.py:308-312: the softmax sub-model sharing the trained weights."""

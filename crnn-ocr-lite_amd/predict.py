@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Prediction CLI with the reference's flag surface (predict.py:62-79): forward on the GPU, whole-batch
 HIP beam-search decode (beam_width=10, top_paths=1, merge_repeated as TF 1.8), optional edit-distance report
-and prediction.csv."""
+and prediction.csv.  --device_score (with --validate) keeps decoding and scoring on the GPU: same report, same prediction.csv."""
 import argparse
 import os
 import pickle
@@ -33,11 +33,21 @@ def build_parser():
                         help='image decoding processes feeding the generator (0 = the reference\'s single-threaded loader)')
     parser.add_argument('--device_ingest', action='store_true',
                         help='build the batches on the GPU: pages go up as uint8 with a box table, one kernel crops, pads and normalises')
+    parser.add_argument('--device_score', action='store_true',
+                        help='with --validate: decode and score on the GPU (one edit-distance kernel per batch); no softmax map is copied to the host')
     return parser
 
 
+def parse_args(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.device_score and not args.validate:
+        parser.error("--device_score scores against the truth: it needs --validate")
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.G >= 0:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", str(args.G))   # the reference falls back to CPU for G<0; this build has no CPU path
     import utils as U
@@ -80,11 +90,19 @@ def main(argv=None):
     steps = -(-length // args.batch_size)
     print(" [INFO] Predicting... ")
     start = time.time()
-    predicted = model.predict_generator(reader.run_generator(fnames, bboxs=bboxs, downsample_factor=2), steps=steps)
-    print(" [INFO] %d images processed in %s sec. " % (len(fnames), round(time.time() - start, 2)))
-    start = time.time()
-    predicted_text = decoder.decode(predicted)[:length]
-    print(" [INFO] %d predictions decoded in %s sec. " % (len(predicted), round(time.time() - start, 2)))
+    score = None
+    if args.device_score:                                    # forward, beam search and edit distance per batch, all on the device
+        score = model.score_generator(reader.run_generator(fnames, bboxs=bboxs, downsample_factor=2), steps=steps, decoder=decoder, length=length)
+        print(" [INFO] %d images processed in %s sec. " % (len(fnames), round(time.time() - start, 2)))
+        start = time.time()
+        predicted_text = score.texts(decoder)
+        print(" [INFO] %d predictions decoded in %s sec. " % (steps * args.batch_size, round(time.time() - start, 2)))
+    else:
+        predicted = model.predict_generator(reader.run_generator(fnames, bboxs=bboxs, downsample_factor=2), steps=steps)
+        print(" [INFO] %d images processed in %s sec. " % (len(fnames), round(time.time() - start, 2)))
+        start = time.time()
+        predicted_text = decoder.decode(predicted)[:length]
+        print(" [INFO] %d predictions decoded in %s sec. " % (len(predicted), round(time.time() - start, 2)))
     if args.result_path is not None:
         import pandas as pd
         if len(fnames) != len(predicted_text):
@@ -98,8 +116,11 @@ def main(argv=None):
         start = time.time()
         true_text = [decoder.labels_to_text(y_true[i]) for i in range(len(y_true))]
         print(" [INFO] Example pairs (predicted, true): \n", list(zip(predicted_text[:10], true_text[:10])))
-        ed = U.edit_distance(predicted_text, true_text)
-        ned = U.normalized_edit_distance(predicted_text, true_text)
+        if score is not None:
+            ed, ned = score.edit_distance, score.normalized_edit_distance
+        else:
+            ed = U.edit_distance(predicted_text, true_text)
+            ned = U.normalized_edit_distance(predicted_text, true_text)
         print(" [INFO] edit distances calculated in %s sec. " % round(time.time() - start, 2))
         print(" [INFO] mean edit distance: %f ; normalized edit distance score: %f " % (ed, ned))
 

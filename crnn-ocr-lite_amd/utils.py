@@ -13,4 +13,5 @@ from crnn_mi355x.decode import DecodeCTCPred, labels_to_text  # noqa: F401
 from crnn_mi355x.data import (Readf, open_img, read_img, norm, parse_mjsynth, get_lengths, get_lexicon, make_ohe)  # noqa: F401
 from crnn_mi355x.ingest import DeviceIngest, DeviceReadf, plan_crop  # noqa: F401  (beyond the reference: batches built on the device)
 from crnn_mi355x.metrics import levenshtein, edit_distance, normalized_edit_distance  # noqa: F401
+from crnn_mi355x.metrics import Score, device_edit_distances, check_label_metric  # noqa: F401  (beyond the reference: scored on the device)
 from crnn_mi355x.callbacks import Callback, EarlyStoppingIter, ModelCheckpoint  # noqa: F401

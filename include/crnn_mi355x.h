@@ -196,6 +196,16 @@ int crnn_ctc_greedy_decode(const float* y, const int* input_len, int* out, int* 
  * best beam (sum of max-shifted log-probs, as TF r1.8 accumulates it).  State lives in LDS: no workspace. */
 int crnn_ctc_beam_decode(const float* y, const int* input_len, int* out, int* out_len, float* scores, int B, int T,
                          int C, int beam_width, int merge_repeated, crnn_stream_t stream);
+/* Edit distance of decoded rows against the truth (utils.py:262-298 after labels_to_text, utils.py:314-321), one launch for the batch.
+ * For each row i < n: a = pred[i, :] ([n, pred_cols] int32) and b = truth[i, :] ([n, truth_cols] int32), each with every element equal to
+ * skip0 or skip1 removed WHEREVER it stands (labels_to_text drops blank and -1 anywhere, not only at the end); dist[i] = Levenshtein(a, b)
+ * with unit costs, pred_len[i] = |a|, truth_len[i] = |b|.  Rows past n of the three outputs are not written.  Labels are compared as plain
+ * int32 and nothing is indexed by a label value, so any int32 is a valid label: there is no range check.  One wavefront per pair (Myers'
+ * bit vectors, the 64-bit ballot as the word); no workspace, no LDS.  Supported: truth_cols <= 64 and pred_cols <= 1024, else -3; -2 for a
+ * null pointer, n < 0 or a column count < 1; n == 0 launches nothing.  The distance is symmetric: a caller whose truth is the wider side
+ * may pass the operands swapped. */
+int crnn_edit_distance(const int* pred, int pred_cols, const int* truth, int truth_cols, int skip0, int skip1,
+                       int* dist, int* pred_len, int* truth_len, int n, crnn_stream_t stream);
 
 /* ---- input side: word crops of page images -> the batch crnn_forward reads (reference utils.py:364-416, open_img + norm) ---- */
 /* One crop.  The page is a row-major uint8 image at byte `page_off` of the arena; the crop is page[r0:r1, c0:c1] (hc x wc), rotated so that the
