@@ -212,6 +212,26 @@ def test_dense1_stream_kernels_shape_rules():
     assert L.crnn_gemm_wres_supported(4608, 128) == 0 and L.crnn_gemm_wres_supported(4608, 256) == -3 and L.crnn_gemm_wres_supported(8320, 128) == -3
 
 
+def test_workspace_plan_and_block_output_fusion_equal_the_recorded_plan():
+    """Host arithmetic only: the workspace size, every schedule-dependent and per-block tensor's (offset, count, dtype | absent) and the seven
+    crnn_block_output_fused answers of the built library equal tests/golden/workspace_plan.json over shapes x LSTM / GRU x stn x precision
+    mode x flags (none, every single CRNN_FLAG_* bit, the combinations the tests and bench.py use).  The step driver may change how it reaches
+    these decisions, not the decisions: no workspace byte moves."""
+    import importlib.util
+    gold_dir = os.path.join(os.path.dirname(__file__), "golden")
+    spec = importlib.util.spec_from_file_location("make_workspace_plan", os.path.join(gold_dir, "make_workspace_plan.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    gold = json.load(open(os.path.join(gold_dir, "workspace_plan.json")))
+    assert gold["shapes"] == [list(s) for s in gen.SHAPES] and gold["flags"] == gen.flag_values(native) and gold["names"] == gen.NAMES
+    keys = [k for k, _ in gen.configs(native)]
+    got = gen.records(native)
+    assert len(got) == len(gold["records"]) == len(keys) == 7 * 2 * 2 * 3 * len(gold["flags"])
+    bad = [(k, g, w) for k, g, w in zip(keys, got, gold["records"]) if g != w]
+    assert not bad, "%d configurations differ, first: %s" % (len(bad), bad[:3])
+    assert all(r[0] > 0 for r in got) and any(r[1] for r in got) and any(not r[1] for r in got)
+
+
 def test_row_stream_kernels_keep_their_row_loops_spill_free():
     """The bf16 row-stream kernels sit at their 168-register ceiling; a harmless-looking edit (an address spelled with one multiplication instead of two)
     once put a 16-byte spill into the depthwise-stage backward's row loop and cost the kernel 22 %.  hipcc cross-compiles gfx950 without a GPU: no
