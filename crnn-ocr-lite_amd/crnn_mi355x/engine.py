@@ -63,7 +63,7 @@ class Engine:
         self._c = ctypes.byref(self.cfg)
         nbytes = self.lib.crnn_workspace_bytes(self._c)
         if nbytes == 0:
-            raise native.CrnnError("unsupported CRNN configuration (n_units % 64 == 0, classes <= 64, max_len <= 31 required)")
+            raise native.CrnnError("unsupported CRNN configuration (n_units % 64 == 0, classes <= 128, max_len <= 31 required)")
         self.T = self.lib.crnn_time_steps(self._c)
         self.B, self.C = batch, num_classes
         self.n_total = self.lib.crnn_params_total(self._c)
@@ -287,8 +287,9 @@ class Engine:
 
     def _check_ctc_inputs(self, labels, input_length, label_length):
         """Host-side validation of the CTC inputs (the kernel indexes LDS with the label ids): labels (B, max_len) with
-        0 <= id < num_classes, 0 <= label_length <= max_len, input_length <= T - 2.  Device tensors are trusted (checking
-        them would force a synchronisation in the hot loop); NumPy batches from Readf are checked."""
+        0 <= id < num_classes (num_classes up to 128: ids of 64 and above are ordinary labels), 0 <= label_length <= max_len,
+        input_length <= T - 2.  Device tensors are trusted (checking them would force a synchronisation in the hot loop); NumPy batches
+        from Readf are checked."""
         if not torch.is_tensor(labels):
             lab = np.asarray(labels)
             if lab.size != self.B * self.cfg.max_len:

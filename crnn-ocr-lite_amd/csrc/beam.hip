@@ -12,6 +12,9 @@
 // and re-enters later is the same node again (its descendants regain their parent term).  The per-entry loop over
 // the 37 children only iterates over "events" (labels that can enter the beam, or that name an existing entry),
 // found with one wave ballot; every decision inside it is wave-uniform.
+// Alphabets of 65..128 classes run the CPL = 2 instantiation (classes per lane): lane l holds the posteriors and the children of labels l and l + 64, gives
+// one ballot per half, and the events of the lower half are consumed before those of the upper half -- label order, as above.  The blank (C - 1) then
+// always sits in the upper half.  The beam itself stays one entry per lane.
 #include "common.h"
 
 #define BEAM_MAX 64          // one beam entry per lane
@@ -64,6 +67,7 @@ __device__ __forceinline__ void wave_argmin(float v, int lane, int cnt, float& m
   mv = rl(mv, 0); ml = rl(ml, 0);
 }
 
+template <int CPL>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ y, const int* __restrict__ input_len,
                                                       int* __restrict__ out, int* __restrict__ out_len,
                                                       float* __restrict__ scores, int T, int C, int bw, int merge_repeated,
@@ -95,12 +99,24 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   for (int k = 0; k < kNodeRegs; ++k) nd[k] = -1;
 
   float ynext = (Tb > 0 && lane < C) ? y[(long)b * T * C + lane] : 0.f;        // the next step's posteriors are requested a step ahead
+  float ynext1 = 0.f;                                                           // (class lane + 64, CPL == 2)
+  if constexpr (CPL == 2) ynext1 = (Tb > 0 && lane + 64 < C) ? y[(long)b * T * C + lane + 64] : 0.f;
   for (int t = 0; t < Tb; ++t) {
     const float ycur = ynext;
     if (t + 1 < Tb && lane < C) ynext = y[((long)b * T + t + 1) * C + lane];
     float lg = (lane < C) ? logf(ycur + BEAM_EPS) : BNEG;
-    const float inp = lg - wave_max64(lg);               // lane = class
-    const float inp_blank = rl(inp, blank);
+    float inp, inp1 = BNEG, inp_blank;                   // lane = class (inp1: class lane + 64)
+    if constexpr (CPL == 1) {
+      inp = lg - wave_max64(lg);
+      inp_blank = rl(inp, blank);
+    } else {
+      const float ycur1 = ynext1;
+      if (t + 1 < Tb && lane + 64 < C) ynext1 = y[((long)b * T + t + 1) * C + lane + 64];
+      const float lg1 = (lane + 64 < C) ? logf(ycur1 + BEAM_EPS) : BNEG;
+      const float mx = wave_max64(fmaxf(lg, lg1));
+      inp = lg - mx; inp1 = lg1 - mx;
+      inp_blank = rl(inp1, blank - 64);
+    }
     // ---- oldp <- newp; re-score the entries (parent term only while the parent is in the beam)
     b_ob = b_nb; b_ol = b_nl; b_ot = b_nt;
     {
@@ -111,6 +127,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         if (lane < n && b_node != 0 && nj == b_par) { found = true; prev = (b_lab == lj) ? obj : otj; }
       }
       float in_lab = __shfl(inp, b_lab & 63, 64);
+      if constexpr (CPL == 2) {
+        const float in_lab1 = __shfl(inp1, b_lab & 63, 64);
+        if (b_lab >> 6) in_lab = in_lab1;                  // (the root's label -1 never reads in_lab)
+      }
       if (lane < n) {
         float nl = BNEG;
         if (b_node != 0) {
@@ -132,32 +152,46 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       if (!(bot > BNEG && (nle < bw || bot > bval))) continue;
       const float prev = (lane == blab) ? bob : bot;
       const float v = (lane < blank && prev > BNEG) ? inp + prev : BNEG;     // lane = child label
-      int cb = -1;
+      float v1 = BNEG;                                                          // child label lane + 64 (CPL == 2)
+      if constexpr (CPL == 2) {
+        const float prev1 = (lane + 64 == blab) ? bob : bot;
+        v1 = (lane + 64 < blank && prev1 > BNEG) ? inp1 + prev1 : BNEG;
+      }
+      int cb = -1, cb1 = -1;
       for (int j = 0; j < n; ++j) {
         int pj = rl(b_par, j), lj = rl(b_lab, j);
         if (pj == bnode && lj == lane) cb = j;                                  // this child is beam entry j
+        if constexpr (CPL == 2) if (pj == bnode && lj == lane + 64) cb1 = j;
       }
       const bool ev = (lane < blank) && (cb >= 0 || (v > BNEG && (nle < bw || v > bval)));
-      unsigned long long mask = __ballot(ev);
-      while (mask) {
-        const int c = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        const float vc = rl(v, c);
-        const int ccb = rl(cb, c);
-        if (ccb >= 0 && rl(b_act, ccb)) continue;                       // child already in the beam
-        if (vc > BNEG && (nle < bw || vc > bval)) {
-          int slot;
-          if (nle == bw) {                                                      // evict the bottom
-            slot = bslot;
-            int k = rl(l_ref, bslot);
-            if (k >= 0 && lane == k) b_act = 0;
-          } else {
-            slot = nle++;
+      unsigned long long hmask[CPL];
+      hmask[0] = __ballot(ev);
+      if constexpr (CPL == 2) hmask[1] = __ballot((lane + 64 < blank) && (cb1 >= 0 || (v1 > BNEG && (nle < bw || v1 > bval))));
+#pragma unroll
+      for (int h = 0; h < CPL; ++h) {                                           // label order: the lower half's events, then the upper half's
+        unsigned long long mask = hmask[h];
+        const float vh = h ? v1 : v;
+        const int cbh = h ? cb1 : cb;
+        while (mask) {
+          const int c = __ffsll((long long)mask) - 1;
+          mask &= mask - 1;
+          const float vc = rl(vh, c);
+          const int ccb = rl(cbh, c);
+          if (ccb >= 0 && rl(b_act, ccb)) continue;                       // child already in the beam
+          if (vc > BNEG && (nle < bw || vc > bval)) {
+            int slot;
+            if (nle == bw) {                                                      // evict the bottom
+              slot = bslot;
+              int k = rl(l_ref, bslot);
+              if (k >= 0 && lane == k) b_act = 0;
+            } else {
+              slot = nle++;
+            }
+            if (lane == slot) { l_v = vc; l_ref = -1; l_par = bi; l_lab = c + 64 * h; }
+            wave_argmin(l_v, lane, nle, bval, bslot);
+          } else if (ccb >= 0 && lane == ccb) {                                   // re-offered, rejected: reset oldp
+            b_ob = b_ol = b_ot = BNEG;
           }
-          if (lane == slot) { l_v = vc; l_ref = -1; l_par = bi; l_lab = c; }
-          wave_argmin(l_v, lane, nle, bval, bslot);
-        } else if (ccb >= 0 && lane == ccb) {                                   // re-offered, rejected: reset oldp
-          b_ob = b_ol = b_ot = BNEG;
         }
       }
     }
@@ -244,11 +278,12 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
 
 extern "C" int crnn_ctc_beam_decode(const float* y, const int* input_len, int* out, int* out_len, float* scores, int B, int T,
                                     int C, int beam_width, int merge_repeated, hipStream_t stream) {
-  if (C > 64 || C < 2 || beam_width < 1 || beam_width > BEAM_MAX) return CRNN_ERR_UNSUPPORTED;
+  if (C > 128 || C < 2 || beam_width < 1 || beam_width > BEAM_MAX) return CRNN_ERR_UNSUPPORTED;
   int nmax = 1 + T * beam_width;
   size_t lds = (size_t)nmax * 4 + BEAM_MAX * 16 + 64;
   if (lds > 64 * 1024) return CRNN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(64), lds, stream, y, input_len, out, out_len, scores, T, C, beam_width, merge_repeated, nmax);
+  auto kernel = C <= 64 ? ctc_beam_kernel<1> : ctc_beam_kernel<2>;   // one class per lane, or two (lane l: classes l and l + 64)
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(64), lds, stream, y, input_len, out, out_len, scores, T, C, beam_width, merge_repeated, nmax);
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;
 }

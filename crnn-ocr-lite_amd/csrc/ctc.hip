@@ -25,20 +25,34 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
   return mm + logf(expf(a - mm) + expf(b - mm) + expf(c - mm));
 }
 
-// ---- row softmax over C (<= 64) classes: one wave per row -------------------------------------------
+// ---- row softmax over C (<= 128) classes: one wave per row ------------------------------------------
+// CPL = classes per lane: 1 for C <= 64 (lane l = class l), 2 for 65..128 (lane l = classes l and l + 64: the second value rides through the same
+// wave_max / wave_sum).  The entry points pick the instantiation from C, so the narrow alphabets run the one-class-per-lane code unchanged.
+template <int CPL>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ z, float* __restrict__ p, long rows, int C) {
   long row = blockIdx.x * 4L + (threadIdx.x >> 6);
   int lane = threadIdx.x & 63;
   if (row >= rows) return;
   float v = lane < C ? z[row * C + lane] : NEG_INF;
-  float m = wave_max(v);
-  float e = lane < C ? expf(v - m) : 0.f;
-  float s = wave_sum(e);
-  if (lane < C) p[row * C + lane] = e / s;
+  if constexpr (CPL == 1) {
+    float m = wave_max(v);
+    float e = lane < C ? expf(v - m) : 0.f;
+    float s = wave_sum(e);
+    if (lane < C) p[row * C + lane] = e / s;
+  } else {
+    const bool up = lane + 64 < C;
+    float v1 = up ? z[row * C + lane + 64] : NEG_INF;
+    float m = wave_max(fmaxf(v, v1));
+    float e = lane < C ? expf(v - m) : 0.f, e1 = up ? expf(v1 - m) : 0.f;
+    float s = wave_sum(e + e1);
+    if (lane < C) p[row * C + lane] = e / s;
+    if (up) p[row * C + lane + 64] = e1 / s;
+  }
 }
 extern "C" int crnn_softmax_rows(const float* z, float* p, long rows, int C, hipStream_t stream) {
-  if (C > 64) return CRNN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(softmax_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, z, p, rows, C);
+  if (C > 128) return CRNN_ERR_UNSUPPORTED;
+  if (C <= 64) hipLaunchKernelGGL(softmax_rows_kernel<1>, dim3(cdiv(rows, 4)), dim3(256), 0, stream, z, p, rows, C);
+  else hipLaunchKernelGGL(softmax_rows_kernel<2>, dim3(cdiv(rows, 4)), dim3(256), 0, stream, z, p, rows, C);
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;
 }
@@ -46,6 +60,7 @@ extern "C" int crnn_softmax_rows(const float* z, float* p, long rows, int C, hip
 // dense2's epilogue in one pass (round 5): z [rows][ldz] are the raw products of the streaming GEMM over a padded weight matrix (columns >= C are never read);
 // logits = z + bias go out in permuted row order (out row = (m % P) * (rows / P) + m / P: time-major rows back to batch-major, as the tile GEMM's epilogue
 // does) together with their softmax p1 (workspace) and p2 (the caller's y_pred, may be NULL) -- the softmax and copy launches of the unfused path.
+template <int CPL>
 __global__ __launch_bounds__(256) void softmax_rows_perm_kernel(const float* __restrict__ z, int ldz, const float* __restrict__ bias, float* __restrict__ logits,
                                                                 float* __restrict__ p1, float* __restrict__ p2, long rows, int C, int P) {
   const long m = blockIdx.x * 4L + (threadIdx.x >> 6);
@@ -53,21 +68,42 @@ __global__ __launch_bounds__(256) void softmax_rows_perm_kernel(const float* __r
   if (m >= rows) return;
   const long orow = P ? (m % P) * (rows / P) + m / P : m;
   const float v = lane < C ? z[m * ldz + lane] + (bias ? bias[lane] : 0.f) : NEG_INF;
-  const float mx = wave_max(v);
-  const float e = lane < C ? expf(v - mx) : 0.f;
-  const float sum = wave_sum(e);
-  if (lane < C) {
-    logits[orow * C + lane] = v;
-    const float pr = e / sum;
-    p1[orow * C + lane] = pr;
-    if (p2) p2[orow * C + lane] = pr;
+  if constexpr (CPL == 1) {
+    const float mx = wave_max(v);
+    const float e = lane < C ? expf(v - mx) : 0.f;
+    const float sum = wave_sum(e);
+    if (lane < C) {
+      logits[orow * C + lane] = v;
+      const float pr = e / sum;
+      p1[orow * C + lane] = pr;
+      if (p2) p2[orow * C + lane] = pr;
+    }
+  } else {
+    const bool up = lane + 64 < C;
+    const float v1 = up ? z[m * ldz + lane + 64] + (bias ? bias[lane + 64] : 0.f) : NEG_INF;
+    const float mx = wave_max(fmaxf(v, v1));
+    const float e = lane < C ? expf(v - mx) : 0.f, e1 = up ? expf(v1 - mx) : 0.f;
+    const float sum = wave_sum(e + e1);
+    if (lane < C) {
+      logits[orow * C + lane] = v;
+      const float pr = e / sum;
+      p1[orow * C + lane] = pr;
+      if (p2) p2[orow * C + lane] = pr;
+    }
+    if (up) {
+      logits[orow * C + lane + 64] = v1;
+      const float pr = e1 / sum;
+      p1[orow * C + lane + 64] = pr;
+      if (p2) p2[orow * C + lane + 64] = pr;
+    }
   }
 }
 extern "C" int crnn_softmax_rows_perm(const float* z, int ldz, const float* bias, float* logits, float* p1, float* p2, long rows, int C, int permP,
                                       hipStream_t stream) {
   if (!z || !logits || !p1 || rows <= 0 || C < 1 || ldz < C || permP < 0 || (permP && rows % permP)) return CRNN_ERR_ARG;
-  if (C > 64) return CRNN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(softmax_rows_perm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, z, ldz, bias, logits, p1, p2, rows, C, permP);
+  if (C > 128) return CRNN_ERR_UNSUPPORTED;
+  if (C <= 64) hipLaunchKernelGGL(softmax_rows_perm_kernel<1>, dim3(cdiv(rows, 4)), dim3(256), 0, stream, z, ldz, bias, logits, p1, p2, rows, C, permP);
+  else hipLaunchKernelGGL(softmax_rows_perm_kernel<2>, dim3(cdiv(rows, 4)), dim3(256), 0, stream, z, ldz, bias, logits, p1, p2, rows, C, permP);
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;
 }
@@ -84,9 +120,12 @@ extern "C" int crnn_softmax_rows_perm(const float* z, int ldz, const float* bias
 // Round 5 (scripts/ctc_bench.py, phase-ablation builds): 61 -> 28 us per launch at batch 256 -- the gradient phase was 30 us of it (the blank lane walking
 // its 24-state mask through LDS with the wave waiting, two workgroup barriers per time step), the log-softmax phase ran on 50 lanes of 256.
 // LDS: lsm [Tb][C], alpha [Tb][64], beta [Tb][64], ys [Tb][C], ab [4][64].
+// CPL = classes per lane: with 65..128 classes (CPL = 2) the class lane l of phases 1 and 3 owns classes l and l + 64 -- two log-softmax values, two
+// occupancy masks, two gradient elements, one wave reduction over both --; the state lanes and the recursions do not depend on the class count.
 #ifndef CTC_WAVES
 #define CTC_WAVES 16     // round 5: 4 -> 16 (phases 1 and 3 deal the time steps over the waves: 41 -> 28 us at batch 256; 8 waves: 31.5)
 #endif
+template <int CPL>
 __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const float* __restrict__ y, const int* __restrict__ labels,
                                                                        const int* __restrict__ input_len, const int* __restrict__ label_len,
                                                                        float* __restrict__ loss, float* __restrict__ dlogits, int B, int T,
@@ -110,10 +149,14 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
   for (int t = wave; t < T; t += CTC_WAVES) {
     bool inside = (t >= skip && t < skip + Tb);
     if (!inside && lane < C) dlogits[((long)t * B + b) * C + lane] = 0.f;
+    if constexpr (CPL == 2) if (!inside && lane + 64 < C) dlogits[((long)t * B + b) * C + lane + 64] = 0.f;
   }
   if (Tb == 0 || S > 64) {             // degenerate sample (uniform across the workgroup)
     if (tid == 0) loss[b] = (Tb == 0 && L == 0) ? 0.f : INFINITY;
-    for (int t = skip + wave; t < skip + Tb; t += CTC_WAVES) if (lane < C) dlogits[((long)t * B + b) * C + lane] = 0.f;
+    for (int t = skip + wave; t < skip + Tb; t += CTC_WAVES) {
+      if (lane < C) dlogits[((long)t * B + b) * C + lane] = 0.f;
+      if constexpr (CPL == 2) if (lane + 64 < C) dlogits[((long)t * B + b) * C + lane + 64] = 0.f;
+    }
     return;
   }
   __syncthreads();
@@ -124,10 +167,20 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
   // evaluating 3 C logarithms and C exponentials in sequence: a fifth of the kernel)
   for (int t = wave; t < Tb; t += CTC_WAVES) {
     const float z = lane < C ? logf(ys[t * C + lane] + CTC_EPS) : NEG_INF;
-    const float m = wave_max(z);
-    const float e = lane < C ? expf(z - m) : 0.f;
-    const float lz = m + logf(wave_sum(e));
-    if (lane < C) lsm[t * C + lane] = z - lz;
+    if constexpr (CPL == 1) {
+      const float m = wave_max(z);
+      const float e = lane < C ? expf(z - m) : 0.f;
+      const float lz = m + logf(wave_sum(e));
+      if (lane < C) lsm[t * C + lane] = z - lz;
+    } else {
+      const bool up = lane + 64 < C;
+      const float z1 = up ? logf(ys[t * C + lane + 64] + CTC_EPS) : NEG_INF;
+      const float m = wave_max(fmaxf(z, z1));
+      const float e = (lane < C ? expf(z - m) : 0.f) + (up ? expf(z1 - m) : 0.f);
+      const float lz = m + logf(wave_sum(e));
+      if (lane < C) lsm[t * C + lane] = z - lz;
+      if (up) lsm[t * C + lane + 64] = z1 - lz;
+    }
   }
   __syncthreads();
 #if CRNN_CTC_EXP == 1
@@ -179,16 +232,20 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
   const float ll = ll_sh;
   if (tid == 0) loss[b] = -ll;
   if (ll == NEG_INF) {  // no valid path: TF reports inf loss, zero gradient
-    for (int t = skip + wave; t < skip + Tb; t += CTC_WAVES) if (lane < C) dlogits[((long)t * B + b) * C + lane] = 0.f;
+    for (int t = skip + wave; t < skip + Tb; t += CTC_WAVES) {
+      if (lane < C) dlogits[((long)t * B + b) * C + lane] = 0.f;
+      if constexpr (CPL == 2) if (lane + 64 < C) dlogits[((long)t * B + b) * C + lane + 64] = 0.f;
+    }
     return;
   }
   // which extended-label states carry class `lane` (bit s set <=> ext_s == lane).  The BLANK class sits on every even state (L + 1 of them): its lane takes
   // the sum from a wave reduction of the state lanes' own registers instead of walking its mask (round 5: 24 dependent LDS reads per time step on one lane
   // -- with the whole wave waiting for it -- were 30 of the kernel's 55 us; phase timings in scripts/ctc_bench.py)
-  unsigned long long occ_mask = 0ull;
+  unsigned long long occ_mask = 0ull, occ_mask1 = 0ull;   // (occ_mask1: class lane + 64, CPL == 2 only)
   for (int s2 = 0; s2 < S; ++s2) {
     int e2 = __shfl(ext, s2, 64);
     if (e2 == lane && lane != blank) occ_mask |= 1ull << s2;
+    if constexpr (CPL == 2) if (e2 == lane + 64 && lane + 64 != blank) occ_mask1 |= 1ull << s2;
   }
   // phase 3: gradient, time steps round-robin over the waves.  A wave works on its own ab row only: the hand-over from the state lanes to the class lanes is
   // inside the wave (LDS operations of one wave complete in order), no workgroup barrier.
@@ -209,8 +266,24 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
       pk = ys[t * C + lane];
       gyk = gz / (pk + CTC_EPS);          // d loss / d y_pred[t][k]
     }
-    const float dot = wave_sum(gyk * pk);
-    if (lane < C) dlogits[((long)(t + skip) * B + b) * C + lane] = grad_scale * pk * (gyk - dot);
+    if constexpr (CPL == 1) {
+      const float dot = wave_sum(gyk * pk);
+      if (lane < C) dlogits[((long)(t + skip) * B + b) * C + lane] = grad_scale * pk * (gyk - dot);
+    } else {
+      const int k1 = lane + 64;
+      float gyk1 = 0.f, pk1 = 0.f;
+      if (k1 < C) {
+        const float l = lsm[t * C + k1];
+        float occ = (k1 == blank) ? wblank : 0.f;
+        for (unsigned long long m = occ_mask1; m; m &= m - 1) occ += abw[__ffsll((long long)m) - 1];
+        const float gz = expf(l) - occ;
+        pk1 = ys[t * C + k1];
+        gyk1 = gz / (pk1 + CTC_EPS);
+      }
+      const float dot = wave_sum(gyk * pk + gyk1 * pk1);
+      if (lane < C) dlogits[((long)(t + skip) * B + b) * C + lane] = grad_scale * pk * (gyk - dot);
+      if (k1 < C) dlogits[((long)(t + skip) * B + b) * C + k1] = grad_scale * pk1 * (gyk1 - dot);
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();       // (the class lanes are done with this row before the state lanes overwrite it)
   }
@@ -218,16 +291,17 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
 
 extern "C" int crnn_ctc_loss_grad(const float* y, const int* labels, const int* input_len, const int* label_len, float* loss,
                                   float* dlogits, int B, int T, int C, int Lmax, int skip, float grad_scale, hipStream_t stream) {
-  if (C > 64 || C < 2 || T <= skip) return CRNN_ERR_UNSUPPORTED;
+  if (C > 128 || C < 2 || T <= skip) return CRNN_ERR_UNSUPPORTED;
   if (Lmax < 0 || 2 * Lmax + 1 > 64) return CRNN_ERR_UNSUPPORTED;   // the extended label (2L+1 states) lives on the 64 lanes of one wavefront
   if (B <= 0) return CRNN_ERR_ARG;
   size_t lds = (2 * (size_t)(T - skip) * C + 2 * (size_t)(T - skip) * 64 + 64 * CTC_WAVES + 4) * sizeof(float);
   if (lds > 160 * 1024) return CRNN_ERR_UNSUPPORTED;
+  auto kernel = C <= 64 ? ctc_loss_grad_kernel<1> : ctc_loss_grad_kernel<2>;   // one class per lane, or two (lane l: classes l and l + 64)
   if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)ctc_loss_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(ctc_loss_grad_kernel, dim3(B), dim3(64 * CTC_WAVES), lds, stream, y, labels, input_len, label_len, loss, dlogits, B, T, C, Lmax, skip, grad_scale);
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * CTC_WAVES), lds, stream, y, labels, input_len, label_len, loss, dlogits, B, T, C, Lmax, skip, grad_scale);
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;
 }

@@ -166,7 +166,7 @@ Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
   S.bwd_stream_planes = S.products == 2 && S.planes_bwd == 2 && !tile_gemms;
   S.loc_fused = c->stn && !(fl & CRNN_FLAG_LOC_NET_KERNELS) && crnn_loc_net_fused_supported(d.H0, d.W0) == CRNN_OK && al_wp;
   // dense layers: the stripe streams / weights-resident kernels in the bf16 modes (whole 64-row stripes); dense2's one-pass fp32 backward in every mode
-  S.dense2_stream = mode && !tile_gemms && TB % 64 == 0 && (2 * u) % 64 == 0 && d.C <= 64;
+  S.dense2_stream = mode && !tile_gemms && TB % 64 == 0 && (2 * u) % 64 == 0 && d.C <= 128;
   S.dense1_stream = mode == 2 && !tile_gemms && d.feat % 8 == 0 && crnn_dense_fwd_stream_supported(TB, d.tds, d.feat) == CRNN_OK;
   S.dense1_fwd_stream = S.dense1_stream && al_wp;
   S.dense1_dgrad_wres = mode == 2 && !tile_gemms && crnn_gemm_wres_supported(d.feat, d.tds) == CRNN_OK && TB * d.feat < (1L << 31);
@@ -462,7 +462,7 @@ int check_cfg(const crnn_config* c) {
   if (!c || c->batch <= 0) return CRNN_ERR_ARG;
   if (c->units < 64 || c->units % 64) return CRNN_ERR_UNSUPPORTED;
   if (c->mfma_bf16 < 0 || c->mfma_bf16 > 2) return CRNN_ERR_ARG;
-  if (c->num_classes > 64 || c->num_classes < 2) return CRNN_ERR_UNSUPPORTED;
+  if (c->num_classes > 128 || c->num_classes < 2) return CRNN_ERR_UNSUPPORTED;   // two classes per lane of a wavefront (ctc.hip, beam.hip)
   if (2 * c->max_len + 1 > 64) return CRNN_ERR_UNSUPPORTED;
   if (c->tds % 4) return CRNN_ERR_UNSUPPORTED;
   Dims d = make_dims(c);

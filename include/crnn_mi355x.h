@@ -29,7 +29,7 @@ typedef struct ihipStream_t* crnn_stream_t; /* hipStream_t (torch.cuda.current_s
 typedef struct {
   int batch;        /* images per step on this GPU */
   int imgh, imgw;   /* 100 x 32: axis-1 = text width/time axis (utils.py:60) */
-  int num_classes;  /* len(lexicon)+1 = 38; blank = num_classes-1 */
+  int num_classes;  /* len(lexicon)+1 = 38; blank = num_classes-1; 2..128 (above 64 the softmax / CTC / beam kernels hold two classes per lane) */
   int max_len;      /* max_string_len (labels row length) */
   int tds;          /* time_dense_size */
   int units;        /* n_units (multiple of 64) */
@@ -192,7 +192,7 @@ int crnn_convert_f32_to_bf16(const float* x, void* y, long n, crnn_stream_t stre
 /* y [B,T,C] softmax; out [B,T] int32 padded with -1; out_len [B]; input_len may be NULL (= T) */
 int crnn_ctc_greedy_decode(const float* y, const int* input_len, int* out, int* out_len, int B, int T, int C,
                            crnn_stream_t stream);
-/* tf.nn.ctc_beam_search_decoder(beam_width <= 64, top_paths=1, merge_repeated); scores [B] = log-score of the
+/* tf.nn.ctc_beam_search_decoder(beam_width <= 64, top_paths=1, merge_repeated), C <= 128 classes; scores [B] = log-score of the
  * best beam (sum of max-shifted log-probs, as TF r1.8 accumulates it).  State lives in LDS: no workspace. */
 int crnn_ctc_beam_decode(const float* y, const int* input_len, int* out, int* out_len, float* scores, int B, int T,
                          int C, int beam_width, int merge_repeated, crnn_stream_t stream);
@@ -773,11 +773,11 @@ int crnn_gru_bwd_ex(const void* u0, const void* u1, const float* h0, const float
                     float* dh1, float* dhp0, float* dhp1, int T, int B, int u, int dt_u, crnn_stream_t stream);
 int crnn_transpose(const float* in, float* out, int R, int C, crnn_stream_t stream);
 int crnn_transpose_ex(const float* in, void* out, int R, int C, int dt_out, crnn_stream_t stream);   /* dt_out 1: bf16 result */
-/* softmax + CTC (utils.py:86, 98-103) */
+/* softmax + CTC (utils.py:86, 98-103).  C <= 128 classes (else -3): one class per lane of a wavefront up to 64, two (lane l: classes l and l + 64) above. */
 int crnn_softmax_rows(const float* z, float* p, long rows, int C, crnn_stream_t stream);
 /* dense2's epilogue in one pass (round 5): logits = z[:, :C] + bias (z [rows][ldz]: the raw products of a GEMM over a padded weight matrix), written in permuted
  * row order out_row = (m % permP) * (rows / permP) + m / permP (permP = 0: none; time-major rows back to batch-major as crnn_gemm_f32's permP), together with their row
- * softmax in p1 and, when p2 != NULL, in p2 as well (reference utils.py:85-86).  Same arithmetic as crnn_softmax_rows.  C <= 64. */
+ * softmax in p1 and, when p2 != NULL, in p2 as well (reference utils.py:85-86).  Same arithmetic as crnn_softmax_rows.  C <= 128 (above 64: lane l holds classes l and l + 64). */
 int crnn_softmax_rows_perm(const float* z, int ldz, const float* bias, float* logits, float* p1, float* p2, long rows, int C, int permP, crnn_stream_t stream);
 /* dense2's backward in one pass (round 5; dense.hip; reference utils.py:82-86 under the CTC loss of utils.py:98-103): for x [M][K] (the layer's
  * dropped-out input, leading dimension ldx), dy [M][C] (compact) and W [K][C],
@@ -786,11 +786,14 @@ int crnn_softmax_rows_perm(const float* z, int ldz, const float* bias, float* lo
  * per-workgroup partial gradients (scratch) summed in workgroup order.  db must be dW + K * C (the two gradients are one span of the gradient
  * buffer).  drop_rate 0: no dropout; keep: the site's keep bytes (crnn_dropout_keep / crnn_dropout_keep_bytes; M * K / 8 bytes, 4-byte aligned) or NULL
  * (the kernel's loader wave evaluates the decisions itself: same results, 1.6 us per 8-row step slower).  x rows contiguous (ldx == K).
- * _supported: K % 128 == 0, 128 <= K <= 512, C <= 40; else CRNN_ERR_UNSUPPORTED (the caller runs the GEMMs). */
+ * _supported: K % 128 == 0, 128 <= K <= 512, C <= 40; else CRNN_ERR_UNSUPPORTED (the caller runs the GEMMs: every alphabet of 41..128 classes). */
 int crnn_dense_bwd_small_supported(long M, int K, int C);
 size_t crnn_dense_bwd_small_scratch_bytes(long M, int K, int C);
 int crnn_dense_bwd_small(const float* x, const float* dy, const float* W, float* dx, float* dW, float* db, float* scratch, size_t scratch_bytes,
                          long M, int K, int C, int ldx, int lddx, const void* keep, float drop_rate, uint64_t seed, uint32_t layer, crnn_stream_t stream);
+/* y [B][T][C] softmax, labels [B][Lmax] (ids in [0, C - 1), blank = C - 1), dlogits [T][B][C] time-major = grad_scale * d loss / d logits, rows outside
+ * [skip, skip + input_len) zero.  Supported (else -3): 2 <= C <= 128, 2 * Lmax + 1 <= 64, and (T - skip) * (2 C + 128) + 1028 floats of LDS within 160 KB (T = 102,
+ * skip = 2, C = 128: 157,712 bytes). */
 int crnn_ctc_loss_grad(const float* y, const int* labels, const int* input_len, const int* label_len, float* loss,
                        float* dlogits, int B, int T, int C, int Lmax, int skip, float grad_scale, crnn_stream_t stream);
 
