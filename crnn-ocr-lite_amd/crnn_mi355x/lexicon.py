@@ -1,0 +1,213 @@
+"""Lexicon-constrained decoding (beyond the reference): from a word list, the word the network gives the highest CTC probability -- the standard
+way to use and to evaluate a word recogniser -- and the exact CTC log-probability of any given transcription, the model's confidence in it.
+Scores are log p(word | softmax map) in Keras' semantics (the negative of K.ctc_batch_cost for that label), computed by csrc/lexicon.hip for
+every (image, word) pair on the device; nothing but the chosen indices and their scores comes back.
+
+Tie rule: of words with equal scores the one earlier in the table wins, and the table is the caller's list sorted by length with a stable sort:
+the shorter word, then the earlier one in the caller's list."""
+import warnings
+
+import numpy as np
+
+MAX_WORD_LEN = 31            # the library's max_len limit: 2 L + 1 <= 63 states, one per lane of a wavefront
+MAX_TOP_PATHS = 8            # crnn_ctc_lexicon_topk
+SCORE_BYTES = 256 << 20      # default budget of the scores buffer [chunk][M] fp32: the batch is scored in chunks that stay under it
+
+
+class Lexicon:
+    """A word list encoded with the model's alphabet.  `inverse_classes`: {id: character} (what DecodeCTCPred holds) or a list of characters.
+    Words with a character outside the alphabet, or longer than 31, go to `.rejected` as (caller position, word) and are never scored; the
+    constructor warns once with their count.  The empty string is a legal word.  The accepted words are sorted by length (stable) -- words that
+    share a wavefront are then alike -- and uploaded once per device:
+      .words[i]   text at table index i          .order[i]   the caller's position of table index i
+      .labels     (N, Lmax) int32 padded with -1  .lengths    (N,) int32        .index_of[p]  table index of caller position p, -1 if rejected"""
+
+    def __init__(self, words, inverse_classes):
+        items = inverse_classes.items() if hasattr(inverse_classes, "items") else enumerate(inverse_classes)
+        self.inverse_classes = inverse_classes
+        self.classes = {str(ch): int(k) for k, ch in items}
+        words = [str(w) for w in words]
+        enc, pos, self.rejected = [], [], []
+        for p, w in enumerate(words):
+            ids = self.encode(w)
+            if ids is None:
+                self.rejected.append((p, w))
+            else:
+                enc.append(ids); pos.append(p)
+        if self.rejected:
+            warnings.warn("Lexicon: %d of %d words rejected (a character outside the alphabet, or longer than %d)"
+                          % (len(self.rejected), len(words), MAX_WORD_LEN))
+        lens = np.array([len(e) for e in enc], dtype=np.int32)
+        by_len = np.argsort(lens, kind="stable")
+        self.order = np.array(pos, dtype=np.int64)[by_len]
+        self.words = [words[p] for p in self.order]
+        self.lengths = lens[by_len]
+        self.labels = np.full((len(enc), max(1, int(lens.max()) if len(enc) else 1)), -1, dtype=np.int32)
+        for i, k in enumerate(by_len):
+            self.labels[i, :lens[k]] = enc[k]
+        self.index_of = np.full(len(words), -1, dtype=np.int64)
+        self.index_of[self.order] = np.arange(len(self.order))
+        self._dev = {}
+
+    def __len__(self):
+        return len(self.words)
+
+    def encode(self, word):
+        """-> list of label ids, or None when the word cannot be scored."""
+        if len(word) > MAX_WORD_LEN:
+            return None
+        ids = [self.classes.get(ch) for ch in word]
+        return None if any(i is None for i in ids) else ids
+
+    def device(self, device):
+        """-> (labels, lengths) int32 tensors on `device`; uploaded on first use."""
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.labels).to(device), torch.from_numpy(self.lengths).to(device))
+        return self._dev[key]
+
+
+def lexicon_scores(y, labels, lengths, skip=0, cand=None, input_length=None):
+    """y (B, T, C) float32 device tensor, labels (N, Lmax) / lengths (N,) int32 device tensors, cand (B, K) int32 device tensor or None
+    -> scores (B, N) or (B, K) float32 device tensor: one pre-pass and one scoring launch (crnn_ctc_lexicon_score)."""
+    import torch
+    from . import native
+    from .engine import _ptr, _stream
+    B, T, C = y.shape
+    N, Lmax = labels.shape
+    M = cand.shape[1] if cand is not None else N
+    lib = native.lib()
+    scores = torch.full((B, M), float("-inf"), dtype=torch.float32, device=y.device)
+    if B == 0 or N == 0 or M == 0:
+        return scores
+    ws = torch.empty(max(1, lib.crnn_ctc_lexicon_workspace_bytes(B, T, C, skip) // 4), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        native.check(lib.crnn_ctc_lexicon_score(_ptr(y), _ptr(input_length), _ptr(labels), _ptr(lengths), _ptr(cand), _ptr(scores), _ptr(ws),
+                                                ws.numel() * 4, B, T, C, skip, N, Lmax, M if cand is not None else 0, _stream()), "lexicon_score")
+    return scores
+
+
+def lexicon_topk(scores, k, cand=None):
+    """scores (B, M) -> (idx (B, k) int32, val (B, k) float32) device tensors (crnn_ctc_lexicon_topk)."""
+    import torch
+    from . import native
+    from .engine import _ptr, _stream
+    B, M = scores.shape
+    idx = torch.full((B, k), -1, dtype=torch.int32, device=scores.device)
+    val = torch.full((B, k), float("-inf"), dtype=torch.float32, device=scores.device)
+    if B == 0 or M == 0:
+        return idx, val
+    with torch.cuda.device(scores.device):
+        native.check(native.lib().crnn_ctc_lexicon_topk(_ptr(scores), _ptr(cand), _ptr(idx), _ptr(val), B, M, k, _stream()), "lexicon_topk")
+    return idx, val
+
+
+class LexiconDecoder:
+    """Drop-in where a DecodeCTCPred is passed (predict.py, Model.score_generator, metrics.Score): `inverse_classes`, `labels_to_text`,
+    `decode`, `decode_labels(result, device=)`.  skip: 0 scores the frames the beam decoder reads, 2 the training loss's window.
+    score_bytes: budget of the scores buffer; the batch is scored in chunks of max(1, score_bytes // (4 * words)) images."""
+
+    def __init__(self, lexicon, top_paths=1, skip=0, score_bytes=SCORE_BYTES):
+        if not 1 <= top_paths <= MAX_TOP_PATHS:
+            raise ValueError("top_paths must be 1..%d" % MAX_TOP_PATHS)
+        self.lexicon = lexicon
+        self.top_paths = top_paths
+        self.skip = skip
+        self.score_bytes = score_bytes
+        self.inverse_classes = lexicon.inverse_classes
+
+    def labels_to_text(self, labels):
+        from .decode import labels_to_text
+        return labels_to_text(labels, self.inverse_classes)
+
+    # ---- device side ----
+    def _candidates(self, candidates, n):
+        """list of lists of caller positions, or an int array padded with -1 -> (n, K) int32 ndarray of table indices (-1 = empty / rejected),
+        every row in ascending table order with the empty slots last: neighbours in a row are then alike in length, as the table's are, and
+        the tie rule of the dense mode holds -- the lower position is the shorter word, then the earlier one in the caller's list."""
+        if isinstance(candidates, np.ndarray):
+            c = candidates.astype(np.int64)
+        else:
+            K = max([len(r) for r in candidates] + [1])
+            c = np.full((len(candidates), K), -1, dtype=np.int64)
+            for i, r in enumerate(candidates):
+                c[i, :len(r)] = r
+        if c.ndim != 2 or c.shape[0] != n:
+            raise ValueError("candidates: expected %d rows, got shape %r" % (n, c.shape))
+        inside = (c >= 0) & (c < len(self.lexicon.index_of))
+        out = np.full(c.shape, -1, dtype=np.int32)
+        out[inside] = self.lexicon.index_of[c[inside]]
+        key = np.where(out < 0, np.iinfo(np.int32).max, out)
+        return np.take_along_axis(out, np.argsort(key, axis=1, kind="stable"), 1)
+
+    def _topk(self, result, candidates, k):
+        """-> (idx (n, k) int32 table indices or -1, val (n, k) float32), device tensors."""
+        import torch
+        y = result if torch.is_tensor(result) else torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32))
+        n = y.shape[0]
+        cand = self._candidates(candidates, n) if candidates is not None else None
+        device = y.device if y.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        labels, lengths = self.lexicon.device(device)
+        M = cand.shape[1] if cand is not None else len(self.lexicon)
+        rows = max(1, min(4096, self.score_bytes // (4 * max(M, 1))))
+        idx, val = [], []
+        for lo in range(0, n, rows):
+            chunk = y[lo:lo + rows]
+            chunk = (chunk if chunk.is_cuda else chunk.to(device)).contiguous().float()
+            cd = torch.from_numpy(np.ascontiguousarray(cand[lo:lo + rows])).to(device) if cand is not None else None
+            i, v = lexicon_topk(lexicon_scores(chunk, labels, lengths, self.skip, cd), k, cd)
+            idx.append(i); val.append(v)
+        if not idx:
+            return torch.zeros((0, k), dtype=torch.int32, device=device), torch.zeros((0, k), dtype=torch.float32, device=device)
+        return (idx[0], val[0]) if len(idx) == 1 else (torch.cat(idx, 0), torch.cat(val, 0))
+
+    # ---- the decoder surface ----
+    def decode_topk(self, result, candidates=None):
+        """-> (words, log_probs): per image the top_paths best words (best first, '' where no word has a finite score) and their CTC
+        log-probabilities, an (n, top_paths) float32 ndarray (-inf in the empty slots)."""
+        idx, val = self._topk(result, candidates, self.top_paths)
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        return [[self.lexicon.words[i] if i >= 0 else "" for i in row] for row in idx], val
+
+    def decode(self, result, candidates=None):
+        """-> the best word per image; an image with no finite score decodes to ''."""
+        idx, _ = self._topk(result, candidates, 1)
+        return [self.lexicon.words[i] if i >= 0 else "" for i in idx[:, 0].cpu().numpy()]
+
+    def decode_labels(self, result, device=False):
+        """DecodeCTCPred.decode_labels' contract: (n, T, C) softmax -> (n, Lmax) int32 label rows of the best word padded with -1 (all -1 where
+        no word has a finite score).  device=True: -> (labels, lengths) int32 DEVICE tensors, nothing copied back."""
+        import torch
+        idx, _ = self._topk(result, None, 1)
+        labels, lengths = self.lexicon.device(idx.device)
+        n, width = idx.shape[0], self.lexicon.labels.shape[1]
+        if len(self.lexicon) == 0:
+            rows = torch.full((n, width), -1, dtype=torch.int32, device=idx.device)
+            lens = torch.zeros(n, dtype=torch.int32, device=idx.device)
+        else:
+            best = idx[:, 0].long()
+            none = best < 0
+            best = best.clamp(min=0)
+            rows = torch.where(none[:, None], torch.full_like(labels[:1], -1), labels[best])
+            lens = torch.where(none, torch.zeros_like(lengths[:1]), lengths[best])
+        return (rows, lens) if device else rows.cpu().numpy()
+
+    def log_prob(self, result, texts):
+        """The exact CTC log-probability of one given transcription per image (one candidate per image, the same kernel): the confidence of
+        a beam result.  -> (n,) float32 ndarray; -inf for a text the alphabet cannot spell, one longer than 31, or one the frames cannot hold."""
+        import torch
+        y = result if torch.is_tensor(result) else torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32))
+        y = (y if y.is_cuda else y.cuda()).contiguous().float()
+        n = y.shape[0]
+        if len(texts) != n:
+            raise ValueError("log_prob: %d texts for %d images" % (len(texts), n))
+        enc = [self.lexicon.encode(str(t)) for t in texts]
+        table = np.full((max(n, 1), max([len(e) for e in enc if e is not None] + [1])), -1, dtype=np.int32)
+        lens = np.full(max(n, 1), -1, dtype=np.int32)                  # -1: a table entry the kernel does not trust -> -inf
+        for i, e in enumerate(enc):
+            if e is not None:
+                table[i, :len(e)] = e; lens[i] = len(e)
+        cand = torch.arange(n, dtype=torch.int32, device=y.device).reshape(n, 1)
+        scores = lexicon_scores(y, torch.from_numpy(table).to(y.device), torch.from_numpy(lens).to(y.device), self.skip, cand)
+        return scores[:, 0].cpu().numpy()

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Prediction CLI with the reference's flag surface (predict.py:62-79): forward on the GPU, whole-batch
 HIP beam-search decode (beam_width=10, top_paths=1, merge_repeated as TF 1.8), optional edit-distance report
-and prediction.csv.  --device_score (with --validate) keeps decoding and scoring on the GPU: same report, same prediction.csv."""
+and prediction.csv.  --device_score (with --validate) keeps decoding and scoring on the GPU: same report, same prediction.csv.
+--lexicon FILE decodes to the most probable word of a list (crnn_mi355x.lexicon) instead of the beam search."""
 import argparse
 import os
 import pickle
@@ -35,6 +36,8 @@ def build_parser():
                         help='build the batches on the GPU: pages go up as uint8 with a box table, one kernel crops, pads and normalises')
     parser.add_argument('--device_score', action='store_true',
                         help='with --validate: decode and score on the GPU (one edit-distance kernel per batch); no softmax map is copied to the host')
+    parser.add_argument('--lexicon', type=str, default=None,
+                        help='a word list, one word per line: decode to the word of the list with the highest CTC probability instead of the beam search')
     return parser
 
 
@@ -57,6 +60,13 @@ def main(argv=None):
     classes = {ch: i for i, ch in enumerate(U.get_lexicon())}
     inverse_classes = {v: k for k, v in classes.items()}
     decoder = U.DecodeCTCPred(top_paths=1, beam_width=10, inverse_classes=inverse_classes)
+    if args.lexicon is not None:
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")                  # the count is printed below instead
+            lexicon = U.Lexicon([line.rstrip("\r\n") for line in open(args.lexicon)], inverse_classes)
+        print(" [INFO] Lexicon: %d words, %d rejected (a character outside the alphabet, or longer than 31) " % (len(lexicon), len(lexicon.rejected)))
+        decoder = U.LexiconDecoder(lexicon, top_paths=1)
     img_size = (args.imgh, args.imgW, 1)
 
     def walk():

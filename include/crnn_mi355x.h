@@ -207,6 +207,28 @@ int crnn_ctc_beam_decode(const float* y, const int* input_len, int* out, int* ou
 int crnn_edit_distance(const int* pred, int pred_cols, const int* truth, int truth_cols, int skip0, int skip1,
                        int* dist, int* pred_len, int* truth_len, int n, crnn_stream_t stream);
 
+/* ---- lexicon decoding: CTC log-probabilities of a word list (csrc/lexicon.hip) ------------------------------ */
+/* scores[b][j] = log p(word | y[b, skip : skip + Tb]) in Keras' semantics: the negative of what K.ctc_batch_cost / crnn_ctc_loss_grad return for
+ * that label on that window (z = log(y + 1e-7), TF's log-softmax applied again, fp32 log-domain alpha recursion, the same operations in the same
+ * order as the loss kernel).  y [B][T][C] softmax, blank = C - 1; input_len [B] frames used per sample, clamped to [0, T - skip], or NULL
+ * (= T - skip); skip = 0: the window the decoders read, 2: the training loss's window (utils.py:102).  words [N][Lmax] int32 label ids and
+ * word_len [N]: the word table.  cand [B][K] int32 or NULL: per-sample candidate lists as indices into the table, -1 = empty slot; NULL = every
+ * sample against every word (K ignored).  scores [B][M] fp32, M = N, or K with cand.  -inf where no path exists (a word longer than the frames
+ * allow once the blanks between its repeated letters are counted); Tb = 0: 0 for the empty word, -inf otherwise.  Nothing of the table is
+ * trusted: a word_len outside [0, Lmax], a label outside [0, C - 2], a candidate index outside [0, N) (the -1 of an empty slot included) score
+ * -inf and index nothing.  ws: crnn_ctc_lexicon_workspace_bytes(B, T, C, skip) bytes = lsm [B][T - skip][C] fp32, written by a pre-pass (one
+ * log-softmax per sample, not per workgroup) and read by the scoring kernel, which holds one sample's map in LDS.
+ * Supported: C <= 128, Lmax <= 31 (S = 2L + 1 <= 63 states, one per lane) and an LDS budget of 64 KiB for the map: (T - skip) * C * 4 <= 65536
+ * (T = 102 at C = 128 is 52 KB), else -3; -2 for a null pointer (y, words, word_len, scores, ws), a negative size, C < 2, T <= skip or a workspace
+ * that is too small.  B, N or K equal to 0 launches nothing. */
+size_t crnn_ctc_lexicon_workspace_bytes(int B, int T, int C, int skip);
+int crnn_ctc_lexicon_score(const float* y, const int* input_len, const int* words, const int* word_len, const int* cand, float* scores,
+                           void* ws, size_t ws_bytes, int B, int T, int C, int skip, int N, int Lmax, int K, crnn_stream_t stream);
+/* The k best (1 <= k <= 8, else -2) of each row of scores [B][M]: idx [B][k] int32 = position j, or cand[b][j] when cand [B][M] is given (the
+ * word-table index), val [B][k] = the score; descending by score, equal scores to the lower position j; slots with no finite score left get
+ * idx = -1, val = -inf.  One launch, one workgroup per row, a fixed order: two calls on the same input agree bit for bit.  No workspace. */
+int crnn_ctc_lexicon_topk(const float* scores, const int* cand, int* idx, float* val, int B, int M, int k, crnn_stream_t stream);
+
 /* ---- input side: word crops of page images -> the batch crnn_forward reads (reference utils.py:364-416, open_img + norm) ---- */
 /* One crop.  The page is a row-major uint8 image at byte `page_off` of the arena; the crop is page[r0:r1, c0:c1] (hc x wc), rotated so that the
  * text direction becomes axis 0: rot(i, j) = page[r0 + hc - 1 - j, c0 + i], shape (wc, hc).  upscale: wc <= imgh/2 and hc <= imgw/2 -- the content is
