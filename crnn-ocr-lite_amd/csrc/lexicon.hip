@@ -2,7 +2,7 @@
 //   scores[b][j] = log p(word_j | y[b, skip : skip + Tb]) = -K.ctc_batch_cost(word_j, y[b, skip:], Tb, |word_j|)     (utils.py:98-103 per pair)
 // B x N independent alpha recursions over the same B maps: a throughput kernel, not a loop over ctc_loss_grad_kernel (16 waves, a beta recursion
 // and a gradient phase per pair).  Three kernels:
-//   lex_lsm_kernel     pre-pass, once per sample: lsm = log_softmax(log(y + 1e-7)) of the window's rows into the workspace -- phase 1 of
+//   lex_lsm_kernel     (lex_lsm.h) pre-pass, once per sample: lsm = log_softmax(log(y + 1e-7)) of the window's rows into the workspace -- phase 1 of
 //                      ctc_loss_grad_kernel word for word (a time step per wave, CPL = 1 or 2 classes per lane), so that the per-image-candidates
 //                      mode (a few dozen words per image) does not pay a log-softmax per workgroup.
 //   lex_score_kernel   one workgroup = one sample x a tile of 4 x wpw words (wpw = 16; ceil(M / 4), at least 4, for rows of fewer than 64 words).  The sample's lsm [Tb][C] is copied into LDS (7.6 KB at T = 50, C = 38:
@@ -33,13 +33,12 @@
 //   * Not built: a linear-domain recursion with a wave-wide scale -- it flushes unlikely words to -inf where the oracle has -200; two independent words
 //     interleaved in one wave's instruction stream -- the issue slots it would fill are full.
 #include "common.h"
+#include "lex_lsm.h"      // lex_lsm_kernel, LEX_EPS, NEG_INF: shared with align.hip
 #include <limits.h>
 
 #ifndef LEX_PACK
 #define LEX_PACK 2
 #endif
-#define LEX_EPS 1e-7f
-#define NEG_INF (-INFINITY)
 #define LEX_WAVES 4
 #define LEX_WORDS_PER_WAVE 16         // words a wave walks: one copy of the map into LDS serves 64 words; rows shorter than that (candidate lists) are dealt
 #define LEX_WORDS_PER_WAVE_MIN 4      // evenly to the four waves, ceil(M / 4) each and at least 4 -- a workgroup's waves sit on the CU's four SIMDs
@@ -58,33 +57,6 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
   const float m = fmaxf(a, fmaxf(b, c));
   const float mm = (m == NEG_INF) ? 0.f : m;
   return mm + logf(expf(a - mm) + expf(b - mm) + expf(c - mm));
-}
-
-// ---- pre-pass: lsm [B][Tmax][C] = log_softmax(log(y[b, skip + t] + eps)), one wave per row ----------------------------------------------
-template <int CPL>
-__global__ __launch_bounds__(256) void lex_lsm_kernel(const float* __restrict__ y, float* __restrict__ lsm, long rows, int T, int Tmax, int C, int skip) {
-  const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const long b = row / Tmax;
-  const int t = (int)(row - b * Tmax);
-  const float* ys = y + ((long)b * T + skip + t) * C;
-  float* out = lsm + row * C;
-  const float z = lane < C ? logf(ys[lane] + LEX_EPS) : NEG_INF;
-  if constexpr (CPL == 1) {
-    const float m = wave_max(z);
-    const float e = lane < C ? expf(z - m) : 0.f;
-    const float lz = m + logf(wave_sum(e));
-    if (lane < C) out[lane] = z - lz;
-  } else {
-    const bool up = lane + 64 < C;
-    const float z1 = up ? logf(ys[lane + 64] + LEX_EPS) : NEG_INF;
-    const float m = wave_max(fmaxf(z, z1));
-    const float e = (lane < C ? expf(z - m) : 0.f) + (up ? expf(z1 - m) : 0.f);
-    const float lz = m + logf(wave_sum(e));
-    if (lane < C) out[lane] = z - lz;
-    if (up) out[lane + 64] = z1 - lz;
-  }
 }
 
 // ---- scores ------------------------------------------------------------------------------------------------------------------------------
@@ -235,11 +207,8 @@ extern "C" int crnn_ctc_lexicon_score(const float* y, const int* input_len, cons
   const int wpw = max(LEX_WORDS_PER_WAVE_MIN, min(LEX_WORDS_PER_WAVE, cdiv(M, LEX_WAVES)));
   const int tiles = cdiv(M, LEX_WAVES * wpw);
   if ((long)B * tiles > 0x7fffffffL) return CRNN_ERR_UNSUPPORTED;
-  const long rows = (long)B * Tmax;
   float* lsm = (float*)ws;
-  if (C <= 64) hipLaunchKernelGGL(lex_lsm_kernel<1>, dim3(cdiv(rows, 4)), dim3(256), 0, stream, y, lsm, rows, T, Tmax, C, skip);
-  else hipLaunchKernelGGL(lex_lsm_kernel<2>, dim3(cdiv(rows, 4)), dim3(256), 0, stream, y, lsm, rows, T, Tmax, C, skip);
-  CRNN_LAUNCH_CHECK();
+  CRNN_TRY(lex_lsm_launch(y, lsm, B, T, C, skip, stream));
   hipLaunchKernelGGL(lex_score_kernel, dim3(B * tiles), dim3(64 * LEX_WAVES), lds, stream, (const float*)lsm, input_len, words, word_len, cand, scores,
                      Tmax, C, N, Lmax, M, tiles, wpw);
   CRNN_LAUNCH_CHECK();

@@ -2,7 +2,9 @@
 """Prediction CLI with the reference's flag surface (predict.py:62-79): forward on the GPU, whole-batch
 HIP beam-search decode (beam_width=10, top_paths=1, merge_repeated as TF 1.8), optional edit-distance report
 and prediction.csv.  --device_score (with --validate) keeps decoding and scoring on the GPU: same report, same prediction.csv.
---lexicon FILE decodes to the most probable word of a list (crnn_mi355x.lexicon) instead of the beam search."""
+--lexicon FILE decodes to the most probable word of a list (crnn_mi355x.lexicon) instead of the beam search.
+--align (with --result_path) aligns every prediction to its own softmax map (crnn_mi355x.align) and writes alignment.csv: per character its frames
+on the network's time axis and its log-probability."""
 import argparse
 import os
 import pickle
@@ -38,6 +40,8 @@ def build_parser():
                         help='with --validate: decode and score on the GPU (one edit-distance kernel per batch); no softmax map is copied to the host')
     parser.add_argument('--lexicon', type=str, default=None,
                         help='a word list, one word per line: decode to the word of the list with the highest CTC probability instead of the beam search')
+    parser.add_argument('--align', action='store_true',
+                        help='with --result_path: also write alignment.csv -- the best CTC path of every prediction through its own softmax map, per character its frames and log-probability')
     return parser
 
 
@@ -46,6 +50,10 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.device_score and not args.validate:
         parser.error("--device_score scores against the truth: it needs --validate")
+    if args.align and args.result_path is None:
+        parser.error("--align writes alignment.csv next to prediction.csv: it needs --result_path")
+    if args.align and args.device_score:
+        parser.error("--align reads the softmax maps, which --device_score never materialises: use one or the other")
     return args
 
 
@@ -121,6 +129,10 @@ def main(argv=None):
         pd.DataFrame({"fname": fnames, "prediction": predicted_text}).to_csv(out_name)
         print(" [INFO] Prediction example: \n", predicted_text[:10])
         print(" [INFO] Result store in: ", out_name)
+        if args.align:
+            from crnn_mi355x.align import CTCAligner, write_alignment_csv
+            aligned = CTCAligner(inverse_classes).align(predicted[:length], predicted_text)
+            write_alignment_csv(os.path.join(args.result_path, "alignment.csv"), fnames, aligned)
     if args.validate:
         print(" [INFO] Computing edit distance metric... ")
         start = time.time()

@@ -229,6 +229,29 @@ int crnn_ctc_lexicon_score(const float* y, const int* input_len, const int* word
  * idx = -1, val = -inf.  One launch, one workgroup per row, a fixed order: two calls on the same input agree bit for bit.  No workspace. */
 int crnn_ctc_lexicon_topk(const float* scores, const int* cand, int* idx, float* val, int B, int M, int k, crnn_stream_t stream);
 
+/* ---- character alignment: the best CTC path of a given transcription, with its backtrace (csrc/align.hip) ---- */
+/* Per sample the Viterbi path of labels[b] through y[b, skip : skip + Tb]: where each character sits on the time axis and the log-probability
+ * mass of each.  y, input_len, skip, the window, blank = C - 1 and the workspace are crnn_ctc_lexicon_score's: ws holds lsm [B][T - skip][C] fp32 =
+ * log_softmax(log(y + 1e-7)), written by the same pre-pass, bit for bit.  labels [B][Lmax] int32: ONE row per sample, padding of any value;
+ * label_len [B]; Lmax is only the row stride and may be as large as T -- what the decoders' decode_labels(device=True) return.  All frame
+ * indices are window coordinates: frame 0 is y[b, skip].
+ * Recursion, fp32 over lsm: ext[s] = blank for even s, labels[(s - 1) / 2] for odd s, S = 2 len + 1 states; v_0[0] = lsm[0][blank],
+ * v_0[1] = lsm[0][ext[1]] (S > 1), -inf elsewhere; v_t[s] = max(v_{t-1}[s], v_{t-1}[s-1], v_{t-1}[s-2] where s is odd and ext[s] != ext[s-2])
+ * + lsm[t][ext[s]].  TIE RULE: equal values go to the higher state index -- among the predecessors stay beats s - 1 beats s - 2 (strict > in
+ * that order); at the end S - 1 beats S - 2 unless v[S-2] > v[S-1].
+ * score [B]: the value of the best path = the fp32 sum of lsm[t][ext[path[t]]] added in increasing t, bit for bit.  The other outputs may each
+ * be NULL (not wanted): states [B][T - skip] the state 0..2 len of the best path for t < Tb, -1 for t >= Tb; start, end [B][Lmax]: for
+ * character l < len the first frame in state 2l + 1 and one past the last; char_logp [B][Lmax]: the sum of lsm[t][label_l] over that span, fp32,
+ * in increasing t from the first frame's value.  Every slot that belongs to no aligned character: start = end = -1, char_logp = -inf.
+ * A sample WITHOUT an alignment gets score = -inf, states all -1 and its slots filled as above: the frames cannot hold the word once the blanks
+ * between repeated letters are counted; label_len outside [0, min(Lmax, 31)]; a label outside [0, C - 2] inside the length.  Nothing is indexed
+ * through such a value.  A map with a NaN, an infinity or a negative entry inside the window (not a softmax map) gives no alignment as well.  Tb = 0: score exactly 0 for the empty word, -inf otherwise; len = 0: every frame in state 0.
+ * -2 for a null y, labels, label_len, score or ws, a negative size, C < 2, T <= skip, Lmax < 1 or a workspace that is too small; -3 for C > 128
+ * or T - skip > 512 (backpointers and path live in LDS: 10.5 KB per sample at 512 frames).  B == 0 launches nothing. */
+size_t crnn_ctc_align_workspace_bytes(int B, int T, int C, int skip);   /* == crnn_ctc_lexicon_workspace_bytes */
+int crnn_ctc_align(const float* y, const int* input_len, const int* labels, const int* label_len, float* score, int* states, int* start,
+                   int* end, float* char_logp, void* ws, size_t ws_bytes, int B, int T, int C, int skip, int Lmax, crnn_stream_t stream);
+
 /* ---- input side: word crops of page images -> the batch crnn_forward reads (reference utils.py:364-416, open_img + norm) ---- */
 /* One crop.  The page is a row-major uint8 image at byte `page_off` of the arena; the crop is page[r0:r1, c0:c1] (hc x wc), rotated so that the
  * text direction becomes axis 0: rot(i, j) = page[r0 + hc - 1 - j, c0 + i], shape (wc, hc).  upscale: wc <= imgh/2 and hc <= imgw/2 -- the content is
