@@ -15,10 +15,9 @@ import collections
 
 import numpy as np
 
-from .lexicon import MAX_WORD_LEN
+from .labels import CHUNK, Alphabet, device_map, label_table  # noqa: F401  (CHUNK: importable from here as before)
 
 MAX_FRAMES = 512             # the library's limit on T - skip: backpointers and the path live in LDS
-CHUNK = 4096                 # images per launch, and per upload of a host array: what decode_labels uses
 
 CharSpan = collections.namedtuple("CharSpan", "char start end log_prob")
 CharSpan.__doc__ = """One aligned character: frames [start, end) of the softmax map it occupies (skip included), and the sum of its log-probabilities there."""
@@ -30,7 +29,7 @@ per frame of the window (even = blank, odd s = character (s - 1) / 2; -1 past th
 def ctc_align(y, labels, lengths, skip=0, input_length=None):
     """y (B, T, C) float32 device tensor, labels (B, Lmax) / lengths (B,) int32 device tensors (one row per sample, any padding),
     input_length (B,) int32 device tensor or None -> dict of device tensors: score (B,), states (B, T - skip) int32, start / end (B, Lmax) int32
-    in frames of the window (frame 0 = y[:, skip]), char_logp (B, Lmax).  One pre-pass and one launch (crnn_ctc_align) per chunk of 4096; the
+    in frames of the window (frame 0 = y[:, skip]), char_logp (B, Lmax).  One pre-pass and one launch (crnn_ctc_align) per CHUNK images; the
     outputs of the whole batch are allocated at once (4 (T - skip) + 12 Lmax + 4 bytes per image, next to a map of 4 T C).  A map with a NaN, an
     infinity or a negative entry gives no alignment.  Raises ValueError for more than 512 frames."""
     import torch
@@ -72,39 +71,21 @@ class CTCAligner:
     2 over the training loss's window; spans are reported in frames of the map either way."""
 
     def __init__(self, inverse_classes, skip=0):
-        items = inverse_classes.items() if hasattr(inverse_classes, "items") else enumerate(inverse_classes)
-        self.inverse_classes = inverse_classes
-        self.classes = {str(ch): int(k) for k, ch in items}
+        self.alphabet = Alphabet(inverse_classes)
+        self.inverse_classes, self.classes = inverse_classes, self.alphabet.classes
         self.skip = skip
 
     def encode(self, text):
         """Lexicon.encode's rule: -> list of label ids, or None for a text the alphabet cannot spell or one longer than 31."""
-        if len(text) > MAX_WORD_LEN:
-            return None
-        ids = [self.classes.get(ch) for ch in text]
-        return None if any(i is None for i in ids) else ids
+        return self.alphabet.encode(text)
 
     def _table(self, texts):
-        """-> (labels (n, width) int32 padded with -1, lengths (n,) int32; -1 = a text that cannot be aligned: the kernel does not trust it)"""
-        enc = [self.encode(str(t)) for t in texts]
-        n = len(enc)
-        table = np.full((max(n, 1), max([len(e) for e in enc if e is not None] + [1])), -1, dtype=np.int32)
-        lens = np.full(max(n, 1), -1, dtype=np.int32)
-        for i, e in enumerate(enc):
-            if e is not None:
-                table[i, :len(e)] = e; lens[i] = len(e)
-        return table[:n], lens[:n]
-
-    @staticmethod
-    def _device_map(result):
-        import torch
-        y = result if torch.is_tensor(result) else torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32))
-        return (y if y.is_cuda else y.cuda()).contiguous().float()
+        return label_table([self.encode(str(t)) for t in texts])
 
     def align_labels(self, result, labels, lengths):
         """result (n, T, C) softmax (ndarray or device tensor), labels (n, Lmax) / lengths (n,) int32 device tensors -> ctc_align's dict of device
         tensors; nothing is copied back.  Frames are those of the window: add `skip` for frames of `result`."""
-        y = self._device_map(result)
+        y = device_map(result)
         return ctc_align(y, labels.to(y.device), lengths.to(y.device), self.skip)
 
     def _alignments(self, out, texts):
@@ -122,19 +103,17 @@ class CTCAligner:
 
     def align(self, result, texts):
         """One given transcription per image -> [Alignment].  A text the alphabet cannot spell, or one longer than 31, or one the frames cannot
-        hold, gives log_prob = -inf and no chars.  A host array goes up in chunks of 4096 images, as decode_labels uploads it, and each chunk's
+        hold, gives log_prob = -inf and no chars.  A host array goes up in chunks of CHUNK images, as decode_labels uploads it, and each chunk's
         results come back before the next goes up."""
         import torch
         texts = [str(t) for t in texts]
         n = result.shape[0]
         if len(texts) != n:
             raise ValueError("align: %d texts for %d images" % (len(texts), n))
-        table, lens = self._table(texts)
-        if n == 0:
-            return []
+        table, lens = self._table(texts)                          # (-1 = a text that cannot be aligned: the kernel does not trust it)
         res = []
         for lo in range(0, n, CHUNK):
-            y = self._device_map(result[lo:lo + CHUNK])
+            y = device_map(result[lo:lo + CHUNK])
             out = ctc_align(y, torch.from_numpy(table[lo:lo + CHUNK]).to(y.device), torch.from_numpy(lens[lo:lo + CHUNK]).to(y.device), self.skip)
             res += self._alignments(out, texts[lo:lo + CHUNK])
         return res
@@ -142,7 +121,7 @@ class CTCAligner:
     def align_decoded(self, result, decoder):
         """Decode and align in one go: decoder.decode_labels(result, device=True) -- a DecodeCTCPred (beam or greedy) or a LexiconDecoder -- and the
         alignment of every image to its own decoding; the label rows never leave the device.  -> [Alignment], texts as decoder.decode gives them."""
-        y = self._device_map(result)
+        y = device_map(result)
         labels, lengths = decoder.decode_labels(y, device=True)
         out = self.align_labels(y, labels, lengths)
         rows, lens = labels.cpu().numpy(), lengths.cpu().numpy()

@@ -4,6 +4,8 @@ decoded by one launch of the HIP wavefront beam kernel (csrc/beam.hip), with TF-
 merge_repeated=True ('cellist' decodes to 'celist', as in the reference's own screenshots)."""
 import numpy as np
 
+from .labels import CHUNK, device_map
+
 
 def labels_to_text(labels, inverse_classes=None):
     """utils.py:314-321: blank (== len(inverse_classes)) or -1 -> ''."""
@@ -31,11 +33,9 @@ class DecodeCTCPred:
         from . import engine, native
         if self.beam_width < self.top_paths:
             self.beam_width = self.top_paths
-        y = result if torch.is_tensor(result) else torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32))
         out, lens = [], []
-        for lo in range(0, y.shape[0], 4096):
-            chunk = y[lo:lo + 4096]
-            chunk = (chunk if chunk.is_cuda else chunk.cuda()).contiguous()
+        for lo in range(0, len(result), CHUNK):
+            chunk = device_map(result[lo:lo + CHUNK])
             if self.greedy:
                 B, T, C = chunk.shape
                 lab = torch.empty((B, T), dtype=torch.int32, device=chunk.device)

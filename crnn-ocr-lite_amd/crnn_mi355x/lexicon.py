@@ -9,7 +9,8 @@ import warnings
 
 import numpy as np
 
-MAX_WORD_LEN = 31            # the library's max_len limit: 2 L + 1 <= 63 states, one per lane of a wavefront
+from .labels import CHUNK, MAX_WORD_LEN, Alphabet, device_map, label_table  # noqa: F401  (MAX_WORD_LEN: importable from here as before)
+
 MAX_TOP_PATHS = 8            # crnn_ctc_lexicon_topk
 SCORE_BYTES = 256 << 20      # default budget of the scores buffer [chunk][M] fp32: the batch is scored in chunks that stay under it
 
@@ -23,9 +24,8 @@ class Lexicon:
       .labels     (N, Lmax) int32 padded with -1  .lengths    (N,) int32        .index_of[p]  table index of caller position p, -1 if rejected"""
 
     def __init__(self, words, inverse_classes):
-        items = inverse_classes.items() if hasattr(inverse_classes, "items") else enumerate(inverse_classes)
-        self.inverse_classes = inverse_classes
-        self.classes = {str(ch): int(k) for k, ch in items}
+        self.alphabet = Alphabet(inverse_classes)
+        self.inverse_classes, self.classes = inverse_classes, self.alphabet.classes
         words = [str(w) for w in words]
         enc, pos, self.rejected = [], [], []
         for p, w in enumerate(words):
@@ -54,10 +54,7 @@ class Lexicon:
 
     def encode(self, word):
         """-> list of label ids, or None when the word cannot be scored."""
-        if len(word) > MAX_WORD_LEN:
-            return None
-        ids = [self.classes.get(ch) for ch in word]
-        return None if any(i is None for i in ids) else ids
+        return self.alphabet.encode(word)
 
     def device(self, device):
         """-> (labels, lengths) int32 tensors on `device`; uploaded on first use."""
@@ -144,17 +141,15 @@ class LexiconDecoder:
     def _topk(self, result, candidates, k):
         """-> (idx (n, k) int32 table indices or -1, val (n, k) float32), device tensors."""
         import torch
-        y = result if torch.is_tensor(result) else torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32))
-        n = y.shape[0]
+        n = len(result)
         cand = self._candidates(candidates, n) if candidates is not None else None
-        device = y.device if y.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        device = result.device if torch.is_tensor(result) and result.is_cuda else torch.device("cuda", torch.cuda.current_device())
         labels, lengths = self.lexicon.device(device)
         M = cand.shape[1] if cand is not None else len(self.lexicon)
-        rows = max(1, min(4096, self.score_bytes // (4 * max(M, 1))))
+        rows = max(1, min(CHUNK, self.score_bytes // (4 * max(M, 1))))
         idx, val = [], []
         for lo in range(0, n, rows):
-            chunk = y[lo:lo + rows]
-            chunk = (chunk if chunk.is_cuda else chunk.to(device)).contiguous().float()
+            chunk = device_map(result[lo:lo + rows], device)
             cd = torch.from_numpy(np.ascontiguousarray(cand[lo:lo + rows])).to(device) if cand is not None else None
             i, v = lexicon_topk(lexicon_scores(chunk, labels, lengths, self.skip, cd), k, cd)
             idx.append(i); val.append(v)
@@ -197,17 +192,11 @@ class LexiconDecoder:
         """The exact CTC log-probability of one given transcription per image (one candidate per image, the same kernel): the confidence of
         a beam result.  -> (n,) float32 ndarray; -inf for a text the alphabet cannot spell, one longer than 31, or one the frames cannot hold."""
         import torch
-        y = result if torch.is_tensor(result) else torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32))
-        y = (y if y.is_cuda else y.cuda()).contiguous().float()
+        y = device_map(result)
         n = y.shape[0]
         if len(texts) != n:
             raise ValueError("log_prob: %d texts for %d images" % (len(texts), n))
-        enc = [self.lexicon.encode(str(t)) for t in texts]
-        table = np.full((max(n, 1), max([len(e) for e in enc if e is not None] + [1])), -1, dtype=np.int32)
-        lens = np.full(max(n, 1), -1, dtype=np.int32)                  # -1: a table entry the kernel does not trust -> -inf
-        for i, e in enumerate(enc):
-            if e is not None:
-                table[i, :len(e)] = e; lens[i] = len(e)
+        table, lens = label_table([self.lexicon.encode(str(t)) for t in texts])
         cand = torch.arange(n, dtype=torch.int32, device=y.device).reshape(n, 1)
         scores = lexicon_scores(y, torch.from_numpy(table).to(y.device), torch.from_numpy(lens).to(y.device), self.skip, cand)
         return scores[:, 0].cpu().numpy()

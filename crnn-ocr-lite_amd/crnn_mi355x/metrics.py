@@ -2,6 +2,8 @@
 levenshtein -> float, edit_distance -> mean over pairs, normalized_edit_distance -> mean of d/len(truth)."""
 import numpy as np
 
+from .labels import class_items
+
 
 def levenshtein(seq1, seq2):
     """Two-row dynamic programme (the reference fills the full matrix; same result, returned as float)."""
@@ -34,9 +36,8 @@ def check_label_metric(inverse_classes):
     """An edit distance over label rows is the edit distance over the decoded TEXTS only when every class maps to a distinct string of
     exactly one character (labels_to_text joins str(inverse_classes[c])).  Raises ValueError naming the first class that breaks that;
     accepts the {id: character} dictionary DecodeCTCPred holds, or a lexicon list."""
-    items = inverse_classes.items() if hasattr(inverse_classes, "items") else enumerate(inverse_classes)
     seen = {}
-    for k, ch in items:
+    for k, ch in class_items(inverse_classes):
         s = str(ch)
         if len(s) != 1:
             raise ValueError("class %r maps to %r, not to one character: a distance over labels would not be the distance over texts" % (k, s))

@@ -76,10 +76,12 @@ def build(verbose=False):
     """Compile every HIP source for gfx950 into crnn-ocr-lite_amd/libcrnn_mi355x.so (in-tree)."""
     objs, jobs = [], []
     inc = os.path.join(REPO_ROOT, "include")
+    # every object depends on every header and include file of csrc and on the two public headers: a forgotten one would leave a stale library
+    headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc"))] + [HEADER, HOOKS_HEADER]
     for s in SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(CSRC, s.replace(".hip", ".o"))
-        deps = [src, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rnn_cell.h"), os.path.join(CSRC, "rnn_exchange.h"), os.path.join(CSRC, "gemm_bf16.inc"), os.path.join(CSRC, "lex_lsm.h"), HEADER]
+        deps = [src] + headers
         if not os.path.exists(obj) or any(os.path.getmtime(d) > os.path.getmtime(obj) for d in deps):
             jobs.append(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", inc, "-c", src, "-o", obj])
         objs.append(obj)
@@ -95,7 +97,7 @@ def build(verbose=False):
     if not os.path.exists(LIB_PATH) or any(os.path.getmtime(o) > os.path.getmtime(LIB_PATH) for o in objs):
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB_PATH])
     hsrc = os.path.join(CSRC, "testhooks.hip")
-    hdeps = [hsrc, os.path.join(CSRC, "common.h"), HEADER, HOOKS_HEADER]
+    hdeps = [hsrc] + headers
     if not os.path.exists(HOOKS_PATH) or any(os.path.getmtime(d) > os.path.getmtime(HOOKS_PATH) for d in hdeps):
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", inc, hsrc, "-o", HOOKS_PATH]
         if verbose:

@@ -3,7 +3,7 @@
 //   score[b]        = max over the CTC paths pi of labels[b] of sum_t lsm[t][pi_t],  lsm = log_softmax(log(y[b, skip : skip + Tb] + 1e-7))
 //   states[b][t]    = state of the best path at frame t (extended label: even = blank, odd s = character (s - 1) / 2), -1 for t >= Tb
 //   start / end [l] = first frame of character l and one past its last;  char_logp[l] = sum of lsm[t][label_l] over that span
-// Two kernels: lex_lsm_kernel (lex_lsm.h, the pre-pass of lexicon.hip: the same bits in the same workspace) and ctc_align_kernel.
+// Two kernels: lex_lsm_kernel (ctc_core.h, the pre-pass of lexicon.hip: the same bits in the same workspace) and ctc_align_kernel.
 //   ctc_align_kernel   one wavefront = one sample, ALIGN_WAVES samples per workgroup.  The extended label (S = 2L + 1 <= 63 states) lives one state
 //                      per lane as in ctc.hip / lexicon.hip.  Per frame: the s - 1 / s - 2 neighbours by two DPP wave shifts (a vector move each, no
 //                      LDS round trip), two compares, an add.  lsm[t][ext] does not depend on the chain: the 16 values of the NEXT block of frames
@@ -19,7 +19,7 @@
 // the blank; the sample's results are then replaced by "no alignment" (score -inf, states -1, no spans).  A map that is not a softmax map (a NaN, an infinity, a
 // negative entry) makes the path's value NaN: no alignment either, and the span pass reads only spans the path marked.
 #include "common.h"
-#include "lex_lsm.h"
+#include "ctc_core.h"
 
 #define ALIGN_WAVES 4
 #define ALIGN_MAX_LABEL_LEN 31
@@ -57,22 +57,14 @@ __global__ __launch_bounds__(64 * ALIGN_WAVES) void ctc_align_kernel(const float
   if (b >= B) return;                                     // (wave-uniform; no workgroup barrier below)
   cs[lane] = -1;                                          // cs and ce: no span until the path marks one
   const int blank = C - 1;
-  int Tb = input_len ? input_len[b] : Tmax; if (Tb > Tmax) Tb = Tmax; if (Tb < 0) Tb = 0;
-  Tb = __builtin_amdgcn_readfirstlane(Tb);
+  const int Tb = __builtin_amdgcn_readfirstlane(ctc_window(input_len, b, Tmax));
   int len = label_len[b];
   bool ok = len >= 0 && len <= Lmax && len <= ALIGN_MAX_LABEL_LEN;
   const int L = __builtin_amdgcn_readfirstlane(ok ? len : 0);      // an untrusted length walks as the empty word; its results are replaced below
   const int S = 2 * L + 1, s = lane;
-  int ext = blank;
-  bool bad = false;
-  if (s < S && (s & 1)) {
-    const int v = labels[(long)b * Lmax + (s >> 1)];
-    if (v < 0 || v > C - 2) bad = true; else ext = v;
-  }
-  ok = ok && !__ballot(bad);
+  const int ext = ctc_ext_checked(labels + (long)b * Lmax, S, s, C, ~0ull, ok);
   const int mylab = __shfl(ext, (2 * lane + 1) & 63, 64);          // lane l: the label of character l (validated above)
-  const int ext2 = __shfl_up(ext, 2, 64);
-  const bool can_skip = (s >= 2) && (s < S) && (ext != blank) && (ext != ext2);
+  const bool can_skip = ctc_can_skip(ext, s, S, blank);
   const float* lsm_b = lsm_g + (long)b * Tmax * C;
   const float* col = lsm_b + ext;                                  // lsm[t][ext] = col[t * C]
 
@@ -171,8 +163,7 @@ __global__ __launch_bounds__(64 * ALIGN_WAVES) void ctc_align_kernel(const float
 
 // ---- entry points --------------------------------------------------------------------------------------------------------------------------
 extern "C" size_t crnn_ctc_align_workspace_bytes(int B, int T, int C, int skip) {
-  if (B < 0 || C < 1 || skip < 0 || T <= skip) return 0;
-  return (size_t)B * (size_t)(T - skip) * (size_t)C * sizeof(float);
+  return lex_lsm_bytes(B, T, C, skip);
 }
 
 extern "C" int crnn_ctc_align(const float* y, const int* input_len, const int* labels, const int* label_len, float* score, int* states, int* start,
@@ -181,7 +172,7 @@ extern "C" int crnn_ctc_align(const float* y, const int* input_len, const int* l
   if (B < 0 || T < 0 || C < 2 || skip < 0 || T <= skip || Lmax < 1) return CRNN_ERR_ARG;
   const int Tmax = T - skip;
   if (C > 128 || Tmax > ALIGN_MAX_FRAMES) return CRNN_ERR_UNSUPPORTED;
-  if (ws_bytes < crnn_ctc_align_workspace_bytes(B, T, C, skip)) return CRNN_ERR_ARG;
+  if (ws_bytes < lex_lsm_bytes(B, T, C, skip)) return CRNN_ERR_ARG;
   if (B == 0) return CRNN_OK;
   float* lsm = (float*)ws;
   CRNN_TRY(lex_lsm_launch(y, lsm, B, T, C, skip, stream));

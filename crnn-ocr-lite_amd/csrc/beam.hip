@@ -16,14 +16,13 @@
 // one ballot per half, and the events of the lower half are consumed before those of the upper half -- label order, as above.  The blank (C - 1) then
 // always sits in the upper half.  The beam itself stays one entry per lane.
 #include "common.h"
+#include "ctc_core.h"      // CTC_EPS, NEG_INF, ctc_window
 
 #define BEAM_MAX 64          // one beam entry per lane
-#define BEAM_EPS 1e-7f
-#define BNEG (-INFINITY)
 
 __device__ __forceinline__ float blse(float a, float b) {
-  if (a == BNEG) return b;
-  if (b == BNEG) return a;
+  if (a == NEG_INF) return b;
+  if (b == NEG_INF) return a;
   float m = fmaxf(a, b), n = fminf(a, b);
   return m + log1pf(expf(n - m));
 }
@@ -79,13 +78,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   int* s_lab = s_par + BEAM_MAX;
   float* s_val = reinterpret_cast<float*>(s_lab + BEAM_MAX);
   const int b = blockIdx.x, lane = threadIdx.x, blank = C - 1;
-  int Tb = input_len ? input_len[b] : T; if (Tb > T) Tb = T; if (Tb < 0) Tb = 0;
+  const int Tb = ctc_window(input_len, b, T);
 
   // beam entry `lane` (valid for lane < n)
   int b_node = 0, b_par = -1, b_lab = -1, b_act = 0;
-  float b_ob = BNEG, b_ol = BNEG, b_ot = BNEG, b_nb = 0.f, b_nl = BNEG, b_nt = 0.f;
+  float b_ob = NEG_INF, b_ol = NEG_INF, b_ot = NEG_INF, b_nb = 0.f, b_nl = NEG_INF, b_nt = 0.f;
   // TopN slot `lane` (valid for lane < nle)
-  float l_v = BNEG; int l_ref = -1, l_par = -1, l_lab = -1;
+  float l_v = NEG_INF; int l_ref = -1, l_par = -1, l_lab = -1;
   int n = 1, nnodes = 1;
   if (lane == 0) nodes[0] = 0;
   __syncthreads();
@@ -104,15 +103,15 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   for (int t = 0; t < Tb; ++t) {
     const float ycur = ynext;
     if (t + 1 < Tb && lane < C) ynext = y[((long)b * T + t + 1) * C + lane];
-    float lg = (lane < C) ? logf(ycur + BEAM_EPS) : BNEG;
-    float inp, inp1 = BNEG, inp_blank;                   // lane = class (inp1: class lane + 64)
+    float lg = (lane < C) ? logf(ycur + CTC_EPS) : NEG_INF;
+    float inp, inp1 = NEG_INF, inp_blank;                   // lane = class (inp1: class lane + 64)
     if constexpr (CPL == 1) {
       inp = lg - wave_max64(lg);
       inp_blank = rl(inp, blank);
     } else {
       const float ycur1 = ynext1;
       if (t + 1 < Tb && lane + 64 < C) ynext1 = y[((long)b * T + t + 1) * C + lane + 64];
-      const float lg1 = (lane + 64 < C) ? logf(ycur1 + BEAM_EPS) : BNEG;
+      const float lg1 = (lane + 64 < C) ? logf(ycur1 + CTC_EPS) : NEG_INF;
       const float mx = wave_max64(fmaxf(lg, lg1));
       inp = lg - mx; inp1 = lg1 - mx;
       inp_blank = rl(inp1, blank - 64);
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     // ---- oldp <- newp; re-score the entries (parent term only while the parent is in the beam)
     b_ob = b_nb; b_ol = b_nl; b_ot = b_nt;
     {
-      float prev = BNEG; bool found = false;
+      float prev = NEG_INF; bool found = false;
       for (int j = 0; j < n; ++j) {
         int nj = rl(b_node, j), lj = rl(b_lab, j);
         float obj = rl(b_ob, j), otj = rl(b_ot, j);
@@ -132,10 +131,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         if (b_lab >> 6) in_lab = in_lab1;                  // (the root's label -1 never reads in_lab)
       }
       if (lane < n) {
-        float nl = BNEG;
+        float nl = NEG_INF;
         if (b_node != 0) {
           nl = found ? blse(b_ol, prev) : b_ol;
-          nl = (nl == BNEG) ? BNEG : nl + in_lab;
+          nl = (nl == NEG_INF) ? NEG_INF : nl + in_lab;
         }
         b_nb = b_ot + inp_blank; b_nl = nl; b_nt = blse(b_nb, nl);
       }
@@ -149,13 +148,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     for (int bi = 0; bi < n; ++bi) {
       const float bot = rl(b_ot, bi), bob = rl(b_ob, bi);
       const int blab = rl(b_lab, bi), bnode = rl(b_node, bi);
-      if (!(bot > BNEG && (nle < bw || bot > bval))) continue;
+      if (!(bot > NEG_INF && (nle < bw || bot > bval))) continue;
       const float prev = (lane == blab) ? bob : bot;
-      const float v = (lane < blank && prev > BNEG) ? inp + prev : BNEG;     // lane = child label
-      float v1 = BNEG;                                                          // child label lane + 64 (CPL == 2)
+      const float v = (lane < blank && prev > NEG_INF) ? inp + prev : NEG_INF;     // lane = child label
+      float v1 = NEG_INF;                                                          // child label lane + 64 (CPL == 2)
       if constexpr (CPL == 2) {
         const float prev1 = (lane + 64 == blab) ? bob : bot;
-        v1 = (lane + 64 < blank && prev1 > BNEG) ? inp1 + prev1 : BNEG;
+        v1 = (lane + 64 < blank && prev1 > NEG_INF) ? inp1 + prev1 : NEG_INF;
       }
       int cb = -1, cb1 = -1;
       for (int j = 0; j < n; ++j) {
@@ -163,10 +162,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
         if (pj == bnode && lj == lane) cb = j;                                  // this child is beam entry j
         if constexpr (CPL == 2) if (pj == bnode && lj == lane + 64) cb1 = j;
       }
-      const bool ev = (lane < blank) && (cb >= 0 || (v > BNEG && (nle < bw || v > bval)));
+      const bool ev = (lane < blank) && (cb >= 0 || (v > NEG_INF && (nle < bw || v > bval)));
       unsigned long long hmask[CPL];
       hmask[0] = __ballot(ev);
-      if constexpr (CPL == 2) hmask[1] = __ballot((lane + 64 < blank) && (cb1 >= 0 || (v1 > BNEG && (nle < bw || v1 > bval))));
+      if constexpr (CPL == 2) hmask[1] = __ballot((lane + 64 < blank) && (cb1 >= 0 || (v1 > NEG_INF && (nle < bw || v1 > bval))));
 #pragma unroll
       for (int h = 0; h < CPL; ++h) {                                           // label order: the lower half's events, then the upper half's
         unsigned long long mask = hmask[h];
@@ -178,7 +177,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
           const float vc = rl(vh, c);
           const int ccb = rl(cbh, c);
           if (ccb >= 0 && rl(b_act, ccb)) continue;                       // child already in the beam
-          if (vc > BNEG && (nle < bw || vc > bval)) {
+          if (vc > NEG_INF && (nle < bw || vc > bval)) {
             int slot;
             if (nle == bw) {                                                      // evict the bottom
               slot = bslot;
@@ -190,7 +189,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
             if (lane == slot) { l_v = vc; l_ref = -1; l_par = bi; l_lab = c + 64 * h; }
             wave_argmin(l_v, lane, nle, bval, bslot);
           } else if (ccb >= 0 && lane == ccb) {                                   // re-offered, rejected: reset oldp
-            b_ob = b_ol = b_ot = BNEG;
+            b_ob = b_ol = b_ot = NEG_INF;
           }
         }
       }
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     __syncthreads();
     if (lane < nle) { s_ref[rank] = l_ref; s_par[rank] = l_par; s_lab[rank] = l_lab; s_val[rank] = l_v; }
     __syncthreads();
-    int r_ref = -1, r_par = 0, r_lab = 0; float r_val = BNEG;
+    int r_ref = -1, r_par = 0, r_lab = 0; float r_val = NEG_INF;
     if (lane < nle) { r_ref = s_ref[lane]; r_par = s_par[lane]; r_lab = s_lab[lane]; r_val = s_val[lane]; }
     // surviving entries: copy from their old lane; new children: parent node from the parent's lane
     const int src = (r_ref >= 0) ? r_ref : (r_par & 63);
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     int new_node = g_node, new_par = g_par, new_lab = g_lab;
     float new_nb = g_nb, new_nl = g_nl, new_nt = g_nt;
     const bool is_new = (lane < nle) && (r_ref < 0);
-    if (is_new) { new_par = g_node; new_lab = r_lab; new_nb = BNEG; new_nl = r_val; new_nt = r_val; new_node = -1; }
+    if (is_new) { new_par = g_node; new_lab = r_lab; new_nb = NEG_INF; new_nl = r_val; new_nt = r_val; new_node = -1; }
     // resolve node ids of the new children one at a time (re-entering prefix -> reuse its node)
     unsigned long long nm = __ballot(is_new);
     while (nm) {

@@ -3,27 +3,13 @@
 //   K.ctc_decode(greedy=True|False, beam_width, top_paths=1)                 (utils.py:347-357)
 // The extended label sequence (S = 2L+1 <= 64) lives one state per lane; the alpha/beta recursions use
 // wavefront shuffles for the s-1 / s-2 neighbours, log-space fp32 throughout.
+// The arithmetic shared with lexicon.hip and align.hip -- the constants, lse2 / lse3, the row softmax and log-softmax, the alpha recursion -- is in ctc_core.h.
 #include "common.h"
+#include "ctc_core.h"
 
 #ifndef CRNN_CTC_EXP
 #define CRNN_CTC_EXP 0      // timing experiments (scripts/ctc_bench.py): 1 = stop after the log-softmax phase, 2 = after the recursions, 3 = before the log-softmax
 #endif
-#define CTC_EPS 1e-7f
-#define NEG_INF (-INFINITY)
-
-__device__ __forceinline__ float lse2(float a, float b) {
-  if (a == NEG_INF) return b;
-  if (b == NEG_INF) return a;
-  float m = fmaxf(a, b);
-  return m + logf(expf(a - m) + expf(b - m));
-}
-// log(e^a + e^b + e^c) in one go, branch-free (absent terms are -inf: e^-inf = 0): three exponentials and one logarithm on the recursions' dependent chain
-// where two nested lse2 took four and two
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  const float m = fmaxf(a, fmaxf(b, c));
-  const float mm = (m == NEG_INF) ? 0.f : m;                  // (all three absent: the sum below is 0 and its logarithm -inf)
-  return mm + logf(expf(a - mm) + expf(b - mm) + expf(c - mm));
-}
 
 // ---- row softmax over C (<= 128) classes: one wave per row ------------------------------------------
 // CPL = classes per lane: 1 for C <= 64 (lane l = class l), 2 for 65..128 (lane l = classes l and l + 64: the second value rides through the same
@@ -33,21 +19,12 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   long row = blockIdx.x * 4L + (threadIdx.x >> 6);
   int lane = threadIdx.x & 63;
   if (row >= rows) return;
-  float v = lane < C ? z[row * C + lane] : NEG_INF;
-  if constexpr (CPL == 1) {
-    float m = wave_max(v);
-    float e = lane < C ? expf(v - m) : 0.f;
-    float s = wave_sum(e);
-    if (lane < C) p[row * C + lane] = e / s;
-  } else {
-    const bool up = lane + 64 < C;
-    float v1 = up ? z[row * C + lane + 64] : NEG_INF;
-    float m = wave_max(fmaxf(v, v1));
-    float e = lane < C ? expf(v - m) : 0.f, e1 = up ? expf(v1 - m) : 0.f;
-    float s = wave_sum(e + e1);
-    if (lane < C) p[row * C + lane] = e / s;
-    if (up) p[row * C + lane + 64] = e1 / s;
-  }
+  const float v = lane < C ? z[row * C + lane] : NEG_INF;
+  float v1 = NEG_INF;
+  if constexpr (CPL == 2) v1 = lane + 64 < C ? z[row * C + lane + 64] : NEG_INF;
+  const ctc_lane_pair pr = softmax_row<CPL>(v, v1, lane, C);
+  if (lane < C) p[row * C + lane] = pr.lo;
+  if constexpr (CPL == 2) if (lane + 64 < C) p[row * C + lane + 64] = pr.hi;
 }
 extern "C" int crnn_softmax_rows(const float* z, float* p, long rows, int C, hipStream_t stream) {
   if (C > 128) return CRNN_ERR_UNSUPPORTED;
@@ -68,34 +45,18 @@ __global__ __launch_bounds__(256) void softmax_rows_perm_kernel(const float* __r
   if (m >= rows) return;
   const long orow = P ? (m % P) * (rows / P) + m / P : m;
   const float v = lane < C ? z[m * ldz + lane] + (bias ? bias[lane] : 0.f) : NEG_INF;
-  if constexpr (CPL == 1) {
-    const float mx = wave_max(v);
-    const float e = lane < C ? expf(v - mx) : 0.f;
-    const float sum = wave_sum(e);
-    if (lane < C) {
-      logits[orow * C + lane] = v;
-      const float pr = e / sum;
-      p1[orow * C + lane] = pr;
-      if (p2) p2[orow * C + lane] = pr;
-    }
-  } else {
-    const bool up = lane + 64 < C;
-    const float v1 = up ? z[m * ldz + lane + 64] + (bias ? bias[lane + 64] : 0.f) : NEG_INF;
-    const float mx = wave_max(fmaxf(v, v1));
-    const float e = lane < C ? expf(v - mx) : 0.f, e1 = up ? expf(v1 - mx) : 0.f;
-    const float sum = wave_sum(e + e1);
-    if (lane < C) {
-      logits[orow * C + lane] = v;
-      const float pr = e / sum;
-      p1[orow * C + lane] = pr;
-      if (p2) p2[orow * C + lane] = pr;
-    }
-    if (up) {
-      logits[orow * C + lane + 64] = v1;
-      const float pr = e1 / sum;
-      p1[orow * C + lane + 64] = pr;
-      if (p2) p2[orow * C + lane + 64] = pr;
-    }
+  float v1 = NEG_INF;
+  if constexpr (CPL == 2) v1 = lane + 64 < C ? z[m * ldz + lane + 64] + (bias ? bias[lane + 64] : 0.f) : NEG_INF;
+  const ctc_lane_pair pr = softmax_row<CPL>(v, v1, lane, C);
+  if (lane < C) {
+    logits[orow * C + lane] = v;
+    p1[orow * C + lane] = pr.lo;
+    if (p2) p2[orow * C + lane] = pr.lo;
+  }
+  if constexpr (CPL == 2) if (lane + 64 < C) {
+    logits[orow * C + lane + 64] = v1;
+    p1[orow * C + lane + 64] = pr.hi;
+    if (p2) p2[orow * C + lane + 64] = pr.hi;
   }
 }
 extern "C" int crnn_softmax_rows_perm(const float* z, int ldz, const float* bias, float* logits, float* p1, float* p2, long rows, int C, int permP,
@@ -134,7 +95,7 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int blank = C - 1;
   const int Tmax = T - skip;
-  int Tb = input_len[b]; if (Tb > Tmax) Tb = Tmax; if (Tb < 0) Tb = 0;
+  const int Tb = ctc_window(input_len[b], Tmax);
   const int L = label_len[b];
   const int S = 2 * L + 1;
   float* lsm = sm;                     // [Tmax][C]
@@ -165,23 +126,7 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
 #endif
   // phase 1: log-softmax of z = log(y + eps): a time step per wave, a class per lane (round 5: was one time step per THREAD -- 50 busy lanes of 256, each
   // evaluating 3 C logarithms and C exponentials in sequence: a fifth of the kernel)
-  for (int t = wave; t < Tb; t += CTC_WAVES) {
-    const float z = lane < C ? logf(ys[t * C + lane] + CTC_EPS) : NEG_INF;
-    if constexpr (CPL == 1) {
-      const float m = wave_max(z);
-      const float e = lane < C ? expf(z - m) : 0.f;
-      const float lz = m + logf(wave_sum(e));
-      if (lane < C) lsm[t * C + lane] = z - lz;
-    } else {
-      const bool up = lane + 64 < C;
-      const float z1 = up ? logf(ys[t * C + lane + 64] + CTC_EPS) : NEG_INF;
-      const float m = wave_max(fmaxf(z, z1));
-      const float e = (lane < C ? expf(z - m) : 0.f) + (up ? expf(z1 - m) : 0.f);
-      const float lz = m + logf(wave_sum(e));
-      if (lane < C) lsm[t * C + lane] = z - lz;
-      if (up) lsm[t * C + lane + 64] = z1 - lz;
-    }
-  }
+  for (int t = wave; t < Tb; t += CTC_WAVES) log_softmax_of_log_row<CPL>(ys + t * C, lsm + t * C, lane, C);
   __syncthreads();
 #if CRNN_CTC_EXP == 1
   return;
@@ -192,22 +137,16 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
   if (s < S && (s & 1)) ext = labels[(long)b * Lmax + (s >> 1)];
   // phase 2: the two recursions on two waves
   if (wave == 0) {
-    int ext2 = __shfl_up(ext, 2, 64);
-    const bool can_skip = (s >= 2) && (s < S) && (ext != blank) && (ext != ext2);
-    float a = NEG_INF;
-    if (s == 0) a = lsm[ext];
-    else if (s == 1 && S > 1) a = lsm[ext];
+    const bool can_skip = ctc_can_skip(ext, s, S, blank);
+    float a = ctc_alpha_init(lsm, ext, s, S);
     alpha[s] = a;
     for (int t = 1; t < Tb; ++t) {
       const float em = lsm[t * C + ext];                        // (independent of the chain: issued ahead of it)
-      const float a1 = __shfl_up(a, 1, 64), a2 = __shfl_up(a, 2, 64);
-      const float v = lse3(a, s >= 1 ? a1 : NEG_INF, can_skip ? a2 : NEG_INF);
-      a = (s < S && v != NEG_INF) ? v + em : NEG_INF;
+      a = ctc_alpha_step(a, em, s, S, can_skip);
       alpha[t * 64 + s] = a;
     }
-    float aL = __shfl(a, S - 1, 64);
-    float aL2 = (S > 1) ? __shfl(a, S - 2, 64) : NEG_INF;
-    if (lane == 0) ll_sh = lse2(aL, aL2);
+    const float ll0 = ctc_alpha_total(a, 0, S);
+    if (lane == 0) ll_sh = ll0;
   } else if (wave == 1) {
     // beta includes the emission at t, like alpha
     int extn2 = __shfl_down(ext, 2, 64);

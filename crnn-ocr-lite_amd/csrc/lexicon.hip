@@ -2,9 +2,8 @@
 //   scores[b][j] = log p(word_j | y[b, skip : skip + Tb]) = -K.ctc_batch_cost(word_j, y[b, skip:], Tb, |word_j|)     (utils.py:98-103 per pair)
 // B x N independent alpha recursions over the same B maps: a throughput kernel, not a loop over ctc_loss_grad_kernel (16 waves, a beta recursion
 // and a gradient phase per pair).  Three kernels:
-//   lex_lsm_kernel     (lex_lsm.h) pre-pass, once per sample: lsm = log_softmax(log(y + 1e-7)) of the window's rows into the workspace -- phase 1 of
-//                      ctc_loss_grad_kernel word for word (a time step per wave, CPL = 1 or 2 classes per lane), so that the per-image-candidates
-//                      mode (a few dozen words per image) does not pay a log-softmax per workgroup.
+//   lex_lsm_kernel     (ctc_core.h) pre-pass, once per sample: lsm = log_softmax(log(y + 1e-7)) of the window's rows into the workspace, so that the
+//                      per-image-candidates mode (a few dozen words per image) does not pay a log-softmax per workgroup.
 //   lex_score_kernel   one workgroup = one sample x a tile of 4 x wpw words (wpw = 16; ceil(M / 4), at least 4, for rows of fewer than 64 words).  The sample's lsm [Tb][C] is copied into LDS (7.6 KB at T = 50, C = 38:
 //                      the 32 waves of a CU are resident); each wave walks wpw words of the tile.  The extended label
 //                      (S = 2L + 1 <= 63 states) lives one state per lane as in ctc.hip; per frame one LDS gather lsm[t][ext] (independent of the chain,
@@ -20,7 +19,7 @@
 //                      position wins a tie), then k rounds of a workgroup arg-max over the threads' heads (value descending, position ascending).
 //                      One launch, a fixed order: two calls agree bit for bit.
 // Arithmetic: the operations of ctc_loss_grad_kernel in its order (logf(y + eps), max-shifted log-softmax, lse3 in fp32, lse2 of the last two
-// states); lse2 / lse3 below are ctc.hip's spelling, kept per translation unit so that the loss kernel's code does not move.
+// states) -- the loss kernel's own code: both take the rows, the trusted label and the alpha recursion from ctc_core.h.
 // Measured (scripts/lexicon_bench.py -> profiles/lexicon_bench.txt; batch 1024, T = 52, C = 38, lexicons of lengths 2..23 sorted by length, MI355X):
 //   * The recursion step is 66 vector instructions (3 v_exp, 1 v_log; expf / logf with their range reduction are most of it), 2 ds_bpermute, 1 ds_read: with 8
 //     waves per SIMD the kernel is bound by vector issue, not by the chain's latency -- 210 cycles per (wave x frame) and SIMD at the nominal clock against about
@@ -33,7 +32,7 @@
 //   * Not built: a linear-domain recursion with a wave-wide scale -- it flushes unlikely words to -inf where the oracle has -200; two independent words
 //     interleaved in one wave's instruction stream -- the issue slots it would fill are full.
 #include "common.h"
-#include "lex_lsm.h"      // lex_lsm_kernel, LEX_EPS, NEG_INF: shared with align.hip
+#include "ctc_core.h"
 #include <limits.h>
 
 #ifndef LEX_PACK
@@ -47,18 +46,6 @@
 #define LEX_TOPK_MAX 8
 #define LEX_TOPK_THREADS 256
 
-__device__ __forceinline__ float lse2(float a, float b) {
-  if (a == NEG_INF) return b;
-  if (b == NEG_INF) return a;
-  float m = fmaxf(a, b);
-  return m + logf(expf(a - m) + expf(b - m));
-}
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  const float m = fmaxf(a, fmaxf(b, c));
-  const float mm = (m == NEG_INF) ? 0.f : m;
-  return mm + logf(expf(a - mm) + expf(b - mm) + expf(c - mm));
-}
-
 // ---- scores ------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * LEX_WAVES) void lex_score_kernel(const float* __restrict__ lsm_g, const int* __restrict__ input_len,
                                                                    const int* __restrict__ words, const int* __restrict__ word_len,
@@ -70,8 +57,7 @@ __global__ __launch_bounds__(64 * LEX_WAVES) void lex_score_kernel(const float* 
   const int b = blockIdx.x / tiles;
   int tile = blockIdx.x - b * tiles + b % tiles; if (tile >= tiles) tile -= tiles;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int blank = C - 1;
-  int Tb = input_len ? input_len[b] : Tmax; if (Tb > Tmax) Tb = Tmax; if (Tb < 0) Tb = 0;
+  const int Tb = ctc_window(input_len, b, Tmax);
   const float* src = lsm_g + (long)b * Tmax * C;
   for (int i = tid; i < Tb * C; i += 64 * LEX_WAVES) lsm[i] = src[i];
   __syncthreads();
@@ -100,33 +86,19 @@ __global__ __launch_bounds__(64 * LEX_WAVES) void lex_score_kernel(const float* 
     const int L = seg == 0 ? Lq[0] : seg == 1 ? Lq[1] : seg == 2 ? Lq[2] : Lq[3];
     bool ok = seg == 0 ? okq[0] : seg == 1 ? okq[1] : seg == 2 ? okq[2] : okq[3];
     const int S = 2 * L + 1;
-    int ext = blank;
-    bool bad = false;
-    if (s < S && (s & 1)) {
-      const int v = words[(long)n * Lmax + (s >> 1)];
-      if (v < 0 || v > C - 2) bad = true; else ext = v;
-    }
     const unsigned long long segmask = lg == 6 ? ~0ull : ((1ull << (1 << lg)) - 1) << (seg << lg);
-    ok = ok && !(__ballot(bad) & segmask);
+    const int ext = ctc_ext_checked(words + (long)n * Lmax, S, s, C, segmask, ok);
     float res;
     if (Tb == 0) {
       res = L == 0 ? 0.f : NEG_INF;
     } else {
-      const int ext2 = __shfl_up(ext, 2, 64);
-      const bool can_skip = (s >= 2) && (s < S) && (ext != blank) && (ext != ext2);
-      float a = NEG_INF;
-      if (s == 0) a = lsm[ext];
-      else if (s == 1 && S > 1) a = lsm[ext];
+      const bool can_skip = ctc_can_skip(ext, s, S, C - 1);
+      float a = ctc_alpha_init(lsm, ext, s, S);
       for (int t = 1; t < Tb; ++t) {
         const float em = lsm[t * C + ext];                        // (independent of the chain: issued ahead of it)
-        const float a1 = __shfl_up(a, 1, 64), a2 = __shfl_up(a, 2, 64);
-        const float v = lse3(a, s >= 1 ? a1 : NEG_INF, can_skip ? a2 : NEG_INF);
-        a = (s < S && v != NEG_INF) ? v + em : NEG_INF;
+        a = ctc_alpha_step(a, em, s, S, can_skip);
       }
-      const int base = lane - s;
-      const float aL = __shfl(a, base + S - 1, 64);
-      const float aL2x = __shfl(a, base + (S > 1 ? S - 2 : 0), 64);
-      res = lse2(aL, S > 1 ? aL2x : NEG_INF);
+      res = ctc_alpha_total(a, lane - s, S);
     }
     if (!ok) res = NEG_INF;
     if (s == 0 && j + seg < j1) scores[(long)b * M + j + seg] = res;
@@ -189,8 +161,7 @@ __global__ __launch_bounds__(LEX_TOPK_THREADS) void lex_topk_kernel(const float*
 
 // ---- entry points --------------------------------------------------------------------------------------------------------------------------
 extern "C" size_t crnn_ctc_lexicon_workspace_bytes(int B, int T, int C, int skip) {
-  if (B < 0 || C < 1 || skip < 0 || T <= skip) return 0;
-  return (size_t)B * (size_t)(T - skip) * (size_t)C * sizeof(float);
+  return lex_lsm_bytes(B, T, C, skip);
 }
 
 extern "C" int crnn_ctc_lexicon_score(const float* y, const int* input_len, const int* words, const int* word_len, const int* cand, float* scores,
@@ -201,7 +172,7 @@ extern "C" int crnn_ctc_lexicon_score(const float* y, const int* input_len, cons
   const int Tmax = T - skip;
   const size_t lds = (size_t)Tmax * C * sizeof(float);
   if (lds > LEX_LDS_BYTES) return CRNN_ERR_UNSUPPORTED;
-  if (ws_bytes < crnn_ctc_lexicon_workspace_bytes(B, T, C, skip)) return CRNN_ERR_ARG;
+  if (ws_bytes < lex_lsm_bytes(B, T, C, skip)) return CRNN_ERR_ARG;
   const int M = cand ? K : N;
   if (B == 0 || N == 0 || M == 0) return CRNN_OK;
   const int wpw = max(LEX_WORDS_PER_WAVE_MIN, min(LEX_WORDS_PER_WAVE, cdiv(M, LEX_WAVES)));
