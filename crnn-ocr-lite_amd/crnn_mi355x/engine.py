@@ -452,3 +452,29 @@ def beam_decode(y, beam_width=10, merge_repeated=True, input_length=None):
     check(lib.crnn_ctc_beam_decode(_ptr(y), _ptr(il), _ptr(out), _ptr(ln), _ptr(sc), B, T, C, int(beam_width), int(bool(merge_repeated)),
                                    _stream()), "beam_decode")
     return out, ln, sc
+
+
+def beam_decode_lm(y, table=None, order=1, beam_width=10, top_paths=1, merge_repeated=False, input_length=None):
+    """The beam search with a character language model and N-best output (csrc/beam_lm.hip).  y (B,T,C) softmax (device tensor or ndarray);
+    table: float32 (C ** (order - 1), C) device tensor of FINITE weights (lm.CharLM.table) or None for the default scorer.
+    -> (labels (B,k,T) int32 padded -1, lengths (B,k), scores (B,k)) device tensors, k = top_paths, best first."""
+    lib = native.lib()
+    if not torch.is_tensor(y):
+        y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).cuda()
+    y = y.contiguous().float()
+    B, T, C = y.shape
+    if table is not None:
+        rows = lib.crnn_ctc_lm_rows(C, int(order))
+        if rows == 0 or table.dtype != torch.float32 or tuple(table.shape) != (rows, C) or table.device != y.device:
+            raise ValueError("beam_decode_lm: table must be a float32 (%d, %d) tensor on %s" % (rows, C, y.device))
+        table = table.contiguous()
+    out = torch.empty((B, top_paths, T), dtype=torch.int32, device=y.device)
+    ln = torch.empty((B, top_paths), dtype=torch.int32, device=y.device)
+    sc = torch.empty((B, top_paths), dtype=torch.float32, device=y.device)
+    il = None
+    if input_length is not None:
+        il = torch.as_tensor(np.asarray(input_length).reshape(-1).astype(np.int32)).to(y.device)
+    with torch.cuda.device(y.device):
+        check(lib.crnn_ctc_beam_decode_lm(_ptr(y), _ptr(il), _ptr(table), int(order), _ptr(out), _ptr(ln), _ptr(sc), B, T, C, int(beam_width),
+                                          int(top_paths), int(bool(merge_repeated)), _stream()), "beam_decode_lm")
+    return out, ln, sc

@@ -4,7 +4,9 @@ HIP beam-search decode (beam_width=10, top_paths=1, merge_repeated as TF 1.8), o
 and prediction.csv.  --device_score (with --validate) keeps decoding and scoring on the GPU: same report, same prediction.csv.
 --lexicon FILE decodes to the most probable word of a list (crnn_mi355x.lexicon) instead of the beam search.
 --align (with --result_path) aligns every prediction to its own softmax map (crnn_mi355x.align) and writes alignment.csv: per character its frames
-on the network's time axis and its log-probability."""
+on the network's time axis and its log-probability.
+--lm FILE decodes with a character language model in the beam search (crnn_mi355x.lm): FILE is a saved CharLM (.npz) or a word list to count one from.
+--nbest K (with --result_path) also writes nbest.csv: per image the K best paths of the beam with their scores."""
 import argparse
 import os
 import pickle
@@ -42,6 +44,13 @@ def build_parser():
                         help='a word list, one word per line: decode to the word of the list with the highest CTC probability instead of the beam search')
     parser.add_argument('--align', action='store_true',
                         help='with --result_path: also write alignment.csv -- the best CTC path of every prediction through its own softmax map, per character its frames and log-probability')
+    parser.add_argument('--lm', type=str, default=None,
+                        help='beam search with a character language model: a CharLM saved as .npz, or a word list (one word per line, optional tab-separated count) to count one from')
+    parser.add_argument('--lm_order', type=int, default=3, help='n-gram order of a model counted from a word list')
+    parser.add_argument('--lm_weight', type=float, default=0.5, help='alpha: weight of the language model\'s log-probabilities (a placeholder default: tune it)')
+    parser.add_argument('--lm_bonus', type=float, default=0.0, help='beta: bonus per character (a placeholder default: tune it)')
+    parser.add_argument('--nbest', type=int, default=None,
+                        help='with --result_path: also write nbest.csv -- file, rank, text and score of the K best paths of the beam search')
     return parser
 
 
@@ -54,6 +63,16 @@ def parse_args(argv=None):
         parser.error("--align writes alignment.csv next to prediction.csv: it needs --result_path")
     if args.align and args.device_score:
         parser.error("--align reads the softmax maps, which --device_score never materialises: use one or the other")
+    if args.lm is not None and args.lexicon is not None:
+        parser.error("--lm and --lexicon are two decoders: use one or the other")
+    if args.nbest is not None and args.result_path is None:
+        parser.error("--nbest writes nbest.csv next to prediction.csv: it needs --result_path")
+    if args.nbest is not None and args.lexicon is not None:
+        parser.error("--nbest lists paths of the beam search: it does not go with --lexicon")
+    if args.nbest is not None and args.device_score:
+        parser.error("--nbest reads the softmax maps, which --device_score never materialises: use one or the other")
+    if args.nbest is not None and not 1 <= args.nbest <= 64:
+        parser.error("--nbest must be 1..64")
     return args
 
 
@@ -75,6 +94,18 @@ def main(argv=None):
             lexicon = U.Lexicon([line.rstrip("\r\n") for line in open(args.lexicon)], inverse_classes)
         print(" [INFO] Lexicon: %d words, %d rejected (a character outside the alphabet, or longer than 31) " % (len(lexicon), len(lexicon.rejected)))
         decoder = U.LexiconDecoder(lexicon, top_paths=1)
+    if args.lm is not None or args.nbest is not None:
+        lm = None
+        if args.lm is not None and args.lm.endswith(".npz"):
+            lm = U.CharLM.load(args.lm)
+        elif args.lm is not None:
+            from crnn_mi355x.lm import read_word_list
+            words, counts = read_word_list(args.lm)
+            lm = U.CharLM.from_words(words, inverse_classes, order=args.lm_order, counts=counts)
+            print(" [INFO] Language model: order %d from %d words, %d rejected (a character outside the alphabet) " % (lm.order, len(words), len(lm.rejected)))
+        # without --lm this is the beam search above (merge_repeated as TF) with its other paths kept
+        decoder = U.LMDecoder(lm, alpha=args.lm_weight, beta=args.lm_bonus, beam_width=max(10, args.nbest or 1), top_paths=args.nbest or 1,
+                              merge_repeated=lm is None, inverse_classes=inverse_classes)
     img_size = (args.imgh, args.imgW, 1)
 
     def walk():
@@ -129,6 +160,10 @@ def main(argv=None):
         pd.DataFrame({"fname": fnames, "prediction": predicted_text}).to_csv(out_name)
         print(" [INFO] Prediction example: \n", predicted_text[:10])
         print(" [INFO] Result store in: ", out_name)
+        if args.nbest is not None:
+            nbest = decoder.decode_topk(predicted[:length])
+            pd.DataFrame([{"fname": f, "rank": k, "text": t, "score": v} for f, paths in zip(fnames, nbest) for k, (t, v) in enumerate(paths)],
+                         columns=["fname", "rank", "text", "score"]).to_csv(os.path.join(args.result_path, "nbest.csv"))
         if args.align:
             from crnn_mi355x.align import CTCAligner, write_alignment_csv
             aligned = CTCAligner(inverse_classes).align(predicted[:length], predicted_text)

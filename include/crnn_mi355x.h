@@ -196,6 +196,24 @@ int crnn_ctc_greedy_decode(const float* y, const int* input_len, int* out, int* 
  * best beam (sum of max-shifted log-probs, as TF r1.8 accumulates it).  State lives in LDS: no workspace. */
 int crnn_ctc_beam_decode(const float* y, const int* input_len, int* out, int* out_len, float* scores, int B, int T,
                          int C, int beam_width, int merge_repeated, crnn_stream_t stream);
+/* The same beam search with a character language model (shallow fusion) and N-best output (csrc/beam_lm.hip).  V = C - 1 labels, blank = C - 1.
+ * lm [rows][C] fp32, rows = crnn_ctc_lm_rows(C, order) = C^(order - 1), or NULL (= TF's default scorer): row = a context, the last order - 1
+ * labels as a base-C number in which symbol C - 1 means "before the word starts"; columns 0..V-1 = the weight of appending that label, column V
+ * (the blank's slot) = the weight of ending the word there.  Every prefix node carries ctx (root: rows - 1; child: (parent.ctx * C + label) mod
+ * rows) and w = lm[parent.ctx][label], both fixed for its life.  w enters where TF's BeamScorer hooks sit: a re-scored entry takes
+ * newp.label = lse(newp.label, previous + w), a new child newp.label = inp[label] + (previous + w) (previous = the parent's oldp.blank if the
+ * labels repeat, else its oldp.total; each + one rounded fp32 addition in the order written); candidate tests and evictions see the weighted
+ * totals.  After the last frame every leaf's total gets lm[ctx][V] added; the top_paths best leaves by that sum (ties: the better rank before the
+ * addition) are written in descending order: out [B][top_paths][T] int32 padded with -1 (merge_repeated applied to each path's own labels),
+ * out_len [B][top_paths], scores [B][top_paths] = the sum.  Paths beyond the number of leaves: out_len 0, score -inf, a row of -1.
+ * lm == NULL, top_paths == 1 equals crnn_ctc_beam_decode bit for bit.  The table must be finite; it is not checked.
+ * -3: C outside 2..128, beam_width outside 1..64, top_paths outside 1..beam_width, order < 1, rows * C * 4 > CRNN_LM_TABLE_MAX_BYTES, or LDS
+ * (4 * (1 + T * beam_width) + 1344, plus beam_width * C * 4 of row cache with a table) above 64 KiB.  -2: a null y / out / out_len / scores or a
+ * negative size.  B == 0 launches nothing.  No workspace. */
+#define CRNN_LM_TABLE_MAX_BYTES (16u << 20) /* dense tables: order 3 at 128 classes is 8.4 MB, order 4 at 38 classes 8.3 MB */
+size_t crnn_ctc_lm_rows(int C, int order); /* C^(order - 1) context rows; 0 if unsupported (C, order, or the table above the cap) */
+int crnn_ctc_beam_decode_lm(const float* y, const int* input_len, const float* lm, int order, int* out, int* out_len, float* scores,
+                            int B, int T, int C, int beam_width, int top_paths, int merge_repeated, crnn_stream_t stream);
 /* Edit distance of decoded rows against the truth (utils.py:262-298 after labels_to_text, utils.py:314-321), one launch for the batch.
  * For each row i < n: a = pred[i, :] ([n, pred_cols] int32) and b = truth[i, :] ([n, truth_cols] int32), each with every element equal to
  * skip0 or skip1 removed WHEREVER it stands (labels_to_text drops blank and -1 anywhere, not only at the end); dist[i] = Levenshtein(a, b)
