@@ -4,7 +4,7 @@ decoded by one launch of the HIP wavefront beam kernel (csrc/beam.hip), with TF-
 merge_repeated=True ('cellist' decodes to 'celist', as in the reference's own screenshots)."""
 import numpy as np
 
-from .labels import CHUNK, device_map
+from .labels import decode_chunks
 
 
 def labels_to_text(labels, inverse_classes=None):
@@ -30,27 +30,16 @@ class DecodeCTCPred:
         is; an ndarray is uploaded chunk by chunk.  device=True: -> (labels (N,T), lengths (N,)) int32 DEVICE tensors, nothing copied back
         (what metrics.device_edit_distances reads)."""
         import torch
-        from . import engine, native
+        from . import engine
         if self.beam_width < self.top_paths:
             self.beam_width = self.top_paths
-        out, lens = [], []
-        for lo in range(0, len(result), CHUNK):
-            chunk = device_map(result[lo:lo + CHUNK])
-            if self.greedy:
-                B, T, C = chunk.shape
-                lab = torch.empty((B, T), dtype=torch.int32, device=chunk.device)
-                ln = torch.empty(B, dtype=torch.int32, device=chunk.device)
-                native.check(native.lib().crnn_ctc_greedy_decode(engine._ptr(chunk), None, engine._ptr(lab), engine._ptr(ln), B, T, C,
-                                                                 engine._stream()), "greedy")
-            else:
-                lab, ln, _ = engine.beam_decode(chunk, self.beam_width, self.merge_repeated)
-            out.append(lab if device else lab.cpu().numpy())
-            lens.append(ln)
-        if device:
-            if not out:
+        run = engine.greedy_decode if self.greedy else (lambda chunk: engine.beam_decode(chunk, self.beam_width, self.merge_repeated)[:2])
+        done = decode_chunks(result, run if device else (lambda chunk: (run(chunk)[0].cpu(),)))      # host labels come back chunk by chunk
+        if done is None:
+            if device:
                 return torch.zeros((0, 0), dtype=torch.int32, device="cuda"), torch.zeros(0, dtype=torch.int32, device="cuda")
-            return (out[0], lens[0]) if len(out) == 1 else (torch.cat(out, 0), torch.cat(lens, 0))
-        return np.concatenate(out, 0) if out else np.zeros((0, 0), np.int32)
+            return np.zeros((0, 0), np.int32)
+        return done if device else done[0].numpy()
 
     def decode(self, result):
         return [self.labels_to_text(row) for row in self.decode_labels(result)]

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import native
+from .labels import device_map
 from .native import check, crnn_config
 
 
@@ -425,56 +426,58 @@ class Engine:
 
     # ---- decoding -----------------------------------------------------------------------------------------
     def greedy_decode(self, y=None, input_length=None):
-        y = self.y_pred if y is None else y
-        B, T, C = y.shape
-        out = torch.empty((B, T), dtype=torch.int32, device=self.device); ln = torch.empty(B, dtype=torch.int32, device=self.device)
-        il = self._as_i32(input_length) if input_length is not None else None
-        check(self.lib.crnn_ctc_greedy_decode(_ptr(y), _ptr(il), _ptr(out), _ptr(ln), B, T, C, _stream()), "greedy")
-        return out, ln
+        return greedy_decode(self.y_pred if y is None else y, input_length)
 
     def beam_decode(self, y=None, beam_width=10, merge_repeated=True, input_length=None):
         y = self.y_pred if y is None else y
         return beam_decode(y, beam_width, merge_repeated, input_length)
 
 
-def beam_decode(y, beam_width=10, merge_repeated=True, input_length=None):
-    """y (B,T,C) softmax (device tensor or ndarray) -> (labels (B,T) int32 padded -1, lengths, scores)."""
-    lib = native.lib()
-    if not torch.is_tensor(y):
-        y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).cuda()
-    y = y.contiguous().float()
+def _decode(what, call, y, input_length, k=(), scores=True):
+    """What the decoders' launches share.  y (B,T,C) softmax: an ndarray is uploaded, a tensor made contiguous float32 where it is; input_length
+    (None: every frame) goes to y's device as int32; labels (B,*k,T), lengths (B,*k) and, for a beam search, scores (B,*k) are allocated there,
+    and call(y, input_length, [outputs], B, T, C, stream) -- pointers, as the library takes them -- runs on that device's current stream.
+    -> (labels, lengths[, scores])"""
+    y = device_map(y)
     B, T, C = y.shape
-    out = torch.empty((B, T), dtype=torch.int32, device=y.device); ln = torch.empty(B, dtype=torch.int32, device=y.device)
-    sc = torch.empty(B, dtype=torch.float32, device=y.device)
     il = None
     if input_length is not None:
-        il = torch.as_tensor(np.asarray(input_length).reshape(-1).astype(np.int32)).to(y.device)
-    check(lib.crnn_ctc_beam_decode(_ptr(y), _ptr(il), _ptr(out), _ptr(ln), _ptr(sc), B, T, C, int(beam_width), int(bool(merge_repeated)),
-                                   _stream()), "beam_decode")
-    return out, ln, sc
+        if not torch.is_tensor(input_length):
+            input_length = torch.from_numpy(np.ascontiguousarray(np.asarray(input_length).reshape(-1), dtype=np.int32))
+        il = input_length.to(y.device, dtype=torch.int32).contiguous()
+    res = [torch.empty((B,) + k + (T,), dtype=torch.int32, device=y.device), torch.empty((B,) + k, dtype=torch.int32, device=y.device)]
+    if scores:
+        res.append(torch.empty((B,) + k, dtype=torch.float32, device=y.device))
+    with torch.cuda.device(y.device):
+        check(call(_ptr(y), _ptr(il), [_ptr(t) for t in res], B, T, C, _stream()), what)
+    return tuple(res)
+
+
+def greedy_decode(y, input_length=None):
+    """y (B,T,C) softmax (device tensor or ndarray) -> (labels (B,T) int32 padded -1, lengths)."""
+    return _decode("greedy", lambda y, il, out, B, T, C, st: native.lib().crnn_ctc_greedy_decode(y, il, *out, B, T, C, st), y, input_length,
+                   scores=False)
+
+
+def beam_decode(y, beam_width=10, merge_repeated=True, input_length=None):
+    """y (B,T,C) softmax (device tensor or ndarray) -> (labels (B,T) int32 padded -1, lengths, scores)."""
+    bw, merge = int(beam_width), int(bool(merge_repeated))
+    return _decode("beam_decode", lambda y, il, out, B, T, C, st: native.lib().crnn_ctc_beam_decode(y, il, *out, B, T, C, bw, merge, st), y,
+                   input_length)
 
 
 def beam_decode_lm(y, table=None, order=1, beam_width=10, top_paths=1, merge_repeated=False, input_length=None):
-    """The beam search with a character language model and N-best output (csrc/beam_lm.hip).  y (B,T,C) softmax (device tensor or ndarray);
+    """The beam search with a character language model and N-best output (csrc/beam.hip, LM = true).  y (B,T,C) softmax (device tensor or ndarray);
     table: float32 (C ** (order - 1), C) device tensor of FINITE weights (lm.CharLM.table) or None for the default scorer.
     -> (labels (B,k,T) int32 padded -1, lengths (B,k), scores (B,k)) device tensors, k = top_paths, best first."""
     lib = native.lib()
-    if not torch.is_tensor(y):
-        y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).cuda()
-    y = y.contiguous().float()
-    B, T, C = y.shape
+    y = device_map(y)                                         # the table is checked against the map where the map will be decoded
     if table is not None:
+        C = y.shape[2]
         rows = lib.crnn_ctc_lm_rows(C, int(order))
         if rows == 0 or table.dtype != torch.float32 or tuple(table.shape) != (rows, C) or table.device != y.device:
             raise ValueError("beam_decode_lm: table must be a float32 (%d, %d) tensor on %s" % (rows, C, y.device))
         table = table.contiguous()
-    out = torch.empty((B, top_paths, T), dtype=torch.int32, device=y.device)
-    ln = torch.empty((B, top_paths), dtype=torch.int32, device=y.device)
-    sc = torch.empty((B, top_paths), dtype=torch.float32, device=y.device)
-    il = None
-    if input_length is not None:
-        il = torch.as_tensor(np.asarray(input_length).reshape(-1).astype(np.int32)).to(y.device)
-    with torch.cuda.device(y.device):
-        check(lib.crnn_ctc_beam_decode_lm(_ptr(y), _ptr(il), _ptr(table), int(order), _ptr(out), _ptr(ln), _ptr(sc), B, T, C, int(beam_width),
-                                          int(top_paths), int(bool(merge_repeated)), _stream()), "beam_decode_lm")
-    return out, ln, sc
+    tail = (int(beam_width), int(top_paths), int(bool(merge_repeated)))
+    return _decode("beam_decode_lm", lambda y, il, out, B, T, C, st: lib.crnn_ctc_beam_decode_lm(y, il, _ptr(table), int(order), *out, B, T, C, *tail, st),
+                   y, input_length, (top_paths,))

@@ -42,3 +42,13 @@ def device_map(result, device=None):
     import torch
     y = result if torch.is_tensor(result) else torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32))
     return (y if y.is_cuda else y.to(device or "cuda")).contiguous().float()
+
+
+def decode_chunks(result, launch):
+    """The decoders' loop over a map of any length: launch(chunk) -> a tuple of device tensors, for every CHUNK rows of `result` put on the device
+    by device_map.  -> that tuple for the whole map (concatenated when there is more than one chunk), or None for an empty `result`."""
+    import torch
+    parts = [launch(device_map(result[lo:lo + CHUNK])) for lo in range(0, len(result), CHUNK)]
+    if not parts:
+        return None
+    return parts[0] if len(parts) == 1 else tuple(torch.cat(p, 0) for p in zip(*parts))

@@ -1,5 +1,5 @@
 """Open-vocabulary decoding with a character language model (beyond the reference): the TF beam search of DecodeCTCPred with TF's BeamScorer hooks
-filled in by a dense character n-gram table (shallow fusion), and N-best output -- csrc/beam_lm.hip, one launch per batch, nothing but labels,
+filled in by a dense character n-gram table (shallow fusion), and N-best output -- csrc/beam.hip, one launch per batch, nothing but labels,
 lengths and scores comes back.  LexiconDecoder answers "which word of this list"; LMDecoder reads any string and lets the statistics of a word
 list (or of any text) steer the beam.
 
@@ -8,7 +8,7 @@ column c < C - 1 = log P(c | context), column C - 1 = log P(end of word | contex
 order 3 at 128 classes 8.4 MB; the library's cap is 16 MiB."""
 import numpy as np
 
-from .labels import CHUNK, Alphabet, class_items, device_map
+from .labels import Alphabet, class_items, decode_chunks
 
 TABLE_MAX_BYTES = 16 << 20   # CRNN_LM_TABLE_MAX_BYTES
 
@@ -143,18 +143,17 @@ class LMDecoder:
         """-> (labels (n, k, T), lengths (n, k), scores (n, k)) device tensors"""
         import torch
         from . import engine
-        parts = []
-        for lo in range(0, len(result), CHUNK):
-            chunk = device_map(result[lo:lo + CHUNK])
+
+        def launch(chunk):
             if self.lm is not None and chunk.shape[2] != self.lm.C:
                 raise ValueError("LMDecoder: the map has %d classes, the language model %d" % (chunk.shape[2], self.lm.C))
             table = self.lm.table(self.alpha, self.beta, chunk.device) if self.lm is not None else None
-            parts.append(engine.beam_decode_lm(chunk, table, self.lm.order if self.lm is not None else 1, self.beam_width, top_paths,
-                                               self.merge_repeated))
-        if not parts:
+            return engine.beam_decode_lm(chunk, table, self.lm.order if self.lm is not None else 1, self.beam_width, top_paths, self.merge_repeated)
+        done = decode_chunks(result, launch)
+        if done is None:
             z = lambda *s, dt=torch.int32: torch.zeros(s, dtype=dt, device="cuda")
             return z(0, top_paths, 0), z(0, top_paths), z(0, top_paths, dt=torch.float32)
-        return parts[0] if len(parts) == 1 else tuple(torch.cat(p, 0) for p in zip(*parts))
+        return done
 
     def decode_labels(self, result, device=False):
         """DecodeCTCPred.decode_labels' contract, the best path: (n, T, C) softmax -> (n, T) int32 labels padded with -1.  device=True: ->

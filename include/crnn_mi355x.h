@@ -193,10 +193,12 @@ int crnn_convert_f32_to_bf16(const float* x, void* y, long n, crnn_stream_t stre
 int crnn_ctc_greedy_decode(const float* y, const int* input_len, int* out, int* out_len, int B, int T, int C,
                            crnn_stream_t stream);
 /* tf.nn.ctc_beam_search_decoder(beam_width <= 64, top_paths=1, merge_repeated), C <= 128 classes; scores [B] = log-score of the
- * best beam (sum of max-shifted log-probs, as TF r1.8 accumulates it).  State lives in LDS: no workspace. */
+ * best beam (sum of max-shifted log-probs, as TF r1.8 accumulates it).  State lives in LDS: no workspace.  It is crnn_ctc_beam_decode_lm below
+ * with lm = NULL, order = 1, top_paths = 1, and returns what that returns: -3 where 4 * (1 + T * beam_width) + 1088 bytes of LDS exceed 64 KiB
+ * (T = 251 at width 64 still fits), -2 for a null y / out / out_len / scores or a negative B / T, 0 without a launch for B == 0. */
 int crnn_ctc_beam_decode(const float* y, const int* input_len, int* out, int* out_len, float* scores, int B, int T,
                          int C, int beam_width, int merge_repeated, crnn_stream_t stream);
-/* The same beam search with a character language model (shallow fusion) and N-best output (csrc/beam_lm.hip).  V = C - 1 labels, blank = C - 1.
+/* The same beam search with a character language model (shallow fusion) and N-best output (one kernel, csrc/beam.hip).  V = C - 1 labels, blank = C - 1.
  * lm [rows][C] fp32, rows = crnn_ctc_lm_rows(C, order) = C^(order - 1), or NULL (= TF's default scorer): row = a context, the last order - 1
  * labels as a base-C number in which symbol C - 1 means "before the word starts"; columns 0..V-1 = the weight of appending that label, column V
  * (the blank's slot) = the weight of ending the word there.  Every prefix node carries ctx (root: rows - 1; child: (parent.ctx * C + label) mod
@@ -206,9 +208,9 @@ int crnn_ctc_beam_decode(const float* y, const int* input_len, int* out, int* ou
  * totals.  After the last frame every leaf's total gets lm[ctx][V] added; the top_paths best leaves by that sum (ties: the better rank before the
  * addition) are written in descending order: out [B][top_paths][T] int32 padded with -1 (merge_repeated applied to each path's own labels),
  * out_len [B][top_paths], scores [B][top_paths] = the sum.  Paths beyond the number of leaves: out_len 0, score -inf, a row of -1.
- * lm == NULL, top_paths == 1 equals crnn_ctc_beam_decode bit for bit.  The table must be finite; it is not checked.
+ * lm == NULL, top_paths == 1 is crnn_ctc_beam_decode: the same launch.  The table must be finite; it is not checked.
  * -3: C outside 2..128, beam_width outside 1..64, top_paths outside 1..beam_width, order < 1, rows * C * 4 > CRNN_LM_TABLE_MAX_BYTES, or LDS
- * (4 * (1 + T * beam_width) + 1344, plus beam_width * C * 4 of row cache with a table) above 64 KiB.  -2: a null y / out / out_len / scores or a
+ * (4 * (1 + T * beam_width) + 1088, plus 256 + beam_width * C * 4 of row cache with a table) above 64 KiB.  -2: a null y / out / out_len / scores or a
  * negative size.  B == 0 launches nothing.  No workspace. */
 #define CRNN_LM_TABLE_MAX_BYTES (16u << 20) /* dense tables: order 3 at 128 classes is 8.4 MB, order 4 at 38 classes 8.3 MB */
 size_t crnn_ctc_lm_rows(int C, int order); /* C^(order - 1) context rows; 0 if unsupported (C, order, or the table above the cap) */

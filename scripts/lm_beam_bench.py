@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Beam search with a character language model and N-best output at batch 1024, T = 52 (the 100 x 32 configuration), 38 classes, width 10:
-crnn_ctc_beam_decode_lm (csrc/beam_lm.hip) on the posteriors of the benchmark model (random weights, as lexicon_bench.make_engine builds it), in the
-same process and on the same maps as the yardstick, the plain crnn_ctc_beam_decode launch: without a table, with dense tables of orders 1, 2 and 3
+crnn_ctc_beam_decode_lm (csrc/beam.hip) on the posteriors of the benchmark model (random weights, as lexicon_bench.make_engine builds it), in the
+same process and on the same maps as the yardstick, the plain crnn_ctc_beam_decode launch (the same kernel without a table, top_paths 1): without a table, with dense tables of orders 1, 2 and 3
 (weights 0.8 * log(dirichlet(0.3)) + 0.5, what the tests use), each with top_paths 1 and 5.  HIP events over windows of back-to-back launches after
 warm-up; the launches alternate, two runs each.  Prints, and with --out writes, us per launch, the ratio to the yardstick and the kernels' resource
 usage as the compiler reports it.
@@ -21,13 +21,13 @@ from lexicon_bench import BATCH, T, C, BEAM, make_engine, _timed  # noqa: E402
 
 def resources():
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage",
-           "-c", os.path.join(ROOT, "crnn-ocr-lite_amd", "csrc", "beam_lm.hip"), "-o", os.devnull]
+           "-c", os.path.join(ROOT, "crnn-ocr-lite_amd", "csrc", "beam.hip"), "-o", os.devnull]
     err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     out = []
     for blk in err.split("Function Name: ")[1:]:
         pick = lambda key: int(re.search(r"%s: (\d+)" % re.escape(key), blk).group(1))
         m = re.search(r"ILi(\d)ELb(\d)E", blk.split()[0])
-        out.append("ctc_beam_lm_kernel<CPL = %s, LM = %s> %d VGPRs / %d SGPRs / scratch %d / VGPR spills %d / SGPR spills %d / occupancy %d"
+        out.append("ctc_beam_kernel<CPL = %s, LM = %s> %d VGPRs / %d SGPRs / scratch %d / VGPR spills %d / SGPR spills %d / occupancy %d"
                    % (m.group(1), m.group(2), pick("VGPRs"), pick("TotalSGPRs"), pick("ScratchSize [bytes/lane]"), pick("VGPRs Spill"), pick("SGPRs Spill"),
                       pick("Occupancy [waves/SIMD]")))
     return out

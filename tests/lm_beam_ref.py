@@ -1,4 +1,4 @@
-"""Reference (TEST INFRASTRUCTURE) of the beam search with a character language model and N-best output (csrc/beam_lm.hip): oracle.ctc._beam_one
+"""Reference (TEST INFRASTRUCTURE) of the beam search with a character language model and N-best output (csrc/beam.hip, LM = true): oracle.ctc._beam_one
 -- TF r1.8's algorithm -- with a scorer.  V = C - 1 labels, blank = C - 1; table [rows][C], rows = C ** (order - 1), column V = end-of-word weight.
   * every prefix node carries ctx (root: rows - 1; child: (parent.ctx * C + label) % rows) and w = table[parent.ctx][label];
   * a re-scored entry takes nl = lse(nl, previous + w), a new child nl = inp[label] + (previous + w); -inf stays -inf; every + rounds to `dtype`;
@@ -170,6 +170,26 @@ def plant_double(y, b, label):
 def lm_table(rs, C, order, alpha=0.8, beta=0.5):
     p = rs.dirichlet([0.3] * C, size=lm_rows(C, order))
     return (alpha * np.log(p + 1e-6) + beta).astype(np.float32)
+
+
+# ---- the plain decoder's cases: recorded by tests/golden/make_beam_bits.py, replayed by tests/test_gpu_lm.py -------------------------------------
+PLAIN_B, PLAIN_T = 24, 52
+PLAIN_CASES = [(C, bw, merge) for C in (38, 97) for bw in (1, 10, 64) for merge in (0, 1)]      # one and two classes per lane; the widths' three DPP paths
+# the capacity edge: 4 * (1 + 251 * 64) + 64 * 16 + 64 = 65348 of the 65536 bytes of LDS, a node table far past its register copy (the LDS walk)
+EDGE_C, EDGE_B, EDGE_T, EDGE_BW, EDGE_MERGE, EDGE_SEED = 38, 2, 251, 64, 1, 0
+
+
+def plain_case_inputs(C, bw):
+    """-> (y (PLAIN_B, PLAIN_T, C) float32 softmax, input lengths (PLAIN_B,))"""
+    y = plant_double(posteriors(np.random.RandomState(C + bw), PLAIN_B, PLAIN_T, C), 5, 3)
+    il = np.full(PLAIN_B, PLAIN_T); il[:4] = [1, 2, 17, 51]
+    return y, il
+
+
+def edge_inputs():
+    """-> y (EDGE_B, EDGE_T, EDGE_C); every frame is decoded.  Seed 0: the fp32 and the fp64 run of the reference agree on both rows (no near-tie;
+    tests/test_lm_cpu.py)"""
+    return posteriors(np.random.RandomState(EDGE_SEED), EDGE_B, EDGE_T, EDGE_C)
 
 
 # ---- the cases shared by tests/test_lm_cpu.py (numerical stability) and tests/test_gpu_lm.py (the kernel against the fp32 reference) ------------

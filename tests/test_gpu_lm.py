@@ -1,9 +1,13 @@
-"""-m gpu tests of the beam search with a character language model and N-best output (csrc/beam_lm.hip, crnn_mi355x/lm.py): without a table the
-kernel is crnn_ctc_beam_decode bit for bit; with one it follows the fp32 reference of tests/lm_beam_ref.py (pinned on the CPU by
+"""-m gpu tests of the beam search with a character language model and N-best output (csrc/beam.hip, crnn_mi355x/lm.py): without a table both
+entry points give the bits recorded from the plain decoder's former kernel (tests/golden/beam_bits.npz, written by tests/golden/make_beam_bits.py;
+the two entry points run one kernel, so comparing them with each other alone would see no mistake in it), also at the plain decoder's capacity
+edge, where the labels are the oracle's too; with one it follows the fp32 reference of tests/lm_beam_ref.py (pinned on the CPU by
 tests/test_lm_cpu.py, which also names the near-tie rows -- the only rows not compared) on alphabets on both sides of 64 classes and on a
 context that wraps; a language model changes what is read; N-best order and padding; refusals; determinism; the Python surface and
 predict.py --lm --nbest."""
 import csv
+import functools
+import importlib.util
 import os
 import subprocess
 import sys
@@ -35,16 +39,38 @@ def _decode(y, il, table, order, bw, top, merge):
 
 
 # ---- 1. the default scorer ----------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _recorded():
+    """-> (tests/golden/make_beam_bits.py as a module, {name: int32 ndarray} of tests/golden/beam_bits.npz, the `hipcc --version` it was recorded with)"""
+    spec = importlib.util.spec_from_file_location("make_beam_bits", os.path.join(ROOT, "tests", "golden", "make_beam_bits.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return (gen,) + gen.load()
+
+
+def _assert_recorded(tag, entry, lab, lens, score_bits):
+    """labels, lengths and score bits of one entry point equal the fixture's.  The fixture belongs to the compiler it was recorded with: another one
+    may round logf / expf differently, and then it is to be recorded again from a commit known to be good -- not skipped."""
+    gen, gold, recorded_with = _recorded()
+    differ = [name for name, a in zip(gen.names(tag), (lab, lens, score_bits)) if a.dtype != np.int32 or not np.array_equal(a, gold[name])]
+    here = gen.hipcc_version()
+    assert not differ, "%s differs from tests/golden/beam_bits.npz in: %s\n%s\nfixture recorded with:\n%s\nthis machine:\n%s" % (
+        entry, "; ".join(differ), "`hipcc --version` differs from the fixture's" if here != recorded_with else "same `hipcc --version` as the fixture",
+        recorded_with, here)
+
+
 @pytest.mark.parametrize("merge", [0, 1])
 @pytest.mark.parametrize("bw", [1, 10, 64])
 @pytest.mark.parametrize("C", [38, 97])
 def test_without_a_table_it_is_the_plain_beam_search_bit_for_bit(C, bw, merge):
-    B, T = 24, 52
-    y = R.plant_double(R.posteriors(np.random.RandomState(C + bw), B, T, C), 5, 3)
-    il = np.full(B, T); il[:4] = [1, 2, 17, 51]
+    y, il = R.plain_case_inputs(C, bw)
+    B, T = R.PLAIN_B, R.PLAIN_T
     out = zeros(B, T, dtype=torch.int32); ln = zeros(B, dtype=torch.int32); sc = zeros(B)
     ok(L().crnn_ctc_beam_decode(P(dev(y)), P(dev(il, np.int32)), P(out), P(ln), P(sc), B, T, C, bw, merge, S()))
     lab, lens, scores = _decode(y, il, None, 1, bw, 1, merge)
+    tag = _recorded()[0].case_tag(C, bw, merge)
+    _assert_recorded(tag, "crnn_ctc_beam_decode", host(out), host(ln), host(sc).view(np.int32))
+    _assert_recorded(tag, "crnn_ctc_beam_decode_lm", lab[:, 0], lens[:, 0], np.ascontiguousarray(scores[:, 0]).view(np.int32))
     assert np.array_equal(lab[:, 0], host(out)) and np.array_equal(lens[:, 0], host(ln))
     assert np.array_equal(scores[:, 0].view(np.uint32), host(sc).view(np.uint32))
     assert (lens[4:, 0] > 5).all()
@@ -52,6 +78,52 @@ def test_without_a_table_it_is_the_plain_beam_search_bit_for_bit(C, bw, merge):
     zl, zn, zs = _decode(y, il, np.zeros((1, C), np.float32), 1, bw, 1, merge)
     assert np.array_equal(zl, lab) and np.array_equal(zn, lens)
     assert np.allclose(zs, scores, rtol=1e-4, atol=1e-3)
+
+
+def test_the_plain_decoder_keeps_its_capacity_edge():
+    """T = 251 at width 64 takes 4 * (1 + 251 * 64) + 64 * 16 + 64 = 65348 of the 65536 bytes of LDS: the plain entry point still accepts it (the
+    node table is far past its register copy: the LDS walk), T = 252 is refused by both, and a table's row cache no longer fits at T = 251."""
+    from oracle import ctc
+    C, B, T, bw = R.EDGE_C, R.EDGE_B, R.EDGE_T, R.EDGE_BW
+    assert (C, B, T, bw, R.EDGE_MERGE) == (38, 2, 251, 64, 1)
+    y = R.edge_inputs()
+    out = torch.full((B, T), 1000, dtype=torch.int32, device="cuda"); ln = torch.full((B,), -5, dtype=torch.int32, device="cuda"); sc = zeros(B)
+    ok(L().crnn_ctc_beam_decode(P(dev(y)), None, P(out), P(ln), P(sc), B, T, C, bw, 1, S()))
+    out, ln, sc_bits = host(out), host(ln), host(sc).view(np.int32)
+    want, want_len, _ = ctc.ctc_beam_decode(y, bw, True)      # neither row is a near-tie: tests/test_lm_cpu.py
+    assert np.array_equal(out, want) and np.array_equal(ln, want_len) and (ln > 100).all()
+    _assert_recorded(_recorded()[0].EDGE_TAG, "crnn_ctc_beam_decode", out, ln, sc_bits)
+    # without a table crnn_ctc_beam_decode_lm has the same bound and gives the same bits
+    lab, lens, scores = _decode(y, None, None, 1, bw, 1, 1)
+    _assert_recorded(_recorded()[0].EDGE_TAG, "crnn_ctc_beam_decode_lm", lab[:, 0], lens[:, 0], np.ascontiguousarray(scores[:, 0]).view(np.int32))
+    assert np.array_equal(lab[:, 0], out) and np.array_equal(lens[:, 0], ln) and np.array_equal(scores[:, 0].view(np.int32), sc_bits)
+    # refusals: nothing is written
+    o = torch.full((B, T + 1), 77, dtype=torch.int32, device="cuda"); n = torch.full((B,), 78, dtype=torch.int32, device="cuda")
+    s = torch.full((B,), 7.0, device="cuda")
+    y252, table = zeros(B, T + 1, C), zeros(1, C)
+    assert L().crnn_ctc_beam_decode(P(y252), None, P(o), P(n), P(s), B, T + 1, C, bw, 1, S()) == -3
+    assert L().crnn_ctc_beam_decode_lm(P(y252), None, None, 1, P(o), P(n), P(s), B, T + 1, C, bw, 1, 1, S()) == -3
+    assert L().crnn_ctc_beam_decode_lm(P(dev(y)), None, P(table), 1, P(o), P(n), P(s), B, T, C, bw, 1, 1, S()) == -3
+    torch.cuda.synchronize()
+    assert bool((o == 77).all()) and bool((n == 78).all()) and bool((s == 7.0).all())
+
+
+def test_the_plain_entry_point_checks_its_arguments():
+    B, T, C = 4, 20, 38
+    y = dev(R.posteriors(np.random.RandomState(0), B, T, C))
+    out = torch.full((B, T), 77, dtype=torch.int32, device="cuda"); ln = torch.full((B,), 78, dtype=torch.int32, device="cuda")
+    sc = torch.full((B,), 7.0, device="cuda")
+
+    def call(y_=y, out_=out, ln_=ln, sc_=sc, B_=B, T_=T):
+        return L().crnn_ctc_beam_decode(P(y_), None, P(out_), P(ln_), P(sc_), B_, T_, C, 10, 1, S())
+    assert call(out_=None) == -2 and call(y_=None) == -2 and call(ln_=None) == -2 and call(sc_=None) == -2
+    assert call(B_=-1) == -2 and call(T_=-1) == -2
+    assert call(B_=0) == 0
+    torch.cuda.synchronize()
+    assert bool((out == 77).all()) and bool((ln == 78).all()) and bool((sc == 7.0).all())
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert not bool((out == 77).any()) and not bool((ln == 78).any()) and not bool((sc == 7.0).any())
 
 
 # ---- 2. with a table, against the fp32 reference -----------------------------------------------------------------------------------------------------

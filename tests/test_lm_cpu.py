@@ -84,6 +84,15 @@ def test_gpu_inputs_are_stable_between_fp32_and_fp64(order, C, T, width):
         assert max(len(p[0]) for p in raw) >= 3
 
 
+def test_capacity_edge_input_is_stable_between_fp32_and_fp64():
+    """the T = 251, width 64 map that tests/golden/make_beam_bits.py records and the GPU test holds against oracle.ctc.ctc_beam_decode: neither row is a near-tie"""
+    y = R.edge_inputs()
+    assert y.shape == (2, 251, 38) and R.EDGE_BW == 64
+    raw32 = R.beam_lm_decode(y, R.EDGE_BW, None, 1, 1, False, None, np.float32)[3]
+    raw64 = R.beam_lm_decode(y, R.EDGE_BW, None, 1, 1, False, None, np.float64)[3]
+    assert raw32 == raw64 and min(len(p[0]) for p in raw32) > 100
+
+
 # ---- 4. CharLM -----------------------------------------------------------------------------------------------------------------------------------
 ALPHA = list("abcdefghijklmnopqrstuvwxyz0123456789_")
 
