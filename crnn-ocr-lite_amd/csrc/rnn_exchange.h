@@ -1,6 +1,26 @@
 // Exchange machinery shared by the persistent recurrences (rnn_persist.hip: LSTM, gru_persist.hip: GRU): the sentinel ring in
 // device memory through which the workgroups of a cluster all-gather a step's values, its status words, the workgroup ->
-// (cluster, member) maps and the host-side sizing of a launch.  See the header comment of rnn_persist.hip for the protocol.
+// (cluster, member) maps and the host-side sizing of a launch.  What the kernels build on it: rnn_persist.h.
+//
+// Hand-off protocol (MI355X: per-XCD L2s are not coherent, a CU's L1 is never refreshed by other CUs' stores): the
+// exchange buffer is a ring of kRing = 4 slots per chain, pre-filled with an all-ones sentinel (hipMemsetAsync 0xFF
+// before the launch).  Producers store their slice of exchange e into slot e % 4 with 16-byte write-through (sc1) stores -- or, with
+// the XCD-local map and after the cluster's census has shown that all its members share one XCD (cluster_shares_xcd), plain stores:
+// that XCD's L2 is then the meeting point (LSTM forward 131 -> 98 us, BPTT 198 -> 142 us per layer at B = 256, u = 256, bf16);
+// consumers re-read the tile with 16-byte sc1 loads (L1-bypassing) until no dword equals the sentinel -- the data
+// is its own ready flag (a valid |h| < 1 / a finite gradient never has an all-ones bf16 pair or fp32 pattern, and a NaN
+// produced by arithmetic is 0x7fc0..., not 0xffff...), so there is no flag, no fence and no drain on the critical
+// path.  Slot reuse: once a workgroup has gathered the complete tile of exchange e-1, every member has finished reading
+// e-2 (a member publishes e-1 only after its gather of e-2 returned), so it re-poisons ITS slice of slot (e-2) % 4 =
+// (e+2) % 4 after publishing e, and drains its stores (s_waitcnt vmcnt(0)) before it publishes e+1: whoever
+// later sees its e+1 data -- a precondition for polling slot (e+2) % 4 -- can no longer see the stale e-2 there.
+// (The LSTM has one exchange per step, e = s; the GRU two, gru_persist.hip.)
+// Results do not depend on workgroup placement or dispatch order; a cluster's workgroups have consecutive
+// block ids (or, with the XCD-local map, block ids congruent modulo 8: one XCD, one L2) and the whole grid is sized to be
+// co-resident.  Every spin is bounded: on give-up the chain free-runs (wrong numbers, no hang) and says so twice in the
+// first kStatusBytes of xbuf: the unsigned at byte 0 is a STICKY give-up counter that no launch ever resets (the caller
+// zeroes it once when it allocates xbuf and compares it with the value it saw last -- Engine.check_rnn_status), the
+// unsigned at byte 16 is the per-launch status word (all ones after a clean launch, bit 0 cleared on give-up).
 #pragma once
 #include "common.h"
 
@@ -157,13 +177,12 @@ inline int resident_cap(size_t lds_bytes, int threads, const void* fn) {
 }
 // rows of the batch one launch covers, and the exchange bytes that launch needs
 struct Chunking { int rows_per_launch; size_t xdata_bytes; };
-inline Chunking chunking(int T, int B, int u, int mt, int uw, int es, size_t lds, int per_row, const void* fn) {
-  const int NSW = u / (16 * uw), BT = 16 * mt;
-  int tiles = resident_cap(lds, 256 * uw, fn) / (2 * NSW);
+inline Chunking chunking(int B, int nsw, int threads, int es, size_t lds, int per_row, const void* fn) {
+  int tiles = resident_cap(lds, threads, fn) / (2 * nsw);   // 16-row batch tiles, two directions each, nsw workgroups per cluster
   if (tiles < 1) tiles = 1;
   Chunking c;
-  c.rows_per_launch = tiles * BT;
-  const int rows = (B < c.rows_per_launch) ? cdiv(B, BT) * BT : c.rows_per_launch;
+  c.rows_per_launch = tiles * 16;
+  const int rows = (B < c.rows_per_launch) ? cdiv(B, 16) * 16 : c.rows_per_launch;
   c.xdata_bytes = 2 * (size_t)kRing * rows * per_row * es;
   return c;
 }

@@ -775,17 +775,19 @@ int crnn_pwconv_bnrelu6_fwd_wres(const void* d, const float* in_bnstate, const v
                                  crnn_stream_t stream);
 
 /* Persistent recurrences: ONE launch per Bidirectional(LSTM) layer (utils.py:77-82) instead of T dependent step launches.
- * A cluster of u/16 workgroups runs the chain of one 16- or 32-row batch tile of one direction; each workgroup keeps its
- * 256x64 slice of the recurrent weights in registers (MFMA B fragments) and the cell state / cell-gradient carry in
- * registers for all T steps; per step the cluster all-gathers h_t (forward) / dz_t (backward) through `xbuf` with
- * write-through stores and L1-bypassing polled loads (the data is its own ready flag) and stages it through LDS as the next
- * step's MFMA A operand.  Bit-identical to crnn_lstm_*_ex.  `xbuf`: caller-owned scratch of crnn_lstm_persist_xbuf_bytes()
+ * A cluster of u/32 workgroups runs the chain of one 16-row batch tile of one direction; each workgroup (512 threads, two groups of 16
+ * hidden units) keeps its slices of the recurrent weights in registers (MFMA B fragments; 256x64 per unit group at u = 256) and the
+ * cell state / cell-gradient carry in registers for all T steps; per step the cluster all-gathers h_t (forward) / dz_t (backward)
+ * through `xbuf` with write-through stores and L1-bypassing polled loads (the data is its own ready flag) and stages it through LDS as
+ * the next step's MFMA A operand.  Bit-identical to crnn_lstm_*_ex.  `xbuf`: caller-owned scratch of crnn_lstm_persist_xbuf_bytes()
  * bytes, 16-byte aligned.  Status: the unsigned at byte 16 of xbuf is 0xFFFFFFFF after a clean kernel launch, anything else means a
  * bounded wait gave up (the cluster was not co-resident: results invalid); the unsigned at byte 0 is a STICKY counter of give-ups
  * that no launch resets -- the caller zeroes it once after allocating xbuf and compares it with the last value it saw (the engine
  * does that wherever it synchronises with the host anyway and raises; inside the workspace this is the tensor "rnnx").
- * mt = batch rows per workgroup / 16 (1 | 2), uw = 16-unit groups per workgroup (1 | 2 | 4: 256 / 512 / 1024 threads, the
- * cluster has u/(16 uw) members); 0 = automatic; uw | CRNN_RNN_XCD_LOCAL: the members of a cluster are the workgroup ids congruent
+ * mt, uw name the schedule, and there is one: mt = batch rows per workgroup / 16 is 1, uw = 16-unit groups per workgroup is 2; 0 means
+ * that one too.  Any other mt, or low byte of uw, returns CRNN_ERR_UNSUPPORTED before anything is launched (32-row tiles and 256- /
+ * 1024-thread workgroups existed once and measured slower in every mode: profiles/r02_lstm_bench.json, profiles/r03_lstm_bench.json).
+ * uw | CRNN_RNN_XCD_LOCAL: the members of a cluster are the workgroup ids congruent
  * modulo 8 (observed: one XCD) instead of consecutive ids; each cluster then checks HW_REG_XCC_ID of all its members once per launch and,
  * only if they agree, exchanges with plain L2-resident stores instead of write-through ones -- same results for any placement.  crnn_lstm_persist_supported: 0 if (u, dt_u) has a kernel
  * (fp32: u in {64,128,256}; bf16: u in {128,256,512}), else -3 -- use the step kernels then. */

@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
-"""Persistent LSTM recurrence of one Bidirectional layer (B = 256, T = 52, u = 256; the step's variant: 16-row tiles, two unit groups per workgroup, XCD-local
-clusters), forward and BPTT, bf16 and fp32 recurrent weights: the product library against variant builds of rnn_persist.hip alone
-(RNN_LIBS=name,name -> scripts/_trace/librnn_<name>.so).  Median of 20 launches, us."""
+"""Persistent LSTM recurrence of one Bidirectional layer (B = 256, T = 52, u = 256; 16-row tiles, two unit groups per workgroup, XCD-local
+clusters), forward and BPTT, bf16 and fp32 recurrent weights: the product library against variant builds of rnn_persist.hip alone, in one
+process on the same buffers -- e.g. the parent commit's file, to compare a change of the kernels with what it replaces:
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -I <variant tree>/include <variant tree>/crnn-ocr-lite_amd/csrc/rnn_persist.hip \
+          -o scripts/_trace/librnn_<name>.so
+    RNN_LIBS=<name>[,<name>...] python scripts/lstm_ablate.py
+
+A variant exports crnn_lstm_fwd_persist, crnn_lstm_bwd_persist_db and crnn_lstm_persist_xbuf_bytes with the product's signatures.
+Median of 20 launches, us, warm and after a 512 MiB fill (operands out of the caches)."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "crnn-ocr-lite_amd")]

@@ -15,7 +15,7 @@ lib = ctypes.CDLL(os.path.join(ROOT, "scripts", "_trace", "librnn_trace.so"))
 lib.crnn_lstm_persist_xbuf_bytes.restype = ctypes.c_size_t
 B, T, u = int(os.environ.get("B", 256)), 52, 256
 G = 4 * u
-mt = int(os.environ.get("MT", 1)); uw = int(os.environ.get("UW", 1)) | (0x100 if os.environ.get("XCD", "0") == "1" else 0)   # XCD=1: XCD-local clusters
+mt = int(os.environ.get("MT", 1)); uw = int(os.environ.get("UW", 2)) | (0x100 if os.environ.get("XCD", "0") == "1" else 0)   # XCD=1: XCD-local clusters
 rs = np.random.RandomState(0)
 P = lambda t: ctypes.c_void_p(t.data_ptr())
 S = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -541,16 +541,16 @@ def _lstm_persist_case(B, T, u, bf16, mt, uw, seed):
 
 
 @pytest.mark.parametrize("B,T,u,bf16,mt,uw", [
-    (5, 7, 64, False, 0, 0), (33, 6, 128, False, 1, 1), (33, 6, 128, False, 2, 2), (70, 9, 256, False, 0, 0), (40, 5, 256, False, 2, 1),
-    (20, 9, 128, True, 0, 0), (37, 8, 256, True, 1, 1), (37, 8, 256, True, 2, 2), (37, 8, 256, True, 1, 4), (256, 52, 256, True, 0, 0),
+    (5, 7, 64, False, 0, 0), (33, 6, 128, False, 0, 0), (33, 6, 128, False, 1, 2), (70, 9, 256, False, 0, 0), (40, 5, 256, False, 1, 2),
+    (20, 9, 128, True, 0, 0), (37, 8, 256, True, 0, 0), (37, 8, 256, True, 1, 2), (256, 52, 256, True, 0, 0),
     (256, 52, 256, True, 1, 2), (64, 102, 256, False, 0, 0), (18, 5, 512, True, 0, 0), (600, 4, 128, True, 0, 0),
     # uw | 0x100 (CRNN_RNN_XCD_LOCAL): cluster members = workgroup ids congruent modulo 8 (needs #clusters % 8 == 0, else the linear map)
-    (256, 52, 256, True, 0, 0x100), (64, 9, 256, False, 1, 0x101), (128, 7, 128, True, 2, 0x102), (37, 8, 256, True, 1, 0x102)])
+    (256, 52, 256, True, 0, 0x100), (64, 9, 256, False, 1, 0x100), (128, 7, 128, True, 1, 0x102), (37, 8, 256, True, 1, 0x102)])
 def test_persistent_lstm_is_bit_identical_to_the_step_kernels(B, T, u, bf16, mt, uw):
-    """One launch per layer (cluster of u/16 workgroups per batch tile, recurrent weights + cell state in registers, h_t / dz_t
+    """One launch per layer (cluster of u/32 workgroups per 16-row batch tile, recurrent weights + cell state in registers, h_t / dz_t
     all-gathered through device memory and staged through LDS) must reproduce the T-launch path bit for bit, forward and
-    BPTT, fp32 and bf16 recurrent products, ragged batch tiles, 16- and 32-row tiles, 256- / 512- / 1024-thread workgroups
-    (cluster sizes u/16, u/32, u/64), T up to the IAM shape's 102, a batch that needs several launches (600 rows)."""
+    BPTT, fp32 and bf16 recurrent products, ragged batch tiles, the one schedule spelled as automatic (0, 0) and explicitly (1, 2),
+    T up to the IAM shape's 102, a batch that needs several launches (600 rows)."""
     r = _lstm_persist_case(B, T, u, bf16, mt, uw, seed=B + T + u)
     a, b = r["step"], r["persist"]
     assert b["status"] == 0, "a bounded wait of the persistent kernel gave up"
@@ -563,6 +563,29 @@ def test_persistent_lstm_is_bit_identical_to_the_step_kernels(B, T, u, bf16, mt,
     for d in range(2):        # the bias gradient the same launch leaves: column sums of dz over time and batch
         ref = b["dz"][d].astype(np.float64).reshape(-1, 4 * u).sum(0)
         assert_close(r["db"][d], ref, rtol=1e-4, atol=1e-5 * max(1.0, np.abs(ref).max()), what="db dir%d" % d)
+
+
+def test_persistent_lstm_refuses_removed_schedules():
+    """The 32-row tiles (mt = 2) and the one- and four-group workgroups (uw = 1, 4) are gone: both entry points answer -3
+    (CRNN_ERR_UNSUPPORTED) before any launch -- valid pointers, a full-size exchange buffer, and its status words stay as they were."""
+    B, T, u = 16, 3, 64; G = 4 * u
+    nbytes = L().crnn_lstm_persist_xbuf_bytes(T, B, u, 0)
+    xbuf = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device="cuda")
+    xbuf[0] = 5; xbuf[4] = 0x1234                       # sticky give-up counter (byte 0), per-launch status (byte 16)
+    before = xbuf.clone()
+    ut = [zeros(G, u) for _ in range(2)]; Ud = [zeros(u, G) for _ in range(2)]
+    xw = [zeros(T, B, G) for _ in range(2)]; gd = zeros(T, B, 2 * u)
+    hcat = zeros(T, B, 2 * u); cs = [zeros(T, B, u) for _ in range(2)]; gt = [zeros(T, B, G) for _ in range(2)]
+    dz = [zeros(T, B, G) for _ in range(2)]; dbp = [zeros(L().crnn_rnn_db_rows(B), G) for _ in range(2)]
+    hb = ctypes.c_void_p(hcat.data_ptr() + 4 * u); gb = ctypes.c_void_p(gd.data_ptr() + 4 * u)
+    for mt, uw in ((2, 0), (0, 1), (0, 4), (2, 2), (1, 0x101), (1, 0x104)):
+        assert L().crnn_lstm_fwd_persist(P(xw[0]), P(xw[1]), P(ut[0]), P(ut[1]), P(hcat), hb, 2 * u, P(cs[0]), P(cs[1]), P(gt[0]), P(gt[1]), T, B, u, 0,
+                                         P(xbuf), nbytes, mt, uw, S()) == -3, (mt, uw)
+        assert L().crnn_lstm_bwd_persist_db(P(Ud[0]), P(Ud[1]), P(cs[0]), P(cs[1]), P(gt[0]), P(gt[1]), P(gd), gb, 2 * u, P(dz[0]), P(dz[1]), P(dbp[0]),
+                                            P(dbp[1]), T, B, u, 0, P(xbuf), nbytes, mt, uw, S()) == -3, (mt, uw)
+    torch.cuda.synchronize()
+    assert torch.equal(xbuf, before)                    # nothing was filled or launched: the whole buffer, status words included
+    assert not hcat.any() and not dz[0].any()
 
 
 def test_persistent_lstm_reports_a_lost_cluster():
