@@ -3,6 +3,7 @@
 HIP beam-search decode (beam_width=10, top_paths=1, merge_repeated as TF 1.8), optional edit-distance report
 and prediction.csv.  --device_score (with --validate) keeps decoding and scoring on the GPU: same report, same prediction.csv.
 --lexicon FILE decodes to the most probable word of a list (crnn_mi355x.lexicon) instead of the beam search.
+--lexicon_shortlist K (with --lexicon) scores per image only the K words nearest in edit distance to the beam search's --lexicon_paths best paths.
 --align (with --result_path) aligns every prediction to its own softmax map (crnn_mi355x.align) and writes alignment.csv: per character its frames
 on the network's time axis and its log-probability.
 --lm FILE decodes with a character language model in the beam search (crnn_mi355x.lm): FILE is a saved CharLM (.npz) or a word list to count one from.
@@ -42,6 +43,10 @@ def build_parser():
                         help='with --validate: decode and score on the GPU (one edit-distance kernel per batch); no softmax map is copied to the host')
     parser.add_argument('--lexicon', type=str, default=None,
                         help='a word list, one word per line: decode to the word of the list with the highest CTC probability instead of the beam search')
+    parser.add_argument('--lexicon_shortlist', type=int, default=None,
+                        help='with --lexicon: score per image only the K (1..1024) words nearest in edit distance to the beam search\'s paths (50 is a placeholder: tune it)')
+    parser.add_argument('--lexicon_paths', type=int, default=None,
+                        help='with --lexicon_shortlist: how many of the beam search\'s best paths (1..8, default 1) the shortlist is made from')
     parser.add_argument('--align', action='store_true',
                         help='with --result_path: also write alignment.csv -- the best CTC path of every prediction through its own softmax map, per character its frames and log-probability')
     parser.add_argument('--lm', type=str, default=None,
@@ -65,6 +70,14 @@ def parse_args(argv=None):
         parser.error("--align reads the softmax maps, which --device_score never materialises: use one or the other")
     if args.lm is not None and args.lexicon is not None:
         parser.error("--lm and --lexicon are two decoders: use one or the other")
+    if (args.lexicon_shortlist is not None or args.lexicon_paths is not None) and args.lexicon is None:
+        parser.error("--lexicon_shortlist and --lexicon_paths shorten a word list: they need --lexicon")
+    if args.lexicon_paths is not None and args.lexicon_shortlist is None:
+        parser.error("--lexicon_paths chooses the paths a shortlist is made from: it needs --lexicon_shortlist")
+    if args.lexicon_shortlist is not None and not 1 <= args.lexicon_shortlist <= 1024:
+        parser.error("--lexicon_shortlist must be 1..1024")
+    if args.lexicon_paths is not None and not 1 <= args.lexicon_paths <= 8:
+        parser.error("--lexicon_paths must be 1..8")
     if args.nbest is not None and args.result_path is None:
         parser.error("--nbest writes nbest.csv next to prediction.csv: it needs --result_path")
     if args.nbest is not None and args.lexicon is not None:
@@ -92,8 +105,11 @@ def main(argv=None):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")                  # the count is printed below instead
             lexicon = U.Lexicon([line.rstrip("\r\n") for line in open(args.lexicon)], inverse_classes)
-        print(" [INFO] Lexicon: %d words, %d rejected (a character outside the alphabet, or longer than 31) " % (len(lexicon), len(lexicon.rejected)))
-        decoder = U.LexiconDecoder(lexicon, top_paths=1)
+        mode = "every word scored" if args.lexicon_shortlist is None else \
+            "shortlist of the %d words nearest to %d beam path(s)" % (args.lexicon_shortlist, args.lexicon_paths or 1)
+        print(" [INFO] Lexicon: %d words, %d rejected (a character outside the alphabet, or longer than 31); %s "
+              % (len(lexicon), len(lexicon.rejected), mode))
+        decoder = U.LexiconDecoder(lexicon, top_paths=1, shortlist=args.lexicon_shortlist, paths=args.lexicon_paths or 1)
     if args.lm is not None or args.nbest is not None:
         lm = None
         if args.lm is not None and args.lm.endswith(".npz"):

@@ -10,7 +10,7 @@ from crnn_mi355x import optimizers  # noqa: F401  (utils.py:28 re-exports keras.
 from crnn_mi355x.surface import (CRNN, Model, init_predictor, load_custom_model, load_model_custom, save_model_json,  # noqa: F401
                                  model_from_json, ctc_lambda_func, BilinearInterpolation, STN, get_initial_weights)
 from crnn_mi355x.decode import DecodeCTCPred, labels_to_text  # noqa: F401
-from crnn_mi355x.lexicon import Lexicon, LexiconDecoder  # noqa: F401  (beyond the reference: lexicon-constrained decoding on the device)
+from crnn_mi355x.lexicon import Lexicon, LexiconDecoder, lexicon_nearest  # noqa: F401  (beyond the reference: lexicon-constrained decoding on the device)
 from crnn_mi355x.lm import CharLM, LMDecoder  # noqa: F401  (beyond the reference: beam search with a character language model, N-best)
 from crnn_mi355x.align import CTCAligner, Alignment, CharSpan  # noqa: F401  (beyond the reference: character alignment on the device)
 from crnn_mi355x.data import (Readf, open_img, read_img, norm, parse_mjsynth, get_lengths, get_lexicon, make_ohe)  # noqa: F401

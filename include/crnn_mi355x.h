@@ -248,6 +248,24 @@ int crnn_ctc_lexicon_score(const float* y, const int* input_len, const int* word
  * word-table index), val [B][k] = the score; descending by score, equal scores to the lower position j; slots with no finite score left get
  * idx = -1, val = -inf.  One launch, one workgroup per row, a fixed order: two calls on the same input agree bit for bit.  No workspace. */
 int crnn_ctc_lexicon_topk(const float* scores, const int* cand, int* idx, float* val, int B, int M, int k, crnn_stream_t stream);
+/* Lexicon shortlists (csrc/lexicon_nearest.hip): per sample the K words of the table nearest in edit distance to its decoded label rows -- the
+ * `cand` lists of crnn_ctc_lexicon_score, made on the device.  queries [B][P][qcols] int32: P label rows per sample in the layout
+ * crnn_ctc_beam_decode_lm writes (qcols = T).  Every query element outside [0, C - 2] is dropped wherever it stands (the blank C - 1, the -1
+ * padding, anything else); what remains is the query, of length m.  If m > 64 only the first 64 kept symbols are used: words are at most 31
+ * long, so such a query is more than 33 edits from every word and the order among the words means nothing there.  words [N][Lmax], word_len [N]:
+ * the table crnn_ctc_lexicon_score takes.  d(b, j) = min over p < P of Levenshtein(query[b][p], word j), unit costs.  A table entry that cannot
+ * be trusted (word_len outside [0, Lmax], a label outside [0, C - 2] inside the length) gets d = 255, is never selected and indexes nothing.
+ * Per sample the K entries smallest by (d ascending, table index ascending) among those with d < 255 are selected; idx [B][K] int32 holds their
+ * table indices in ASCENDING INDEX order (the row order the scoring kernel's tie rule expects), unused slots -1 and last; dist [B][K] int32 the
+ * matching distances, -1 in unused slots.  ws: crnn_lexicon_nearest_workspace_bytes(B, N) bytes = B * (1024 + roundup(N, 4)), 4-byte aligned
+ * (a histogram of d per sample, then d as bytes).  Integer arithmetic and integer atomics only, every order fixed by indices: two calls on the
+ * same input agree bit for bit.
+ * -2: a null pointer (any of the six), a negative B or N, a workspace that is too small or misaligned.  -3: C outside 2..128, Lmax outside
+ * 1..31, P outside 1..8, qcols outside 1..1024, K outside 1..1024, or B > 65535.  B == 0 or N == 0 launches nothing; with N == 0 and B > 0 both
+ * outputs are filled with -1. */
+size_t crnn_lexicon_nearest_workspace_bytes(int B, int N);
+int crnn_lexicon_nearest(const int* queries, int P, int qcols, const int* words, const int* word_len, int* idx, int* dist, void* ws,
+                         size_t ws_bytes, int B, int C, int N, int Lmax, int K, crnn_stream_t stream);
 
 /* ---- character alignment: the best CTC path of a given transcription, with its backtrace (csrc/align.hip) ---- */
 /* Per sample the Viterbi path of labels[b] through y[b, skip : skip + Tb]: where each character sits on the time axis and the log-probability
