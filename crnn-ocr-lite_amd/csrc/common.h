@@ -189,7 +189,7 @@ __device__ __forceinline__ unsigned pack2_bf16(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));   // v_cvt_pk_bf16_f32 (RNE)
 }
 // x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), round-to-nearest-even each (the differences are exact in
-// fp32): the three bf16 planes of the parity mode's products (gemm_bf16.inc: gemm_x3p_kernel; gemm_wres3.hip).  One spelling shared by every
+// fp32): the three bf16 planes of the parity mode's products (gemm_planes.hip: gemm_x3p_kernel; gemm_wres3.hip).  One spelling shared by every
 // kernel that forms planes, so that all of them produce the same words.  w0 / w1 / w2 = the packed pair (v0 low half, v1 high half) of each plane.
 // (scalar v_sub_f32: SLP-packed into v_pk_add_f32 these four subtractions cost ~25 cycles each beside running MFMAs)
 __device__ __forceinline__ void crnn_split3_pair(float v0, float v1, unsigned& w0, unsigned& w1, unsigned& w2) {

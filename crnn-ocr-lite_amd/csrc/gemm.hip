@@ -12,88 +12,14 @@
 // stored [BK][rows] and read as ds_read_b32.  The k order inside a BK chunk is permuted
 // (k = 8*kk8 + 4*half + e) identically for A and B so one b128 read feeds four MFMAs.
 // Workgroup ids are remapped so that tiles sharing the same A rows run on the same XCD (L2).
-#include "common.h"
-#include <stdlib.h>
+//
+// This file also holds the second stages of a split reduction and the extern "C" entry points of the tile GEMM (all but crnn_split3_planes,
+// which sits beside its kernel in gemm_planes.hip): an entry point describes its product as a TileGemm (gemm_tile.h) and the launcher of the
+// product's kernel (here, gemm_bf16.hip, gemm_planes.hip) runs it.
+#include "gemm_tile.h"
 
 #define GBK 32
 #define GLDM (GBK + 4)
-
-struct GemmParams {
-  const float* A; const float* B; float* C;
-  int M, N, K;
-  int lda, ldb, ldc;
-  const float* bias;
-  int act;         // 0 none, 1 relu
-  int accumulate;  // C += result
-  int permP;       // 0: none; else out_row = (m % P) * (M / P) + m / P
-  int klen;        // K range per split (blockIdx.y); nsplit = gridDim.y
-  int vecA, vecB;  // 16-byte vector loads legal for the operand
-  int vecC;        // 16-byte stores legal for C (and the split scratch)
-  int dtA, dtB, dtC;  // storage of the operands / result (CRNN_F32 | CRNN_BF16); the fp32 kernel requires all CRNN_F32
-  int tilesN;
-  int xsplit;      // > 0: 1-D grid of tiles * xsplit workgroups, K split xsplit-fold with split s on XCD s % 8 (all tiles of one K range
-                   // share an L2): id -> xcd = id & 7, tile = (id >> 3) % tiles, split = ((id >> 3) / tiles) * 8 + xcd.  0: 2-D grid (tile, split)
-  float* stats;    // optional [tilesM][2][N]: per-tile column sums / sums of squares of the result as stored (BatchNorm statistics)
-  const float* cscale; const float* cshift;   // optional per-column epilogue  C = ReLU6(C * cscale[n] + cshift[n])  (inference BatchNorm folded in)
-  // optional producer prologue on A (bf16 kernel, bf16 A): the operand the MFMA sees is ReLU6(A * ascale[ch] + ashift[ch])
-  // rounded to bf16, ch = the reduction index (modes 0/1) or the A row (mode 2): the BatchNorm + ReLU6 between a depthwise
-  // and a pointwise convolution, applied while the tile is staged instead of in a pass of its own
-  const float* ascale; const float* ashift;
-  // optional BatchNorm-BACKWARD statistics from the epilogue (bf16-family tile kernels, fp32 result, whole tiles): C is the gradient da that arrives at
-  // a ReLU6(BatchNorm(d)); bnpart [tilesM][2][N] = per-tile column sums of gy and gy * xhat, gy = C where 0 < d * scale + shift < 6,
-  // xhat = (d - mean) / sqrt(var + eps); bnD [M][ldd] fp32 = d, bnstate = [mean | var | scale | shift] x N
-  const float* bnD; int ldd; const float* bnstate; float* bnpart;
-#ifdef CRNN_GEMM_EXP
-  unsigned long long* trace;   // ablation build only: s_memrealtime stamps of workgroup 300, thread 0
-  int exp;         // ablation build only (scripts/gemm_ablate.py): 1 no C stores, 2 no MFMA, 4 B loaded once, 8 A loaded once
-#endif
-};
-
-// ---- statistics epilogue: per-tile column sums / sums of squares of the result as it will be stored, taken straight
-// from the MFMA accumulators (a lane owns one column of each 32x32 block: 16 rows x TM blocks per column block), then
-// combined across the two lane halves (shuffle) and the waves stacked along M (LDS), all in a fixed order.
-typedef float f32x16_stats __attribute__((ext_vector_type(16)));
-template <int TM, int TN>
-__device__ __forceinline__ void tile_stats_regs(const f32x16_stats (&acc)[TM][TN], int row_base, int M, int dtC, int half,
-                                                float (&ssum)[TN], float (&ssq)[TN]) {
-  const bool full = row_base + TM * 32 <= M;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    float s0 = 0.f, s1 = 0.f, q0 = 0.f, q1 = 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float v = acc[i][j][e];
-        if (dtC == CRNN_BF16) v = __uint_as_float(pack2_bf16(v, 0.f) << 16);   // the value the consumer reads back
-        if (!full && row_base + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * half >= M) v = 0.f;
-        if (e & 1) { s1 += v; q1 = fmaf(v, v, q1); } else { s0 += v; q0 = fmaf(v, v, q0); }
-      }
-    float sv = s0 + s1, qv = q0 + q1;
-    sv += __shfl_xor(sv, 32, 64); qv += __shfl_xor(qv, 32, 64);
-    ssum[j] = sv; ssq[j] = qv;
-  }
-}
-// smem: [2][WAVES_M][BN]; lanes of half 0 deposit their wave's column sums, then one thread per (stat, column) adds the waves
-template <int BN, int TN, int WAVES_M>
-__device__ __forceinline__ void tile_stats_finish(float* smem, float* stats, int tm, int n0, int N, int tid, int wmi, int wn0,
-                                                  int half, int l31, const float (&ssum)[TN], const float (&ssq)[TN]) {
-  if (half == 0) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      smem[(0 * WAVES_M + wmi) * BN + wn0 + j * 32 + l31] = ssum[j];
-      smem[(1 * WAVES_M + wmi) * BN + wn0 + j * 32 + l31] = ssq[j];
-    }
-  }
-  __syncthreads();
-  if (tid < 2 * BN) {
-    const int v = tid / BN, c = tid % BN;
-    float a = 0.f;
-#pragma unroll
-    for (int q = 0; q < WAVES_M; ++q) a += smem[(v * WAVES_M + q) * BN + c];
-    if (n0 + c < N) stats[((long)tm * 2 + v) * N + n0 + c] = a;
-  }
-}
 
 template <bool KM, int ROWS>
 __device__ __forceinline__ void load_tile(const float* __restrict__ X, int ld, int row0, int nrows_total,
@@ -351,8 +277,11 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce8_kernel(const float* _
   if (p.accumulate) { const float4 c = *dst; s[0] += c.x; s[1] += c.y; s[2] += c.z; s[3] += c.w; }
   *dst = make_float4(s[0], s[1], s[2], s[3]);
 }
+
+namespace crnn_tile {
+
 // launches the matching second stage
-static inline void launch_splitk_reduce(const float* scratch, int nsplit, const GemmParams& p, hipStream_t stream) {
+void launch_splitk_reduce(const float* scratch, int nsplit, const GemmParams& p, hipStream_t stream) {
   const long total = (long)p.M * p.N;
   const bool vec = nsplit <= 8 && p.dtC == CRNN_F32 && (p.N & 3) == 0 && (p.ldc & 3) == 0 && !(((uintptr_t)p.C | (uintptr_t)scratch) & 15) &&
                    (!p.bias || !((uintptr_t)p.bias & 15));
@@ -361,73 +290,101 @@ static inline void launch_splitk_reduce(const float* scratch, int nsplit, const 
   else hipLaunchKernelGGL(gemm_splitk_reduce_kernel<8>, dim3(cdiv(total, 32)), dim3(32, 8), 0, stream, scratch, nsplit, p);
 }
 
-static inline int aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// (BN, mode) -> the instantiation
+template <int BN>
+static void (*f32_kernel(int mode))(GemmParams) {
+  return mode == 0 ? gemm_f32_kernel<BN, false, true> : mode == 1 ? gemm_f32_kernel<BN, false, false> : gemm_f32_kernel<BN, true, true>;
+}
+// fp32 tensors only, no prologue; a split stays a 2-D grid (the kernel has no XCD-pinned form)
+int gemm_tile_f32(const TileGemm& g) {
+  if (g.dtA != CRNN_F32 || g.dtB != CRNN_F32 || g.dtC != CRNN_F32 || g.ascale || g.ashift || g.bnb) return CRNN_ERR_ARG;
+  TilePlan t;
+  CRNN_TRY(plan_tile_gemm(g, GBK, kSplitWorkgroups, false, false, t));
+  hipLaunchKernelGGL(t.BN == 128 ? f32_kernel<128>(g.mode) : f32_kernel<64>(g.mode), t.grid, dim3(256), 0, g.stream, t.pk);
+  return finish_tile_gemm(g, t);
+}
+
+}  // namespace crnn_tile
+
+using crnn_tile::TileGemm;
+using crnn_tile::gemm_tile;
+
+// operands and shapes of a product; everything else an entry point sets by name
+static TileGemm tile_gemm(crnn_tile::Product product, int mode, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                          hipStream_t stream) {
+  TileGemm g;
+  g.product = product; g.mode = mode; g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.stream = stream;
+  return g;
+}
+// the epilogue options and the scratch of crnn_gemm_f32's argument list (shared by the crnn_gemm_* entry points)
+static int gemm_with_options(TileGemm g, const float* bias, int act, int accumulate, int permP, float* scratch, size_t scratch_bytes) {
+  g.bias = bias; g.act = act; g.accumulate = accumulate; g.permP = permP; g.scratch = scratch; g.scratch_bytes = scratch_bytes;
+  return gemm_tile(g);
+}
 
 // mode: 0 = NN, 1 = NT, 2 = TN.  `scratch` (scratch_bytes) is needed only when the reduction is split
 // (mode 2 with few output tiles); pass nullptr/0 to forbid splitting.
-static int gemm_f32_impl(int mode, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb,
-                         int ldc, const float* bias, int act, int accumulate, int permP, float* scratch,
-                         size_t scratch_bytes, float* stats, hipStream_t stream, const float* cscale = nullptr, const float* cshift = nullptr) {
-  if (M <= 0 || N <= 0 || K <= 0) return CRNN_ERR_ARG;
-  if (permP && (M % permP) != 0) return CRNN_ERR_ARG;
-  if (stats && (bias || act || accumulate || permP || scratch || cscale)) return CRNN_ERR_ARG;   // statistics of the plain product only
-  if (cscale && (scratch || accumulate || !cshift)) return CRNN_ERR_ARG;                          // no split reduction with the folded BatchNorm
-  GemmParams p;
-  p.xsplit = 0;
-  p.stats = stats; p.cscale = cscale; p.cshift = cshift; p.ascale = nullptr; p.ashift = nullptr;
-  p.bnD = nullptr; p.ldd = 0; p.bnstate = nullptr; p.bnpart = nullptr;
-  p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  p.bias = bias; p.act = act; p.accumulate = accumulate; p.permP = permP;
-  p.dtA = p.dtB = p.dtC = CRNN_F32;
-  const bool a_km = (mode == 2), b_km = (mode != 1);
-  // contiguous extent of each operand: A: K (m-major) or M (k-major); B: N (k-major) or K (n-major)
-  p.vecA = aligned16(A) && (lda % 4 == 0) && ((a_km ? M : K) % 4 == 0);
-  p.vecB = aligned16(B) && (ldb % 4 == 0) && ((b_km ? N : K) % 4 == 0);
-  p.vecC = aligned16(C) && (ldc % 4 == 0) && (N % 4 == 0) && (!scratch || aligned16(scratch));
-  const int BN = (N <= 64) ? 64 : 128;
-  const int tilesM = cdiv(M, 128), tilesN = cdiv(N, BN);
-  p.tilesN = tilesN;
-  int tiles = tilesM * tilesN;
-  int nsplit = 1;
-  const int split_target = crnn_knob("CRNN_SPLIT_WGS", 768);   // workgroups a split reduction aims for: 3 resident per CU
-  if (scratch && ((tiles < 256 && K >= 2048) || (tiles <= 16 && K >= 512))) {
-    nsplit = cdiv(split_target, tiles);
-    int maxs = K / (K >= 2048 ? 512 : 128); if (maxs < 1) maxs = 1;
-    if (nsplit > maxs) nsplit = maxs;
-    size_t per = (size_t)M * N * sizeof(float);
-    size_t fit = scratch_bytes / per;
-    if ((size_t)nsplit > fit) nsplit = (int)fit;
-    if (nsplit < 1) nsplit = 1;
-  }
-  int klen = cdiv(K, nsplit);
-  klen = ((klen + GBK - 1) / GBK) * GBK;
-  nsplit = cdiv(K, klen);
-  p.klen = klen;
-  GemmParams pk = p;
-  if (nsplit > 1) pk.C = scratch;
-  dim3 grid(tiles, nsplit), block(256);
-#define LAUNCH(BNV, AK, BKM) hipLaunchKernelGGL((gemm_f32_kernel<BNV, AK, BKM>), grid, block, 0, stream, pk)
-  if (BN == 128) {
-    if (mode == 0) LAUNCH(128, false, true); else if (mode == 1) LAUNCH(128, false, false); else LAUNCH(128, true, true);
-  } else {
-    if (mode == 0) LAUNCH(64, false, true); else if (mode == 1) LAUNCH(64, false, false); else LAUNCH(64, true, true);
-  }
-#undef LAUNCH
-  CRNN_LAUNCH_CHECK();
-  if (nsplit > 1) {
-    launch_splitk_reduce(scratch, nsplit, p, stream);
-    CRNN_LAUNCH_CHECK();
-  }
-  return CRNN_OK;
-}
-
 extern "C" int crnn_gemm_f32(int mode, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb,
                              int ldc, const float* bias, int act, int accumulate, int permP, float* scratch,
                              size_t scratch_bytes, hipStream_t stream) {
-  return gemm_f32_impl(mode, A, B, C, M, N, K, lda, ldb, ldc, bias, act, accumulate, permP, scratch, scratch_bytes, nullptr, stream);
+  return gemm_with_options(tile_gemm(crnn_tile::PRODUCT_F32, mode, A, B, C, M, N, K, lda, ldb, ldc, stream), bias, act, accumulate, permP, scratch, scratch_bytes);
 }
-
-#include "gemm_bf16.inc"
+// Same contract (include/crnn_mi355x.h); products in bf16, accumulation in fp32.  dtA/dtB/dtC give
+// the storage of A, B and C (CRNN_F32 | CRNN_BF16); leading dimensions are in elements of the respective type.
+extern "C" int crnn_gemm_bf16_ex(int mode, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb,
+                                 int ldc, const float* bias, int act, int accumulate, int permP, float* scratch,
+                                 size_t scratch_bytes, int dtA, int dtB, int dtC, hipStream_t stream) {
+  TileGemm g = tile_gemm(crnn_tile::PRODUCT_BF16, mode, A, B, C, M, N, K, lda, ldb, ldc, stream);
+  g.dtA = dtA; g.dtB = dtB; g.dtC = dtC;
+  return gemm_with_options(g, bias, act, accumulate, permP, scratch, scratch_bytes);
+}
+extern "C" int crnn_gemm_bf16(int mode, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb,
+                              int ldc, const float* bias, int act, int accumulate, int permP, float* scratch,
+                              size_t scratch_bytes, hipStream_t stream) {
+  return crnn_gemm_bf16_ex(mode, A, B, C, M, N, K, lda, ldb, ldc, bias, act, accumulate, permP, scratch, scratch_bytes, CRNN_F32, CRNN_F32,
+                           CRNN_F32, stream);
+}
+// fp32 in, fp32 out, fp32-accurate products from three bf16 planes per operand (six bf16 MFMAs per k-step instead of the eight four-times
+// slower fp32 ones): the contract of crnn_gemm_f32 with results equal to it to fp32 round-off (not bit for bit) -- the conv-stack / dense /
+// RNN-projection GEMMs of the parity mode (unless crnn_config.flags has CRNN_FLAG_F32_MFMA_GEMMS).
+extern "C" int crnn_gemm_f32x3(int mode, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb,
+                               int ldc, const float* bias, int act, int accumulate, int permP, float* scratch,
+                               size_t scratch_bytes, hipStream_t stream) {
+  return gemm_with_options(tile_gemm(crnn_tile::PRODUCT_PLANES3, mode, A, B, C, M, N, K, lda, ldb, ldc, stream), bias, act, accumulate, permP, scratch, scratch_bytes);
+}
+// crnn_gemm_f32x3 with two planes per operand (hi*hi + hi*mid + mid*hi: 16 significant bits per factor): same contract
+extern "C" int crnn_gemm_f32x2(int mode, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb,
+                               int ldc, const float* bias, int act, int accumulate, int permP, float* scratch,
+                               size_t scratch_bytes, hipStream_t stream) {
+  return gemm_with_options(tile_gemm(crnn_tile::PRODUCT_PLANES2, mode, A, B, C, M, N, K, lda, ldb, ldc, stream), bias, act, accumulate, permP, scratch, scratch_bytes);
+}
+// crnn_gemm_f32x3 mode 1 for the data gradient da = dq . W^T of a depthwise-separable block in the parity mode (utils.py:45-49 backwards) that also takes
+// the statistics pass of the BatchNorm in front of the pointwise convolution: stat_partials [M / 128][2][N] = per-tile column sums of gy and gy * xhat,
+// gy = da where 0 < d * scale + shift < 6, xhat = (d - mean) / sqrt(var + eps); d [M][N] fp32 = that BatchNorm's input, bnstate = [mean|var|scale|shift] x N.
+// Feed the partials to crnn_bn_bwd_finalize_folded, apply with crnn_bn_bwd_apply_ex.  Whole tiles only (M % 128 == 0, N % 64 == 0, K % 64 == 0,
+// 16-byte aligned operands): -3 otherwise (run crnn_bn_bwd_ex).  da equals crnn_gemm_f32x3's bit for bit; the sums are those of the stand-alone pass in another order.
+extern "C" int crnn_gemm_f32x3_bnstats_supported(long M, int N, int K) {
+  return (M > 0 && M <= 0x7fffffffL && M % 128 == 0 && N % 64 == 0 && (N <= 64 || N % 128 == 0) && K % HBK == 0) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
+extern "C" int crnn_gemm_f32x3_bnstats_rows(long M) { return (int)(M / 128); }
+static int gemm_planes_bnstats(crnn_tile::Product product, const float* dq, const float* W, float* da, long M, int N, int K, const float* d, const float* bnstate,
+                               float* stat_partials, hipStream_t stream) {
+  CRNN_TRY(crnn_gemm_f32x3_bnstats_supported(M, N, K));
+  const crnn_tile::BnBwdEpilogue e{d, N, bnstate, stat_partials};
+  TileGemm g = tile_gemm(product, 1, dq, W, da, (int)M, N, K, K, K, N, stream);
+  g.bnb = &e;
+  return gemm_tile(g);
+}
+extern "C" int crnn_gemm_f32x3_bnstats(const float* dq, const float* W, float* da, long M, int N, int K, const float* d, const float* bnstate,
+                                       float* stat_partials, hipStream_t stream) {
+  return gemm_planes_bnstats(crnn_tile::PRODUCT_PLANES3, dq, W, da, M, N, K, d, bnstate, stat_partials, stream);
+}
+// Two-plane form of crnn_gemm_f32x3_bnstats: operands split into two bf16 planes, products hi*hi + hi*mid + mid*hi (16 significant bits per factor,
+// fp32 accumulation; relative error of a product <= 3 * 2^-18): half the MFMA work.  The parity mode's default for the BACKWARD GEMMs of the conv stack.
+extern "C" int crnn_gemm_f32x2_bnstats(const float* dq, const float* W, float* da, long M, int N, int K, const float* d, const float* bnstate,
+                                       float* stat_partials, hipStream_t stream) {
+  return gemm_planes_bnstats(crnn_tile::PRODUCT_PLANES2, dq, W, da, M, N, K, d, bnstate, stat_partials, stream);
+}
 
 // ---- pointwise 1x1 convolution = GEMM over the pixels, with the next BatchNorm's statistics from the epilogue
 extern "C" int crnn_pwconv_stat_rows(long M) { return cdiv(M, 128); }
@@ -435,62 +392,67 @@ extern "C" int crnn_pwconv_fwd(const void* a, const void* w, void* q, long M, in
                                const float* out_bnstate, int bf16_products, int dt_a, int dt_w, int dt_q, int w_transposed,
                                hipStream_t stream) {
   if (M <= 0 || M > 0x7fffffffL) return CRNN_ERR_ARG;
+  // bf16_products: 0 = fp32 MFMA; 1 = bf16; fp32 tensors only: 2 = fp32-accurate three-plane bf16 products (crnn_gemm_f32x3), 3 = two planes (crnn_gemm_f32x2)
+  const crnn_tile::Product product = bf16_products == 2 ? crnn_tile::PRODUCT_PLANES3 : bf16_products == 3 ? crnn_tile::PRODUCT_PLANES2
+                                     : bf16_products ? crnn_tile::PRODUCT_BF16 : crnn_tile::PRODUCT_F32;
+  if (product == crnn_tile::PRODUCT_F32 && (dt_a != CRNN_F32 || dt_w != CRNN_F32 || dt_q != CRNN_F32)) return CRNN_ERR_ARG;
   // w_transposed: the weights are given as W^T [N][K] (both operands then contiguous along the reduction: the staging
   // needs no k-pair interleave and the fragments are single 16-byte LDS reads)
-  const int mode = w_transposed ? 1 : 0, ldw = w_transposed ? K : N;
+  TileGemm g = tile_gemm(product, w_transposed ? 1 : 0, a, w, q, (int)M, N, K, K, w_transposed ? K : N, N, stream);
+  g.dtA = dt_a; g.dtB = dt_w; g.dtC = dt_q;
+  g.stats = stat_partials;
   // out_bnstate ([mean|var|scale|shift] of the BatchNorm after the conv, inference): q = ReLU6(product * scale + shift)
-  const float* cs = out_bnstate ? out_bnstate + 2L * N : nullptr; const float* ch = out_bnstate ? out_bnstate + 3L * N : nullptr;
-  if (bf16_products == 2 || bf16_products == 3)   // fp32 tensors: 2 = fp32-accurate three-plane bf16 products (crnn_gemm_f32x3), 3 = two planes (crnn_gemm_f32x2)
-    return gemm_bf16_impl(mode, a, w, q, (int)M, N, K, K, ldw, N, nullptr, 0, 0, 0, nullptr, 0, dt_a, dt_w, dt_q, stat_partials, stream, cs, ch,
-                          nullptr, nullptr, true, nullptr, bf16_products == 2 ? 3 : 2);
-  if (bf16_products)
-    return gemm_bf16_impl(mode, a, w, q, (int)M, N, K, K, ldw, N, nullptr, 0, 0, 0, nullptr, 0, dt_a, dt_w, dt_q, stat_partials, stream, cs, ch);
-  if (dt_a != CRNN_F32 || dt_w != CRNN_F32 || dt_q != CRNN_F32) return CRNN_ERR_ARG;
-  return gemm_f32_impl(mode, (const float*)a, (const float*)w, (float*)q, (int)M, N, K, K, ldw, N, nullptr, 0, 0, 0, nullptr, 0, stat_partials, stream, cs, ch);
+  if (out_bnstate) { g.cscale = out_bnstate + 2L * N; g.cshift = out_bnstate + 3L * N; }
+  return gemm_tile(g);
 }
 
-// The same convolution fed by the PRE-BatchNorm depthwise output d (bf16): the operand is ReLU6(BN(d)) (utils.py:45-46),
-// formed per element while the tile is staged (GemmParams::ascale/ashift), so the activated tensor is never written.
+// The same convolution fed by the PRE-BatchNorm depthwise output d: the operand is ReLU6(BN(d)) (utils.py:45-46), formed per element
+// while the tile is staged (GemmParams::ascale/ashift), so the activated tensor is never written.  in_bnstate = [mean|var|scale|shift] x K.
+// forward: q [M][N] = ReLU6(BN(d [M][K])) . w;  weight gradient: dw [K][N] = ReLU6(BN(d))^T [K][M] . g [M][N] (fp32 result)
+static int pwconv_bnrelu6_fwd(crnn_tile::Product product, int dt, const void* d, const float* in_bnstate, const void* w, void* q, long M, int N, int K,
+                              float* stat_partials, int dt_q, int w_transposed, hipStream_t stream) {
+  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
+  TileGemm g = tile_gemm(product, w_transposed ? 1 : 0, d, w, q, (int)M, N, K, K, w_transposed ? K : N, N, stream);
+  g.dtA = g.dtB = dt; g.dtC = dt_q;
+  g.stats = stat_partials;
+  g.ascale = in_bnstate + 2L * K; g.ashift = in_bnstate + 3L * K;
+  return gemm_tile(g);
+}
+static int pwconv_bnrelu6_wgrad(crnn_tile::Product product, int dt, const void* d, const float* in_bnstate, const void* gy, float* dw, long M, int N, int K,
+                                float* scratch, size_t scratch_bytes, hipStream_t stream) {
+  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
+  TileGemm g = tile_gemm(product, 2, d, gy, dw, K, N, (int)M, K, N, N, stream);
+  g.dtA = g.dtB = dt;
+  g.scratch = scratch; g.scratch_bytes = scratch_bytes;
+  g.ascale = in_bnstate + 2L * K; g.ashift = in_bnstate + 3L * K;
+  return gemm_tile(g);
+}
+// bf16 tensors d, w, g (the bf16 kernel's prologue)
 extern "C" int crnn_pwconv_bnrelu6_fwd(const void* d, const float* in_bnstate, const void* w, void* q, long M, int N, int K,
                                        float* stat_partials, int dt_q, int w_transposed, hipStream_t stream) {
-  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
-  const int mode = w_transposed ? 1 : 0, ldw = w_transposed ? K : N;
-  return gemm_bf16_impl(mode, d, w, q, (int)M, N, K, K, ldw, N, nullptr, 0, 0, 0, nullptr, 0, CRNN_BF16, CRNN_BF16, dt_q, stat_partials, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K);
+  return pwconv_bnrelu6_fwd(crnn_tile::PRODUCT_BF16, CRNN_BF16, d, in_bnstate, w, q, M, N, K, stat_partials, dt_q, w_transposed, stream);
 }
-// ... and its weight gradient dw[K][N] = ReLU6(BN(d))^T [K][M] * g[M][N] (fp32 result; g bf16)
 extern "C" int crnn_pwconv_bnrelu6_wgrad(const void* d, const float* in_bnstate, const void* g, float* dw, long M, int N, int K,
                                          float* scratch, size_t scratch_bytes, hipStream_t stream) {
-  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
-  return gemm_bf16_impl(2, d, g, dw, K, N, (int)M, K, N, N, nullptr, 0, 0, 0, scratch, scratch_bytes, CRNN_BF16, CRNN_BF16, CRNN_F32, nullptr, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K);
+  return pwconv_bnrelu6_wgrad(crnn_tile::PRODUCT_BF16, CRNN_BF16, d, in_bnstate, g, dw, M, N, K, scratch, scratch_bytes, stream);
 }
-// Parity mode (fp32 tensors, three-plane products): the same two GEMMs fed by the PRE-BatchNorm depthwise output d [M][K] fp32 -- the staging waves of
-// the three-plane kernel apply ReLU6(d * scale[ch] + shift[ch]) (the arithmetic of crnn_bn_act_pool_drop_ex, bit for bit) to the raw items before the
-// plane split, so the activated tensor is never written.  Results equal crnn_bn_act_pool_drop_ex + crnn_pwconv_fwd(bf16_products = 2) / crnn_gemm_f32x3
-// mode 2 bit for bit.  w [K][N] fp32 (K <= 512); -3 for shapes outside the kernel's rules.
+// Parity mode (fp32 tensors, plane products): the staging waves of the plane kernel apply ReLU6(d * scale[ch] + shift[ch]) (the arithmetic of
+// crnn_bn_act_pool_drop_ex, bit for bit) to the raw items before the plane split.  Results equal crnn_bn_act_pool_drop_ex + crnn_pwconv_fwd(bf16_products = 2 | 3) /
+// crnn_gemm_f32x3 | crnn_gemm_f32x2 mode 2 bit for bit.  w [K][N] fp32 (K <= 512); -3 for shapes outside the kernel's rules.
+// f32x2: two planes (hi*hi + hi*mid + mid*hi: 16 significant bits per factor; crnn_gemm_f32x2_bnstats)
 extern "C" int crnn_pwconv_bnrelu6_fwd_f32x3(const float* d, const float* in_bnstate, const float* w, float* q, long M, int N, int K,
                                              float* stat_partials, hipStream_t stream) {
-  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
-  return gemm_bf16_impl(0, d, w, q, (int)M, N, K, K, N, N, nullptr, 0, 0, 0, nullptr, 0, CRNN_F32, CRNN_F32, CRNN_F32, stat_partials, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true);
+  return pwconv_bnrelu6_fwd(crnn_tile::PRODUCT_PLANES3, CRNN_F32, d, in_bnstate, w, q, M, N, K, stat_partials, CRNN_F32, 0, stream);
 }
-// Two-plane forms of the two entry points below / above (hi*hi + hi*mid + mid*hi: 16 significant bits per factor; crnn_gemm_f32x2_bnstats)
 extern "C" int crnn_pwconv_bnrelu6_fwd_f32x2(const float* d, const float* in_bnstate, const float* w, float* q, long M, int N, int K,
                                              float* stat_partials, hipStream_t stream) {
-  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
-  return gemm_bf16_impl(0, d, w, q, (int)M, N, K, K, N, N, nullptr, 0, 0, 0, nullptr, 0, CRNN_F32, CRNN_F32, CRNN_F32, stat_partials, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true, nullptr, 2);
-}
-extern "C" int crnn_pwconv_bnrelu6_wgrad_f32x2(const float* d, const float* in_bnstate, const float* g, float* dw, long M, int N, int K,
-                                               float* scratch, size_t scratch_bytes, hipStream_t stream) {
-  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
-  return gemm_bf16_impl(2, d, g, dw, K, N, (int)M, K, N, N, nullptr, 0, 0, 0, scratch, scratch_bytes, CRNN_F32, CRNN_F32, CRNN_F32, nullptr, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true, nullptr, 2);
+  return pwconv_bnrelu6_fwd(crnn_tile::PRODUCT_PLANES2, CRNN_F32, d, in_bnstate, w, q, M, N, K, stat_partials, CRNN_F32, 0, stream);
 }
 extern "C" int crnn_pwconv_bnrelu6_wgrad_f32x3(const float* d, const float* in_bnstate, const float* g, float* dw, long M, int N, int K,
                                                float* scratch, size_t scratch_bytes, hipStream_t stream) {
-  if (M <= 0 || M > 0x7fffffffL || !in_bnstate) return CRNN_ERR_ARG;
-  return gemm_bf16_impl(2, d, g, dw, K, N, (int)M, K, N, N, nullptr, 0, 0, 0, scratch, scratch_bytes, CRNN_F32, CRNN_F32, CRNN_F32, nullptr, stream,
-                        nullptr, nullptr, in_bnstate + 2L * K, in_bnstate + 3L * K, true);
+  return pwconv_bnrelu6_wgrad(crnn_tile::PRODUCT_PLANES3, CRNN_F32, d, in_bnstate, g, dw, M, N, K, scratch, scratch_bytes, stream);
+}
+extern "C" int crnn_pwconv_bnrelu6_wgrad_f32x2(const float* d, const float* in_bnstate, const float* g, float* dw, long M, int N, int K,
+                                               float* scratch, size_t scratch_bytes, hipStream_t stream) {
+  return pwconv_bnrelu6_wgrad(crnn_tile::PRODUCT_PLANES2, CRNN_F32, d, in_bnstate, g, dw, M, N, K, scratch, scratch_bytes, stream);
 }

@@ -4,7 +4,7 @@
 // plain forward product.  M is ~10^5..10^6 rows, K and N are 64..512: the product is HBM-bound (arithmetic intensity
 // 43..256 FLOP/B), so the design goal is to keep the pixel stream in flight all the time, not MFMA throughput.
 //
-// What the tile-per-workgroup kernel (gemm_bf16.inc) loses on these shapes -- measured by ablation (scripts/gemm_ablate.py):
+// What the tile-per-workgroup kernel (gemm_bf16.hip) loses on these shapes -- measured by ablation (timing builds up to commit 137e5be; profiles/r02_gemm_ablate.txt):
 // with loads, MFMAs and stores all removed it still needs 45-60 % of its time, i.e. each tile is a serial chain
 // "wait for the first loads -> LDS -> barrier -> ... -> LDS-staged epilogue" and three resident workgroups per CU do not
 // cover it (~25 KB of pixel rows in flight per CU against the ~50 KB that 8 TB/s x ~2.5 us of latency need).  Here:
@@ -22,7 +22,7 @@
 //     holds 4 consecutive output channels of ONE pixel per register group, v_permlane32_swap pairs two groups into 8
 //     consecutive channels, and the result goes out as 16-byte stores straight from the accumulators -- no LDS
 //     staging, no barrier in the epilogue.
-// Numerics: the same MFMA, the same k order (64-k chunks, 16-k steps) as gemm_bf16.inc.
+// Numerics: the same MFMA, the same k order (64-k chunks, 16-k steps) as gemm_bf16.hip.
 #include "common.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));

@@ -2,7 +2,7 @@
 //     da[M][N] = dq[M][K] . W[N][K]^T     + the statistics pass of BatchNorm-1's backward (sum gy, sum gy * xhat)   [+ the planes of a = ReLU6(BN1(d))]
 // dq arrives as bf16 PLANES [planes][M][K] (hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid): the words of common.h crnn_split3_pair), written once
 // by the kernel that produces dq (BatchNorm-2's backward) -- two planes are the bytes of the fp32 tensor they replace.  The kernels this replaces
-// (gemm_bf16.inc gemm_x3p_kernel, gemm_wres3.hip) load fp32 dq, split it in their staging / IO waves once per 128- or 64-channel slice of the result (four to
+// (gemm_planes.hip gemm_x3p_kernel, gemm_wres3.hip) load fp32 dq, split it in their staging / IO waves once per 128- or 64-channel slice of the result (four to
 // eight times per element at N = 512) and were bound by exactly that: the IO side alone 335 us at K = N = 512 against 163 us for the MFMA side
 // (profiles/r06_wres3_ablate.txt).  Here nothing is split in the GEMM and nothing passes through registers on the way in:
 //   * a workgroup is FOUR waves, one per SIMD, each with the whole register file of its SIMD (up to 512 registers): wave w keeps the planes of the 32 x K block

@@ -1,7 +1,7 @@
 // Pixel-streaming weight gradient of a pointwise (1x1) convolution whose input is the PRE-BatchNorm depthwise output
 // (utils.py:44-49, training backward):
 //     dW[K][N] = ReLU6(BN1(d))^T [K][M] . g[M][N]        d, g bf16 (NHWC rows), dW fp32, K = channels in, N = channels out
-// The reduction runs over the M = B*H*W pixels (10^5..10^6), the result is at most 512 x 512.  The tile kernel (gemm_bf16.inc,
+// The reduction runs over the M = B*H*W pixels (10^5..10^6), the result is at most 512 x 512.  The tile kernel (gemm_bf16.hip,
 // mode 2) runs this as output tiles x ~48 reduction ranges with one register-staged k-chunk in flight per workgroup: every
 // 64-pixel chunk costs it a full load round trip (2.8 us per chunk for 0.25 us of MFMAs) -- it ingests ~13 B/clk/CU where the
 // L2 can deliver three times that.  Here the same decomposition is organised as a stream:
@@ -58,7 +58,7 @@ __device__ __forceinline__ unsigned wg_bnrelu6_pair(unsigned w, f32x2_t s, f32x2
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
 }
 
-// fragment = the 8 bf16 (k = 16 ks + 8 half .. +7) of tile row r0 + l31, from a k-major stage (as gemm_bf16.inc read_frag_h<true>)
+// fragment = the 8 bf16 (k = 16 ks + 8 half .. +7) of tile row r0 + l31, from a k-major stage (as gemm_tile.h read_frag_h<true>)
 __device__ __forceinline__ bf16x8_t wg_frag(const unsigned char* Xs, int r0, int ks, int half, int l31) {
   const int li = l31 & 15;
   const unsigned short* X = reinterpret_cast<const unsigned short*>(Xs) + (ks * 16 + 8 * half + (li >> 2)) * kLd + r0 + (l31 & 16) + (li & 3) * 4;

@@ -1,7 +1,7 @@
 // Pixel-streaming weight gradient of a pointwise (1x1) convolution in the PARITY mode (utils.py:44-49, training backward; fp32 tensors):
 //     dW[K][N] = ReLU6(BN1(d))^T [K][M] . g[M][N]      d [M][K], g [M][N] fp32 (NHWC rows), dW fp32, K = channels in, N = channels out
 // with two bf16 planes per operand and the three products hi*hi + hi*mid + mid*hi (16 significant bits per factor: the parity mode's default backward
-// precision, crnn_gemm_f32x2 / include/crnn_mi355x.h).  The tile kernel (gemm_bf16.inc: gemm_x3p_kernel mode 2) runs this as 128 x 128 output tiles x ~32
+// precision, crnn_gemm_f32x2 / include/crnn_mi355x.h).  The tile kernel (gemm_planes.hip: gemm_x3p_kernel mode 2) runs this as 128 x 128 output tiles x ~32
 // reduction ranges, two workgroups per CU, 16 pixels per stage and barrier: 202 us at K = N = 512 against 98 us of fp32 traffic and 75 us of MFMAs.  Here the
 // bf16 mode's stream (gemm_wgrad.hip: pw_wgrad_stream_kernel) is carried over to plane operands:
 //   * a workgroup (512 threads) owns one 128 x 128 output tile over a contiguous range of 32-pixel chunks; the 4 MFMA waves (2 x 2, 64 x 64 each: 4 accumulator
@@ -46,7 +46,7 @@ constexpr int kRing3 = W3G_RING;              // LDS stages (2: 80 KiB, two work
 constexpr int kD3 = W3G_D;                    // chunks in flight in the IO waves' registers
 constexpr int kLead3 = kRing3 - 1;            // stage stored after barrier s: s + kLead3
 
-// fragment = the 8 bf16 (k = 16 ks + 8 half .. +7) of tile row r0 + l31, from a k-major plane (as gemm_bf16.inc read_frag_h<true>)
+// fragment = the 8 bf16 (k = 16 ks + 8 half .. +7) of tile row r0 + l31, from a k-major plane (as gemm_tile.h read_frag_h<true>)
 __device__ __forceinline__ bf16x8_t wg3_frag(const unsigned char* Xs, int r0, int ks, int half, int l31) {
   const int li = l31 & 15;
   const unsigned short* X = reinterpret_cast<const unsigned short*>(Xs) + (ks * 16 + 8 * half + (li >> 2)) * kLd3 + r0 + (l31 & 16) + (li & 3) * 4;

@@ -23,7 +23,7 @@
 //     first fragments of the next stage before it reaches the next barrier and the MFMA pipe does not drain at stage edges.
 // LDS rows are 128 B unpadded, 16-byte chunk c of row r at position c ^ ((r >> 1) & 7) (applied to the per-lane global
 // address; the LDS image stays lane-linear): conflict-free ds_read_b128 fragment reads.
-// Numerics: the same MFMA and the same k order (64-k chunks ascending, 16-k steps ascending) as gemm_nt.hip / gemm_bf16.inc --
+// Numerics: the same MFMA and the same k order (64-k chunks ascending, 16-k steps ascending) as gemm_nt.hip / gemm_bf16.hip --
 // results are bit-identical.
 #include "common.h"
 
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(384 + 64 * NLW) void gemm_wres_kernel(WresParams p)
 //     q[M][N] = ReLU6(BN1(d))[M][K] . W[N][K]^T,   plus the column sums / sums of squares of q as stored (BatchNorm-2 statistics).
 // Same MFMA role as above; the producers cannot be LDS-DMA (the operand is transformed on the way), so the four other waves
 // are IO waves: each loads a quarter of every 16-KiB stage into registers three stages ahead (48 KiB per CU in flight), applies
-// ReLU6(x * scale[ch] + shift[ch]) -> bf16 (the arithmetic of bn_act_pool_drop_kernel / gemm_bf16.inc's prologue, bit for bit)
+// ReLU6(x * scale[ch] + shift[ch]) -> bf16 (the arithmetic of bn_act_pool_drop_kernel / gemm_bf16.hip's prologue, bit for bit)
 // and writes the chunk to its swizzled ring position; between stages it drains a piece of the previous stripe's staged bf16 tile
 // to global memory and accumulates that piece's column sums and sums of squares in registers over the whole launch.  One
 // partial-statistics row per IO wave and stripe lane, written once at the end: [Q * 8 * 4][2][N] instead of [M / 128][2][N].

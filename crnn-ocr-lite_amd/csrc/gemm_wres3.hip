@@ -2,7 +2,7 @@
 //     forward         q[M][N]  = ReLU6(BN1(d))[M][K] . W[K][N]            + column sums / sums of squares of q (BatchNorm-2 statistics)
 //     data gradient   da[M][N] = dq[M][K] . W[N][K]^T                     + the statistics pass of BatchNorm-1's backward (sum gy, sum gy * xhat)
 // fp32 tensors, fp32-accurate products from bf16 planes on v_mfma_f32_32x32x16_bf16 (three planes per operand and six products per k-step, or two
-// planes and three products: common.h crnn_split3_pair, gemm_bf16.inc gemm_x3p_kernel).  The tile kernel these replace re-loads a 128 x K fp32 slab
+// planes and three products: common.h crnn_split3_pair, gemm_planes.hip gemm_x3p_kernel).  The tile kernel these replace re-loads a 128 x K fp32 slab
 // of W out of L2 for every 128-pixel tile, splits it into planes again and reads it from LDS once per MFMA; its staging waves spend as much on W as
 // on the pixels.  Here the design of the bf16 mode's gemm_wres_fwd_kernel is carried over:
 //   * a workgroup owns a SLICE of NS = 128 / KHN output channels for its whole life: each of its four MFMA waves keeps the bf16 planes of a
