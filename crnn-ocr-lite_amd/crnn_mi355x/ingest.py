@@ -117,6 +117,29 @@ def pack_arena(pages, out=None):
     return arena, offs
 
 
+class PageArena:
+    """Pages on the device: `dev` is the uint8 arena (pack_arena's layout), `pages` / `offsets` what it holds.  One upload serves the word
+    detector (detect.WordDetector) and any number of crop launches (DeviceIngest.crops(arena=...)); the page-locked source of the copy
+    lives as long as the arena."""
+
+    def __init__(self, pages, offsets, nbytes, host, dev):
+        self.pages, self.offsets, self.nbytes, self.host, self.dev = pages, offsets, nbytes, host, dev
+
+
+def upload_pages(pages, device):
+    """list of (H, W) uint8 arrays -> PageArena on `device`: one page-locked buffer, one asynchronous copy on the current stream."""
+    import torch
+    pages = [np.ascontiguousarray(pg) for pg in pages]
+    offs, nbytes = arena_layout(pages)
+    device = torch.device(device)
+    with torch.cuda.device(device):
+        host = torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
+        pack_arena(pages, out=host.numpy())
+        dev = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+        dev.copy_(host, non_blocking=True)
+    return PageArena(pages, offs, nbytes, host, dev)
+
+
 def build_table(pages, offsets, page_index, rects, plans, img_size, out=None):
     """The crnn_crop_item table of n crops: page_index (n,), rects (n, 4) = r0, r1, c0, c1, plans = (upscale, s0, s1, b0, b1, p0, p1) arrays
     as plan_crops returns them.  The scale factors are n_in / float(n_out) in Python arithmetic, as data._linear_taps computes them."""
@@ -178,15 +201,35 @@ class DeviceIngest:
             s["np"] = s["host"].numpy()
         return s
 
-    def crops(self, pages, page_index, rects, plans, batch=None, return_u8=False):
+    def upload(self, pages):
+        """Pages -> PageArena on this ingest's device, for crops(..., arena=) and WordDetector.detect(arena=): the pages go up once, and
+        each crop launch afterwards uploads its box table only."""
+        return upload_pages(pages, self.device)
+
+    def crops(self, pages, page_index, rects, plans, batch=None, return_u8=False, arena=None):
         """pages: list of (H, W) uint8 arrays; crop k is pages[page_index[k]][r0:r1, c0:c1] with rects[k] = (r0, r1, c0, c1), placed as plans
-        (plan_crops' tuple of arrays) says.  -> device fp32 (batch or n, imgh, imgw, 1), rows past n zero [, the uint8 pixels before the table]."""
+        (plan_crops' tuple of arrays) says.  -> device fp32 (batch or n, imgh, imgw, 1), rows past n zero [, the uint8 pixels before the table].
+        arena: a PageArena from `upload` -- its pages are used (`pages` may be None) and only the table is copied."""
         import torch
         from .engine import _ptr, _stream
         n = len(page_index)
         B = n if batch is None else int(batch)
         if B < 1 or n > B:
             raise ValueError("%d crops do not fit a batch of %d" % (n, B))
+        if arena is not None:
+            nbytes = n * ITEM_DTYPE.itemsize
+            with torch.cuda.device(self.device):
+                s = self._slot(max(nbytes, 1))
+                build_table(arena.pages, arena.offsets, page_index, rects, plans, self.img_size, out=s["np"][:nbytes].view(ITEM_DTYPE))
+                if nbytes:
+                    s["dev"][:nbytes].copy_(s["host"][:nbytes], non_blocking=True)
+                    s["copied"].record(torch.cuda.current_stream())
+                out = torch.empty((B, self.T0, self.T1, 1), dtype=torch.float32, device=self.device)
+                u8 = torch.empty((B, self.T0, self.T1), dtype=torch.uint8, device=self.device) if return_u8 else None
+                native.check(self.lib.crnn_ingest_crops(ctypes.c_void_p(arena.dev.data_ptr()), arena.nbytes, ctypes.c_void_p(s["host"].data_ptr()),
+                                                        ctypes.c_void_p(s["dev"].data_ptr()), n, B, self.T0, self.T1, _ptr(self.table), _ptr(out),
+                                                        _ptr(u8), _stream()), "ingest_crops")
+            return (out, u8) if return_u8 else out
         pages = [np.ascontiguousarray(pg) for pg in pages]
         offs, arena_bytes = arena_layout(pages)
         total = arena_bytes + n * ITEM_DTYPE.itemsize

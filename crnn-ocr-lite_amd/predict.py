@@ -7,7 +7,10 @@ and prediction.csv.  --device_score (with --validate) keeps decoding and scoring
 --align (with --result_path) aligns every prediction to its own softmax map (crnn_mi355x.align) and writes alignment.csv: per character its frames
 on the network's time axis and its log-probability.
 --lm FILE decodes with a character language model in the beam search (crnn_mi355x.lm): FILE is a saved CharLM (.npz) or a word list to count one from.
---nbest K (with --result_path) also writes nbest.csv: per image the K best paths of the beam with their scores."""
+--nbest K (with --result_path) also writes nbest.csv: per image the K best paths of the beam with their scores.
+--detect treats every image under --image_path as a page and finds its word boxes itself (crnn_mi355x.detect: threshold, smearing, connected
+components) instead of reading them from --boxes; with --device_ingest the boxes are found on the GPU, on the same upload the crops are cut from.
+prediction.csv then carries every box next to its prediction."""
 import argparse
 import os
 import pickle
@@ -56,7 +59,27 @@ def build_parser():
     parser.add_argument('--lm_bonus', type=float, default=0.0, help='beta: bonus per character (a placeholder default: tune it)')
     parser.add_argument('--nbest', type=int, default=None,
                         help='with --result_path: also write nbest.csv -- file, rank, text and score of the K best paths of the beam search')
+    parser.add_argument('--detect', action='store_true',
+                        help='every image under --image_path is a page: find its word boxes (threshold, run-length smearing, connected components) '
+                             'instead of reading --boxes; with --device_ingest on the GPU, sharing the page upload with the crops')
+    parser.add_argument('--detect_gap_x', type=int, default=None, help='with --detect: background runs up to this long inside a row are bridged, 0..64 (the default is a placeholder: tune it)')
+    parser.add_argument('--detect_gap_y', type=int, default=None, help='with --detect: the same down the columns, 0..16 (a placeholder default: tune it)')
+    parser.add_argument('--detect_min_w', type=int, default=None, help='with --detect: narrowest box kept (a placeholder default: tune it)')
+    parser.add_argument('--detect_min_h', type=int, default=None, help='with --detect: lowest box kept (a placeholder default: tune it)')
+    parser.add_argument('--detect_min_ink', type=int, default=None, help='with --detect: fewest ink pixels of a box kept (a placeholder default: tune it)')
+    parser.add_argument('--detect_threshold', type=int, default=None, help='with --detect: ink threshold 0..254, or -1 for Otsu per page (the default)')
+    parser.add_argument('--detect_cap', type=int, default=None, help='with --detect: most boxes kept per page (default 1024)')
     return parser
+
+
+PAGES_PER_UPLOAD = 16                                        # --detect --device_ingest: pages per arena
+DETECT_CAP = 1024                                            # crnn_mi355x.detect.DEFAULTS["cap"]: the host path keeps what the device keeps
+DETECT_FLAGS = ("gap_x", "gap_y", "min_w", "min_h", "min_ink", "threshold", "cap")
+
+
+def detect_params(args):
+    """The --detect_* flags that were given -> keyword arguments of detect_words_host / WordDetector."""
+    return {k: getattr(args, "detect_" + k) for k in DETECT_FLAGS if getattr(args, "detect_" + k) is not None}
 
 
 def parse_args(argv=None):
@@ -86,7 +109,44 @@ def parse_args(argv=None):
         parser.error("--nbest reads the softmax maps, which --device_score never materialises: use one or the other")
     if args.nbest is not None and not 1 <= args.nbest <= 64:
         parser.error("--nbest must be 1..64")
+    if args.detect and args.boxes is not None:
+        parser.error("--detect finds the boxes, --boxes reads them: use one or the other")
+    if args.detect and args.validate:
+        parser.error("--detect has no truth to validate against: it does not go with --validate")
+    if not args.detect and detect_params(args):
+        parser.error("the --detect_* flags tune --detect: they need it")
+    if args.detect:
+        from crnn_mi355x.detect import check_params, DEFAULTS
+        try:
+            check_params(dict(DEFAULTS, **detect_params(args)))
+        except ValueError as e:
+            parser.error(str(e))
     return args
+
+
+def detect_on_device(args, names, model, img_size, U):
+    """--detect --device_ingest: groups of pages go up once; the detector finds the boxes in the arena and the crops are cut from the same
+    arena, batch by batch -> ({page: boxes}, softmax maps of every box in order).  Pages without boxes are left out."""
+    det = U.WordDetector(**detect_params(args))
+    ing = U.DeviceIngest(img_size, normed=True)
+    bboxs, maps = {}, []
+
+    def flush(group):
+        pages = [U.read_img(n) for n in group]
+        arena = ing.upload(pages)
+        index, rects = [], []
+        for k, (name, boxes) in enumerate(zip(group, det.boxes(None, arena=arena))):
+            if boxes:
+                bboxs[name] = boxes
+                index += [k] * len(boxes)
+                rects += [U.box_slices(b, pages[k].shape) for b in boxes]
+        for i in range(0, len(index), args.batch_size):
+            part = slice(i, i + args.batch_size)
+            x = ing.crops(None, index[part], rects[part], ing.plan(rects[part]), batch=args.batch_size, arena=arena)
+            maps.append(model.predict_on_batch(x)[:len(index[part])])
+    for i in range(0, len(names), PAGES_PER_UPLOAD):
+        flush(names[i:i + PAGES_PER_UPLOAD])
+    return bboxs, (np.concatenate(maps, 0) if maps else None)
 
 
 def main(argv=None):
@@ -142,7 +202,25 @@ def main(argv=None):
         reader = U.Readf(img_size=img_size, normed=True, batch_size=args.batch_size, transform_p=0., classes=classes, max_len=args.max_len, workers=args.workers)
     length = len(fnames)
     bboxs = {}
-    if args.boxes is not None:
+    predicted = None
+    if args.detect:
+        fnames = sorted(str(f) for f in walk())                   # every image is a page; no halving of the page set
+        if args.device_ingest:
+            bboxs, predicted = detect_on_device(args, fnames, model, img_size, U)
+        else:
+            for name in fnames:
+                rects, _ = U.detect_words_host(U.read_img(name), **dict({"cap": DETECT_CAP}, **detect_params(args)))
+                if len(rects):
+                    bboxs[name] = [(None, int(r[0]), int(r[2]), int(r[1]), int(r[3])) for r in rects[U.reading_order(rects)]]
+        empty = [f for f in fnames if f not in bboxs]
+        if empty:
+            print(" [INFO] %d page(s) without a word box left out: %s " % (len(empty), ", ".join(os.path.basename(f) for f in empty[:5])))
+        if not bboxs:
+            raise SystemExit(" [ERROR] --detect found no word box on any of the %d pages" % len(fnames))
+        length = sum(len(v) for v in bboxs.values())
+        fnames = [f for f in fnames if f in bboxs]
+        print(" [INFO] Detected %d word boxes on %d pages " % (length, len(fnames)))
+    elif args.boxes is not None:
         bboxs = pickle.load(open(args.boxes, "rb"))          # {image: [(word|None, x0, y0, x1, y1), ...]}
         half = len(bboxs) // 2
         bboxs = {os.path.join(args.image_path, k): v for i, (k, v) in enumerate(bboxs.items()) if i <= half}
@@ -150,7 +228,7 @@ def main(argv=None):
         fnames = list(bboxs.keys())
         if args.validate:
             y_true = np.array([reader.make_target(el[0]) for v in bboxs.values() for el in v], dtype=object)
-    else:
+    elif not args.detect:
         y_true = reader.get_labels(fnames)
     steps = -(-length // args.batch_size)
     print(" [INFO] Predicting... ")
@@ -163,7 +241,8 @@ def main(argv=None):
         predicted_text = score.texts(decoder)
         print(" [INFO] %d predictions decoded in %s sec. " % (steps * args.batch_size, round(time.time() - start, 2)))
     else:
-        predicted = model.predict_generator(reader.run_generator(fnames, bboxs=bboxs, downsample_factor=2), steps=steps)
+        if predicted is None:                                # (--detect --device_ingest made the maps on the upload it found the boxes in)
+            predicted = model.predict_generator(reader.run_generator(fnames, bboxs=bboxs, downsample_factor=2), steps=steps)
         print(" [INFO] %d images processed in %s sec. " % (len(fnames), round(time.time() - start, 2)))
         start = time.time()
         predicted_text = decoder.decode(predicted)[:length]
@@ -173,7 +252,11 @@ def main(argv=None):
         if len(fnames) != len(predicted_text):
             fnames = [f for f in bboxs for _ in range(len(bboxs[f]))]
         out_name = os.path.join(args.result_path, "prediction.csv")
-        pd.DataFrame({"fname": fnames, "prediction": predicted_text}).to_csv(out_name)
+        table = {"fname": fnames, "prediction": predicted_text}
+        if args.detect:                                      # the box of every row, as page[r0:r1, c0:c1]
+            flat = [b for f in bboxs for b in bboxs[f]]
+            table.update(r0=[b[1] for b in flat], c0=[b[2] for b in flat], r1=[b[3] for b in flat], c1=[b[4] for b in flat])
+        pd.DataFrame(table).to_csv(out_name)
         print(" [INFO] Prediction example: \n", predicted_text[:10])
         print(" [INFO] Result store in: ", out_name)
         if args.nbest is not None:

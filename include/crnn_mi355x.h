@@ -316,6 +316,40 @@ typedef struct {
 int crnn_ingest_crops(const void* arena, long arena_bytes, const crnn_crop_item* items, const crnn_crop_item* items_dev, int n, int batch, int imgh, int imgw,
                       const float* table, float* out, void* out_u8, crnn_stream_t stream);
 
+/* ---- word detection: page images -> the word boxes crnn_ingest_crops takes (csrc/detect.hip; the same rule in NumPy: crnn_mi355x.detect) ---- */
+/* A page: a row-major uint8 image at byte `page_off` of the arena, 1 <= rows, cols <= 4096 -- the page fields of crnn_crop_item. */
+typedef struct { long page_off; int rows, cols, stride; } crnn_page_item;
+/* threshold 0..254, or -1 for Otsu per page; polarity 0 auto / 1 dark ink / 2 bright ink; 0 <= gap_x <= 64, 0 <= gap_y <= 16; the filter's
+ * bounds >= 0 (max_w, max_h: 0 = no upper bound); cap >= 1 rows of output per page. */
+typedef struct { int threshold, polarity, gap_x, gap_y, min_w, min_h, min_ink, max_w, max_h, cap; } crnn_detect_params;
+#define CRNN_DETECT_TILE_R 32   /* the labelling tile: components are labelled per tile in LDS and united across tile borders afterwards */
+#define CRNN_DETECT_TILE_C 64
+/* The rule, per page (integers throughout; Otsu's score is four float64 operations in a fixed order, no fused multiply-add):
+ * THRESHOLD t: the given one, or Otsu over the 256-bin histogram h, N = sum h, S = sum v h: for t = 0..254 in order, w0 = sum_{v<=t} h,
+ *   s0 = sum_{v<=t} v h, w1 = N - w0; t with w0 == 0 or w1 == 0 is skipped; d = s0 w1 - (S - s0) w0 (int64), score = ((double)d / (double)w0) *
+ *   ((double)d / (double)w1); the first t of the strictly greatest score.  No admissible t (a constant page): no ink, 0 boxes, threshold -1.
+ * POLARITY: 1: ink is v <= t; 2: ink is v > t; 0: whichever of the two sides has fewer pixels, the dark side on a tie (ink_is_dark of a page
+ *   without admissible t: polarity != 2).
+ * SMEAR: in each row a maximal run of L non-ink pixels with an ink pixel immediately on both sides becomes set when 1 <= L <= gap_x; runs
+ *   that touch the page edge are never filled.  Then the same per column with gap_y, on the result of the horizontal smear.
+ * COMPONENTS: 8-connected in the smeared mask.  A component's rectangle r0, r1, c0, c1 (upper bounds exclusive: page[r0:r1, c0:c1], the
+ *   convention of crnn_crop_item) is that of its pixels -- equal to that of its original ink, smearing never extends past ink -- and `ink` is its
+ *   number of original ink pixels, the fill not counted.
+ * FILTER: kept when c1 - c0 >= min_w, r1 - r0 >= min_h, ink >= min_ink, c1 - c0 <= max_w (max_w > 0), r1 - r0 <= max_h (max_h > 0).
+ * ORDER: ascending row-major index of the component's first pixel.  found = the number that pass, kept = min(found, cap): the first `cap` in
+ *   that order go to rects [P][cap][5] int32 = r0 r1 c0 c1 ink, rows past kept hold -1; info [P][4] int32 = found kept threshold ink_is_dark.
+ * Integer atomics only (min on labels; min, max, add on box records), roots are minimum indices: two calls agree bit for bit.
+ * pages is the table in HOST memory, validated before anything is launched; pages_dev the same P entries in device memory (the kernels clamp
+ * every read into the page and the arena on their own, and a page whose device entry does not fit the validated layout yields found = 0).
+ * ws: crnn_detect_workspace_bytes(pages, P, prm) bytes, 16-byte aligned, no zeroing owed: P * 1088 + ~4 B per pixel of labels + ~6 B per
+ * pixel of box records + 4 B per row (0 for a table or parameters that crnn_detect_words refuses).
+ * -2, nothing launched, outputs untouched: a null pointer, P < 0, rows or cols < 1, a page outside the arena, stride < cols, a parameter outside
+ * its range, cap < 1, a short or misaligned workspace.  -3: a page above 4096 in either direction, more than 2^31 pixels in one call, or
+ * P > 65535.  P == 0 launches nothing. */
+size_t crnn_detect_workspace_bytes(const crnn_page_item* pages, int P, const crnn_detect_params* prm);
+int crnn_detect_words(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int P,
+                      const crnn_detect_params* prm, int* rects, int* info, void* ws, size_t ws_bytes, crnn_stream_t stream);
+
 /* ---- individual operators (unit-tested one by one; the drivers above chain them) --------------------------- */
 /* mode 0: C=A[M,K]*B[K,N]; 1: C=A[M,K]*Bt[N,K]^T; 2: C=At[K,M]^T*B[K,N].  bias[N]|NULL, act 0|1(relu),
  * accumulate: C+=, permP: out_row=(m%P)*(M/P)+m/P (0=off), scratch: split-reduction partials (may be NULL) */
