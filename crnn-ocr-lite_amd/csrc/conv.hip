@@ -7,12 +7,10 @@
 //   generic column reductions and the second-stage (double) reductions.
 // All kernels are HBM-bandwidth bound; the pointwise 1x1 convs go through gemm.hip.
 #include "common.h"
-#include <stdlib.h>
+#include "stream_ops.h"
 
 #define BN_EPS 1e-3f
-#ifndef DW_NT
-#define DW_NT 256   // threads per depthwise workgroup
-#endif
+constexpr int DW_NT = 256;   // threads per depthwise workgroup
 
 // VEC consecutive channels of one pixel, widened to fp32 (VEC = 1, 4 or 8; 8 = one 16-byte access of bf16 storage)
 template <int VEC>
@@ -22,12 +20,8 @@ struct VecF { float v[VEC]; };
 // tensor for the LAST time in the step (or for the last time before the other half of the step) loads it nontemporally so that it does not push out what the
 // next kernel is about to read (its own output, the tensors still to be re-read).  Same values, same order: results bit-identical.  Measured on the bf16s step
 // (profiles/r05_nt_loads_ab.txt): BatchNorm-backward apply pass -0.03 ms, depthwise-stage backward -0.07 ms, together with the forward passes -0.2 ms.
-#ifndef CRNN_NT_BN_BWD2
-#define CRNN_NT_BN_BWD2 1   // BatchNorm backward, apply pass: q and g are read for the last time
-#endif
-#ifndef CRNN_NT_BN_ACT
-#define CRNN_NT_BN_ACT 1    // BatchNorm-2 + ReLU6 + pool + dropout (forward): q is not read again before the backward pass
-#endif
+constexpr bool kNtBnBwd2 = true;   // BatchNorm backward, apply pass: q and g are read for the last time (profiles/r05_nt_loads_ab.txt)
+constexpr bool kNtBnAct = true;    // BatchNorm-2 + ReLU6 + pool + dropout (forward): q is not read again before the backward pass (same file)
 template <int VEC, typename T>
 __device__ __forceinline__ VecF<VEC> vload_nt(const T* p);
 template <int VEC, bool NT, typename T>
@@ -69,37 +63,20 @@ template <> struct VecMax<bf16_t> { static const int value = 8; };
 // mode 0: out = conv(x, k) (flip=1 -> taps flipped = data gradient), optional stats partials
 // mode 1: weight gradient partials: dk[tap][c] += x[shifted] * g[center]
 // ---------------------------------------------------------------------------------------------
-// raw channel vector of the storage type (what sits in HBM and in the LDS tile): 4 fp32 (16 B) or DW_BF16_VN bf16
-#ifndef DW_BF16_VN
-#define DW_BF16_VN 4
-#endif
+// raw channel vector of the storage type (what sits in HBM and in the LDS tile): 4 fp32 (16 B) or 4 bf16 (8 B; 8 bf16 per lane was built once and not adopted, its figures were not kept)
 template <typename T> struct RawV;
 template <> struct RawV<float> { typedef float4 type; static const int N = 4; };
-#if DW_BF16_VN == 8
-template <> struct RawV<bf16_t> { typedef uint4 type; static const int N = 8; };
-#else
 template <> struct RawV<bf16_t> { typedef uint2 type; static const int N = 4; };
-#endif
 template <typename V, typename T> __device__ __forceinline__ V ldraw(const T* p) { return *reinterpret_cast<const V*>(p); }
 __device__ __forceinline__ void widen(const float4& v, float (&f)[4]) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
 __device__ __forceinline__ void widen(const uint2& u, float (&f)[4]) {
   f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
   f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
 }
-__device__ __forceinline__ void widen(const uint4& u, float (&f)[8]) {
-  f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
-  f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-  f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
-  f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
-}
 __device__ __forceinline__ void zerov(float4& v) { v = make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ void zerov(uint2& v) { v = make_uint2(0u, 0u); }
-__device__ __forceinline__ void zerov(uint4& v) { v = make_uint4(0u, 0u, 0u, 0u); }
 __device__ __forceinline__ void narrow_store(float* p, const float (&f)[4]) { st4(p, make_float4(f[0], f[1], f[2], f[3])); }
 __device__ __forceinline__ void narrow_store(bf16_t* p, const float (&f)[4]) { st4(p, make_float4(f[0], f[1], f[2], f[3])); }
-__device__ __forceinline__ void narrow_store(bf16_t* p, const float (&f)[8]) {
-  *reinterpret_cast<uint4*>(p) = make_uint4(pack2_bf16(f[0], f[1]), pack2_bf16(f[2], f[3]), pack2_bf16(f[4], f[5]), pack2_bf16(f[6], f[7]));
-}
 // sum over the pixel-threads of a wave that share a channel lane (lanes l, l^CL, l^2CL, ...), fixed order
 template <int CL>
 __device__ __forceinline__ float pixlane_sum(float v) {
@@ -365,19 +342,16 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_c1_kernel(const float* __res
 // then balanced over the bands of H.
 struct DwTile { int TH, TW, nHb, nWb; size_t lds; };
 static DwTile dw_pick_tile(int H, int W) {
-  const int th_env = crnn_knob("CRNN_DW_TH", 0), tw_env = crnn_knob("CRNN_DW_TW", 0);   // tile overrides (experiment builds only)
   DwTile t;
   t.nWb = cdiv(W, 64);
   t.TW = cdiv(W, t.nWb);
-  if (tw_env > 0) t.TW = tw_env;
   t.nWb = cdiv(W, t.TW);
-  const int lds_env = crnn_knob("CRNN_DW_LDS", 49152);                                   // halo-tile budget in bytes
-  int thmax = (int)((size_t)lds_env / ((size_t)(t.TW + 2) * 128)) - 2;
+  const int lds_budget = 49152;                                                          // halo-tile budget in bytes
+  int thmax = (int)((size_t)lds_budget / ((size_t)(t.TW + 2) * 128)) - 2;
   if (thmax < 1) thmax = 1;
   if (thmax > H) thmax = H;
   int nb = cdiv(H, thmax);
   t.TH = cdiv(H, nb);
-  if (th_env > 0) t.TH = th_env;
   t.nHb = cdiv(H, t.TH);
   const size_t red = (size_t)(DW_NT / 64) * 9 * 64 * 4;  // weight-grad cross-wave reduction scratch (<= 64 channels per slab)
   size_t tile = (size_t)(t.TH + 2) * (t.TW + 2) * 128 + 128 * DW_PXB;   // + slack for the ragged last pixel group
@@ -756,7 +730,7 @@ __global__ void bn_act_pool_drop_kernel(const TI* __restrict__ x, const float* _
     const int cl = (int)(i % (IDX)CL); const IDX pix = i / (IDX)CL;
     VecF<VEC> m, s = vload<VEC>(sc + cl * VEC), t = vload<VEC>(sh + cl * VEC);
     if (ph * pw == 1) {
-      VecF<VEC> v = vload_s<VEC, (CRNN_NT_BN_ACT != 0)>(&x[(long)pix * C + cl * VEC]);
+      VecF<VEC> v = vload_s<VEC, kNtBnAct>(&x[(long)pix * C + cl * VEC]);
 #pragma unroll
       for (int e = 0; e < VEC; ++e) m.v[e] = relu6f(fmaf(v.v[e], s.v[e], t.v[e]));
     } else {
@@ -772,7 +746,7 @@ __global__ void bn_act_pool_drop_kernel(const TI* __restrict__ x, const float* _
         for (int ii = 0; ii < (PHT ? PHT : 1); ++ii)
 #pragma unroll
           for (int j = 0; j < (PWT ? PWT : 1); ++j) {
-            VecF<VEC> v = vload_s<VEC, (CRNN_NT_BN_ACT != 0)>(&x[base + ((long)ii * W + j) * C]);
+            VecF<VEC> v = vload_s<VEC, kNtBnAct>(&x[base + ((long)ii * W + j) * C]);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
               const float tt = fmaf(v.v[e], s.v[e], t.v[e]);
@@ -788,14 +762,14 @@ __global__ void bn_act_pool_drop_kernel(const TI* __restrict__ x, const float* _
         for (int ii = 0; ii < (PHT ? PHT : 1); ++ii)
 #pragma unroll
           for (int j = 0; j < (PWT ? PWT : 1); ++j) {
-            VecF<VEC> v = vload_s<VEC, (CRNN_NT_BN_ACT != 0)>(&x[base + ((long)ii * W + j) * C]);
+            VecF<VEC> v = vload_s<VEC, kNtBnAct>(&x[base + ((long)ii * W + j) * C]);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) m.v[e] = fmaxf(m.v[e], relu6f(fmaf(v.v[e], s.v[e], t.v[e])));
           }
       } else {
         for (int ii = 0; ii < ph; ++ii)
           for (int j = 0; j < pw; ++j) {
-            VecF<VEC> v = vload_s<VEC, (CRNN_NT_BN_ACT != 0)>(&x[base + ((long)ii * W + j) * C]);
+            VecF<VEC> v = vload_s<VEC, kNtBnAct>(&x[base + ((long)ii * W + j) * C]);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) m.v[e] = fmaxf(m.v[e], relu6f(fmaf(v.v[e], s.v[e], t.v[e])));
           }
@@ -902,17 +876,16 @@ __device__ __forceinline__ void bn_store_dx(const BnBwdArgsT<T>& a, T* dx, long 
 
 template <int VEC, typename T>
 __device__ __forceinline__ VecF<VEC> vload_nt(const T* p) {
-  typedef unsigned u32x4_nt __attribute__((ext_vector_type(4)));
   VecF<VEC> r;
   if constexpr (VEC == 8 && sizeof(T) == 2) {
-    const u32x4_nt u = __builtin_nontemporal_load(reinterpret_cast<const u32x4_nt*>(p));
+    const u32x4 u = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
 #pragma unroll
     for (int q = 0; q < 4; ++q) { r.v[2 * q] = __uint_as_float(u[q] << 16); r.v[2 * q + 1] = __uint_as_float(u[q] & 0xffff0000u); }
     return r;
   } else if constexpr (VEC % 4 == 0 && sizeof(T) == 4) {
 #pragma unroll
     for (int h = 0; h < VEC / 4; ++h) {
-      const u32x4_nt u = __builtin_nontemporal_load(reinterpret_cast<const u32x4_nt*>(p) + h);
+      const u32x4 u = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p) + h);
 #pragma unroll
       for (int q = 0; q < 4; ++q) r.v[4 * h + q] = __uint_as_float(u[q]);
     }
@@ -1004,22 +977,7 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(BnBwdArgsT<T> a, float* __r
         for (int e = 0; e < VEC; ++e) bn_bwd_pq(sc.v[e], c1.v[e], c2.v[e], mu.v[e], inv.v[e], Pc.v[e], Qc.v[e]);
       }
       long r = r0 + rt;
-#if CRNN_BNB_ROWS4
-      if (PASS == 1 && !POOL) {
-        for (; r + 3L * RT < r1; r += 4L * RT) {   // four rows in flight: 8 independent 16-byte loads per thread
-          VecF<VEC> xr[4], gr[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) xr[u] = vload<VEC>(&a.x[(r + u * RT) * a.C + c0]);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) gr[u] = bn_gy_vec<VEC, POOL, T>(a, r + u * RT, c0, xr[u], sc, sh, inv_keep);
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) { s.v[e] += gr[u].v[e]; q.v[e] = fmaf(gr[u].v[e], (xr[u].v[e] - mu.v[e]) * inv.v[e], q.v[e]); }
-        }
-      }
-#endif
-      constexpr bool NT = CRNN_NT_BN_BWD2 && PASS == 2;
+      constexpr bool NT = kNtBnBwd2 && PASS == 2;
       for (; r + RT < r1; r += 2L * RT) {   // two rows in flight (independent loads)
         VecF<VEC> xa = vload_s<VEC, NT>(&a.x[r * a.C + c0]);
         VecF<VEC> xb = vload_s<VEC, NT>(&a.x[(r + RT) * a.C + c0]);
@@ -1109,7 +1067,7 @@ __global__ __launch_bounds__(256) void bn_bwd_pool_kernel(BnBwdArgsT<T> a, float
       if (PASS == 2) { c1 = vload<VEC>(coef + c0i); c2 = vload<VEC>(coef + a.C + c0i); }
       // one pool window per step; pass 1 (reduce only) keeps two windows' loads in flight
       auto load_window = [&](long r, const Pos& p, VecF<VEC>& gv, VecF<VEC> (&xw)[4], long& xbase) {
-        constexpr bool NT = CRNN_NT_BN_BWD2 && PASS == 2;
+        constexpr bool NT = kNtBnBwd2 && PASS == 2;
         gv = vload_s<VEC, NT>(&a.g[r * a.C + c0i]);
         xbase = (((long)p.b * a.H + p.ho * ph) * a.W + p.wo * pw) * a.C + c0i;
 #pragma unroll
@@ -1250,17 +1208,13 @@ __global__ __launch_bounds__(RED_CH * RED_PL) void bn_bwd_finalize_kernel(const 
   }
 }
 
-// Chunking of the two BatchNorm-backward passes: rows per chunk = the largest power of two <= 512 that still yields CRNN_BNB_MINCHUNKS
+// Chunking of the two BatchNorm-backward passes: rows per chunk = the largest power of two <= 512 that still yields kBnbMinChunks
 // chunks.  256 (468 partial rows for the 52-row maps at batch 256, 1872 for the 104-row maps) measured best over 256 / 512 / 768 / 1024 /
 // 2048 (scripts/bnp1_bench.py): the statistics pass itself barely cares, the finalize that reads the partial rows halves; chunks of 1024
 // rows (936 workgroups) cost the 104-row maps 6 % in the step.
-#ifndef CRNN_BNB_MINCHUNKS
-#define CRNN_BNB_MINCHUNKS 256
-#endif
-#ifndef CRNN_BNB_ROWS4
-#define CRNN_BNB_ROWS4 1       // statistics pass without pooling: four rows (8 independent 16-byte loads) in flight per thread; 0 = two
-#endif
-static inline int bn_bwd_rows_per_chunk(long rows) { long r = 512; while (r > 16 && rows / r < CRNN_BNB_MINCHUNKS) r >>= 1; return (int)r; }
+constexpr int kBnbMinChunks = 256;
+// (a statistics pass with four rows in flight per thread sat behind a macro that was tested before it was defined: the library never contained it)
+static inline int bn_bwd_rows_per_chunk(long rows) { long r = 512; while (r > 16 && rows / r < kBnbMinChunks) r >>= 1; return (int)r; }
 // upper bound on the number of partial rows for a [M][C] BN backward (pooled variants iterate over M/2 or M/4 windows)
 extern "C" int crnn_bn_bwd_chunks(long M) {
   int best = 0;

@@ -13,28 +13,18 @@
 // Arithmetic per output is that of the separate kernels (same tap order, same fp32 fma chains, same bf16 roundings): dx is
 // bit-identical, dk differs only through the grouping of its partial sums.
 #include "common.h"
+#include "stream_ops.h"
 
 namespace {
 
 constexpr int kNT = 256, kPXB = 3, kVN = 4, kCL = 16, kPT = kNT / kCL;   // 16 lanes x 4 bf16 channels = one 128-byte slab per pixel
 #define BN_EPS_F 1e-3f
-#ifndef FUSED_WPE
-#define FUSED_WPE 2
-#endif
-#ifndef FUSED_ABL
-#define FUSED_ABL 0
-#endif
+constexpr int kFusedWpe = 2;   // workgroups per CU the registers are budgeted for (profiles/r02_dw_bwd_fused_bench.txt)
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // native vector: a uint4 struct copy becomes a memcpy through scratch
+// (chunks travel as u32x4, a native vector: a uint4 struct copy becomes a memcpy through scratch)
 __device__ __forceinline__ void widen(const uint2& u, float (&f)[4]) {
   f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
   f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-}
-__device__ __forceinline__ void widen8(const u32x4& u, float (&f)[8]) {
-  f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
-  f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-  f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
-  f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
 }
 
 constexpr int kFL = 8, kFPT = kNT / kFL, kNCH = 4;   // fill: 8 lanes x 16 bytes per pixel; at most kNCH chunks per thread and band
@@ -55,13 +45,9 @@ __device__ __forceinline__ void fill_load(const FillGeom& g, int base, const bf1
     // every lane loads (from a clamped, valid address): a conditional load would make the number of outstanding loads
     // unknown to the wait-count insertion, which then drains all of them at the first use of any
     const int o = (min(max(gh, 0), g.H - 1) * g.W + min(max(gw, 0), g.W - 1)) * g.C;
-    if (FUSED_ABL != 1) {
-      vd[uu] = *reinterpret_cast<const u32x4*>(db + o);
-      vg[uu] = *reinterpret_cast<const u32x4*>(gb + o);
-      vx[uu] = *reinterpret_cast<const u32x4*>(xb + o);
-    } else {
-      vd[uu] = vg[uu] = vx[uu] = u32x4{0u, 0u, 0u, 0u};
-    }
+    vd[uu] = *reinterpret_cast<const u32x4*>(db + o);
+    vg[uu] = *reinterpret_cast<const u32x4*>(gb + o);
+    vx[uu] = *reinterpret_cast<const u32x4*>(xb + o);
     if (i < g.n16 && (unsigned)gh < (unsigned)g.H && (unsigned)gw < (unsigned)g.W) inside |= 1u << uu;
     fx += dfx; fy += dfy;
     if (fx >= g.Wt) { fx -= g.Wt; ++fy; }
@@ -135,7 +121,7 @@ __device__ __forceinline__ void fill_store(const FillGeom& g, int base, const fl
 // transformed and stored to the ring after them, so HBM works during the arithmetic.  The data gradient and the weight
 // gradient run as two loops over the band so that the flipped taps (36 registers, reloaded per band) and the BatchNorm
 // coefficients (48) are never live together; the weight-gradient accumulators (36) persist.
-__global__ __launch_bounds__(kNT, FUSED_WPE) void dw_bwd_fused_kernel(const bf16_t* __restrict__ d, const bf16_t* __restrict__ da,
+__global__ __launch_bounds__(kNT, kFusedWpe) void dw_bwd_fused_kernel(const bf16_t* __restrict__ d, const bf16_t* __restrict__ da,
                                                                       const float* __restrict__ bnstate, const float* __restrict__ coef,
                                                                       const bf16_t* __restrict__ xin, const float* __restrict__ k,
                                                                       bf16_t* __restrict__ dx, float* __restrict__ partials, int B, int H, int W, int C,
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(kNT, FUSED_WPE) void dw_bwd_fused_kernel(const bf16
     fg.gfirst = h0 + TH + 1; fg.slot0 = (h0 + TH + 2) % R;
     if (has_next) fill_load(fg, 0, db, gb, xb, vd, vg, vx, inside);
     const int rows = min(TH, hend - h0);
-    const int npg = (FUSED_ABL == 2) ? 0 : rows * gpr;
+    const int npg = rows * gpr;
     const int hm = h0 % R;                             // slot of image row h0 - 1 (window row 0 of output row h0)
     // ---------------- data gradient: correlation of dd with the mirrored taps
     {
@@ -235,13 +221,13 @@ __global__ __launch_bounds__(kNT, FUSED_WPE) void dw_bwd_fused_kernel(const bf16
         const int o = ((h0 + ly) * W + w0 + lx) * C;
 #pragma unroll
         for (int e = 0; e < kPXB; ++e)
-          if (lx + e < wc && (FUSED_ABL != 4 || a[e][0] == 12345.678f)) st4(ob + o + e * C, make_float4(a[e][0], a[e][1], a[e][2], a[e][3]));
+          if (lx + e < wc) st4(ob + o + e * C, make_float4(a[e][0], a[e][1], a[e][2], a[e][3]));
         lg += dlg; ly += dly;
         if (lg >= gpr) { lg -= gpr; ++ly; }
       }
     }
     // ---------------- weight gradient: dk[i][j] += x[p + (i-1, j-1)] * dd[p] over the band's pixels
-    if (FUSED_ABL != 3) {
+    {
       int ly = pt / gpr, lg = pt - ly * gpr;
       for (int pg = pt; pg < npg; pg += kPT) {
         const int lx = lg * kPXB;
@@ -320,9 +306,9 @@ FusedGeom fused_geom(int B, int H, int W, int C) {
   g.nCol = cdiv(W, g.Wc);
   const int gpr = g.Wc / kPXB;
   const long row_bytes = 2L * (g.Wc + 2) * 256;      // both tiles, fp32
-  const long budget = (long)crnn_knob("CRNN_FUSED_LDS", 74 * 1024);   // two workgroups per CU (the registers allow no more)
+  const long budget = 74 * 1024;   // two workgroups per CU (the registers allow no more)
   const long base = (long)B * (C / 64) * g.nCol;
-  const int gt = (int)crnn_knob("CRNN_FUSED_WGS", 2048);
+  const int gt = 2048;                               // workgroups asked for
   int G = (int)((gt + base - 1) / base); if (G < 1) G = 1;
   int best_th = 1; double best = 1e30;
   for (int th = 1; th <= H; ++th) {
@@ -337,11 +323,9 @@ FusedGeom fused_geom(int B, int H, int W, int C) {
     const double c = (it + fill + 0.3 * nb) * cdiv(H, hg);
     if (c < best) { best = c; best_th = th; }
   }
-  g.TH = (int)crnn_knob("CRNN_FUSED_TH", best_th);
-  if ((g.TH + 2) * row_bytes > 78 * 1024 || g.TH * (g.Wc + 2) * kFL > kNCH * kNT || g.TH < 1) g.TH = best_th;
+  g.TH = best_th;
   if (G > cdiv(H, 2 * g.TH)) G = cdiv(H, 2 * g.TH);
   if (G < 1) G = 1;
-  G = (int)crnn_knob("CRNN_FUSED_G", G);
   g.Hg = cdiv(H, G);
   g.G = cdiv(H, g.Hg);
   g.rows = B * g.G * g.nCol;

@@ -7,9 +7,6 @@
 #include "common.h"
 #include "ctc_core.h"
 
-#ifndef CRNN_CTC_EXP
-#define CRNN_CTC_EXP 0      // timing experiments (scripts/ctc_bench.py): 1 = stop after the log-softmax phase, 2 = after the recursions, 3 = before the log-softmax
-#endif
 
 // ---- row softmax over C (<= 128) classes: one wave per row ------------------------------------------
 // CPL = classes per lane: 1 for C <= 64 (lane l = class l), 2 for 65..128 (lane l = classes l and l + 64: the second value rides through the same
@@ -78,14 +75,12 @@ extern "C" int crnn_softmax_rows_perm(const float* z, int ldz, const float* bias
 //   phase 2  wave 0    : alpha recursion (t ascending)   ||   wave 1 : beta recursion (t descending)  -> LDS
 //   phase 3  all waves : time steps dealt round-robin to the waves: w_s = exp(alpha+beta-lsm-ll) per state lane, then
 //                        class lane k adds the w_s of its states (bit mask, ascending s; the blank class by a wave reduction) and chains to the logits
-// Round 5 (scripts/ctc_bench.py, phase-ablation builds): 61 -> 28 us per launch at batch 256 -- the gradient phase was 30 us of it (the blank lane walking
+// Round 5 (phase-ablation builds that are gone; profiles/r05_ctc_bench.txt): 61 -> 28 us per launch at batch 256 -- the gradient phase was 30 us of it (the blank lane walking
 // its 24-state mask through LDS with the wave waiting, two workgroup barriers per time step), the log-softmax phase ran on 50 lanes of 256.
 // LDS: lsm [Tb][C], alpha [Tb][64], beta [Tb][64], ys [Tb][C], ab [4][64].
 // CPL = classes per lane: with 65..128 classes (CPL = 2) the class lane l of phases 1 and 3 owns classes l and l + 64 -- two log-softmax values, two
 // occupancy masks, two gradient elements, one wave reduction over both --; the state lanes and the recursions do not depend on the class count.
-#ifndef CTC_WAVES
-#define CTC_WAVES 16     // round 5: 4 -> 16 (phases 1 and 3 deal the time steps over the waves: 41 -> 28 us at batch 256; 8 waves: 31.5)
-#endif
+constexpr int CTC_WAVES = 16;   // round 5: 4 -> 16 (phases 1 and 3 deal the time steps over the waves: 41 -> 28 us at batch 256; 8 waves: 31.5; profiles/r05_ctc_bench.txt)
 template <int CPL>
 __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const float* __restrict__ y, const int* __restrict__ labels,
                                                                        const int* __restrict__ input_len, const int* __restrict__ label_len,
@@ -121,16 +116,10 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
     return;
   }
   __syncthreads();
-#if CRNN_CTC_EXP == 3
-  return;
-#endif
   // phase 1: log-softmax of z = log(y + eps): a time step per wave, a class per lane (round 5: was one time step per THREAD -- 50 busy lanes of 256, each
   // evaluating 3 C logarithms and C exponentials in sequence: a fifth of the kernel)
   for (int t = wave; t < Tb; t += CTC_WAVES) log_softmax_of_log_row<CPL>(ys + t * C, lsm + t * C, lane, C);
   __syncthreads();
-#if CRNN_CTC_EXP == 1
-  return;
-#endif
   // extended label of this lane (every wave holds its own copy)
   const int s = lane;
   int ext = blank;
@@ -165,9 +154,6 @@ __global__ __launch_bounds__(64 * CTC_WAVES) void ctc_loss_grad_kernel(const flo
     }
   }
   __syncthreads();
-#if CRNN_CTC_EXP == 2
-  return;
-#endif
   const float ll = ll_sh;
   if (tid == 0) loss[b] = -ll;
   if (ll == NEG_INF) {  // no valid path: TF reports inf loss, zero gradient

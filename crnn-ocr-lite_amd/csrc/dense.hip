@@ -14,7 +14,7 @@
 //     clocks = 13 us over a workgroup's 52 rows with the LDS reads and the stores compiled out; dy's LDS broadcasts add 5 us that the half-row
 //     pipelining does not hide, the dx stores 1.5: 20 us;
 //   * 5-7 us until the first rows and the weights have landed (256 workgroups ask for 13 MB at once), 3 us for the 20 MB of partial gradients;
-//   * what it was before each fix (the timing build's per-workgroup stamps, -DCRNN_DSB_TRACE): rows loaded into registers one step ahead -- 16 KB
+//   * what it was before each fix (per-workgroup stamps of a timing build that is gone; profiles/r05_dense_bwd_bench.txt): rows loaded into registers one step ahead -- 16 KB
 //     per CU in flight, 1.6 TB/s; W read as 38 strided words per thread -- 2.5 MB through the vector cache per workgroup; W staged by predicated
 //     loads -- issued one by one, 12 us; the loader wave hashing the dropout decisions -- 1.6 us per 8-row step on one wave, the critical path;
 //     a bounds check between unrolled rows -- every row waited out its LDS latency, 0.44 us per row; the unrolled step left to the scheduler --
@@ -23,10 +23,7 @@
 // Determinism: a workgroup owns a contiguous block of rows and sums them in ascending order; the per-workgroup partial gradients are summed in
 // workgroup order (fixed grid for a given M).
 #include "common.h"
-
-#ifndef CRNN_DSB_EXP
-#define CRNN_DSB_EXP 0   // ablation builds for scripts/dense_bench.py: 1 no multiply-adds | 2 no LDS reads of dy | 4 no partial-gradient store | 8 no dx store | 16 no x DMA | 32 no keep hashing | 64 no W staging
-#endif
+#include "stream_ops.h"
 
 namespace {
 
@@ -36,23 +33,12 @@ struct DsbParams {
   const float* x; const float* dy; const float* W; float* dx; float* part; const unsigned char* keep;
   long M; int K, C, ldx, lddx, rows_per_wg; long part_stride;
   float rate; uint64_t seed; uint32_t layer;
-#ifdef CRNN_DSB_TRACE
-  unsigned long long* trace = nullptr;   // timing build only: [workgroup][8] s_memrealtime stamps (100 MHz)
-#endif
 };
-#ifdef CRNN_DSB_TRACE
-#define DSB_STAMP(i) do { if (p.trace && tid == 0) p.trace[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define DSB_STAMP(i) do {} while (0)
-#endif
 
 constexpr int kDsbDepth = 3, kDsbSlots = kDsbDepth + 1;   // steps in flight, ring slots
 constexpr int kDsbRB = 8;                                  // rows per step
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void dsb_glds16(const void* g, void* l) {   // 16 bytes per lane, nontemporal: the layer's input is not read again
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 2);
-}
 __device__ __forceinline__ void dsb_glds4(const void* g, void* l) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 4, 0, 0);
 }
@@ -80,7 +66,6 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, k = tid;
   const bool loader = wave == nw;
   const int nthr = KH + 64;
-  DSB_STAMP(0);
   const int XSLOT = RB * K * 4;                               // bytes of x per ring slot
   const int X0 = dsb_w_bytes(K, C), DY0 = X0 + kDsbSlots * XSLOT, KP0 = DY0 + kDsbSlots * RB * 256;
   float* wl = reinterpret_cast<float*>(smem);
@@ -109,7 +94,7 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
         const int ii = i < nxi ? i : nxi - 1;
         long off = rb * K * 4 + ii * 1024 + lane * 16;
         off = off < xbytes - 16 ? off : xbytes - 16;           // rows past the tensor (last workgroup's partial step): in-bounds bytes nobody uses
-        if (!(CRNN_DSB_EXP & 16)) dsb_glds16(gx + off, smem + X0 + slot * XSLOT + ii * 1024);
+        glds16<2>(gx + off, smem + X0 + slot * XSLOT + ii * 1024);   // nontemporal: the layer's input is not read again
       }
 #pragma unroll
       for (int r = 0; r < RB; ++r) {
@@ -123,7 +108,7 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
         off = off < gkbytes - 4 ? off : gkbytes - 4;
         dsb_glds4(gk + off, smem + (p.keep ? KP0 + slot * 512 : KP0 + kDsbSlots * 512) + j * 256);   // (no table: any bytes, into the spare 512)
       }
-      if (drop && !p.keep && !(CRNN_DSB_EXP & 32)) {           // no table: the loader evaluates the hashes itself (1.6 us per step: it then bounds the kernel)
+      if (drop && !p.keep) {           // no table: the loader evaluates the hashes itself (1.6 us per step: it then bounds the kernel)
 #pragma unroll
         for (int r = 0; r < RB; ++r)
           if (lane < gpr) smem[KP0 + slot * 512 + r * gpr + lane] = (unsigned char)crnn_keep8(key, (uint64_t)((rb + r) * gpr + lane), thr);
@@ -151,12 +136,11 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
 #pragma unroll
       for (int j = 0; j < CP / 2; ++j) { const int i = k + j * KH; v[j] = gw[i < n4 ? i : n4 - 1]; }   // unconditional: all in flight at once (predicated, they went one by one: 12 us)
 #pragma unroll
-      for (int j = 0; j < CP / 2; ++j) { const int i = k + j * KH; if (i < n4 && !(CRNN_DSB_EXP & 64)) reinterpret_cast<float4*>(wl)[i] = v[j]; }
+      for (int j = 0; j < CP / 2; ++j) { const int i = k + j * KH; if (i < n4) reinterpret_cast<float4*>(wl)[i] = v[j]; }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    DSB_STAMP(1);
     f32x2 w0[CP / 2], w1[CP / 2];
 #pragma unroll
     for (int c = 0; c < CP / 2; ++c) {
@@ -169,7 +153,6 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
     for (int t = 0; t < steps; ++t) {
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (t == 0) DSB_STAMP(2);
       const long rb = r0 + (long)t * RB;
       const float* xs = reinterpret_cast<const float*>(smem + X0 + slot * XSLOT);
       const float* dls = reinterpret_cast<const float*>(smem + DY0 + slot * RB * 256);
@@ -182,8 +165,11 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
       float4 d[2][CP / 8];
       auto ld = [&](int h, int r, int half) {
 #pragma unroll
-        for (int j = 0; j < CP / 8; ++j)
-          d[h][j] = (CRNN_DSB_EXP & 2) ? make_float4(1.f, 2.f, 3.f, (float)r) : *reinterpret_cast<const float4*>(dls + r * 64 + half * (CP / 2) + 4 * j);
+        for (int j = 0; j < CP / 8; ++j) {
+          // (a copy of the read, not the read itself, goes into d: assigned directly the same instructions come out in another order than the measured one)
+          const float4 v = *reinterpret_cast<const float4*>(dls + r * 64 + half * (CP / 2) + 4 * j);
+          d[h][j] = v;
+        }
       };
       // (the row sums run as four independent chains -- two per feature -- interleaved with the accumulator updates: with one wave per SIMD a chain's
       //  next link issued right behind the previous one waits out the multiply-add pipeline)
@@ -192,7 +178,6 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
         for (int j = 0; j < CP / 8; ++j) {
           const int c2 = half * (CP / 4) + 2 * j;          // index of the class pair
           const f32x2 dlo = f32x2{d[h][j].x, d[h][j].y}, dhi = f32x2{d[h][j].z, d[h][j].w};
-          if (CRNN_DSB_EXP & 1) { s0 += dlo; a0[c2] += x0; continue; }
           s0 = pk_fma(dlo, w0[c2], s0); a0[c2] = pk_fma(x0, dlo, a0[c2]);
           s1 = pk_fma(dlo, w1[c2], s1); a1[c2] = pk_fma(x1, dlo, a1[c2]);
           t0 = pk_fma(dhi, w0[c2 + 1], t0); a0[c2 + 1] = pk_fma(x0, dhi, a0[c2 + 1]);
@@ -224,16 +209,13 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
         mac(1, 1, x0, x1, s0, s1, t0, t1);
         s0 += t0; s1 += t1;
         const float m0 = (((kb0 >> (k & 7)) & 1) | nodrop) ? inv_keep : 0.f, m1 = (((kb1 >> (k & 7)) & 1) | nodrop) ? inv_keep : 0.f;
-        if (!(CRNN_DSB_EXP & 8) || s0.x == 1234.5f) {
-          __builtin_nontemporal_store((s0.x + s0.y) * m0, dxr);
-          __builtin_nontemporal_store((s1.x + s1.y) * m1, dxr + KH);
-        }
+        __builtin_nontemporal_store((s0.x + s0.y) * m0, dxr);
+        __builtin_nontemporal_store((s1.x + s1.y) * m1, dxr + KH);
         dxr += p.lddx;
         __builtin_amdgcn_sched_barrier(0);
       }
       slot = slot + 1 == kDsbSlots ? 0 : slot + 1;
     }
-    DSB_STAMP(3);
     // every thread read its weights before its first step barrier: their place takes the partial gradients
 #pragma unroll
     for (int c = 0; c < CP / 2; ++c) {
@@ -242,14 +224,9 @@ __global__ __launch_bounds__(kDsbMaxThreads / 2 + 64) void dense_bwd_small_kerne
     }
   }
   __syncthreads();
-  DSB_STAMP(4);
   float* part = p.part + (long)blockIdx.x * p.part_stride;
-  if (!(CRNN_DSB_EXP & 4)) for (int i = tid; i < (K * C) >> 2; i += nthr) reinterpret_cast<float4*>(part)[i] = reinterpret_cast<const float4*>(wl)[i];
+  for (int i = tid; i < (K * C) >> 2; i += nthr) reinterpret_cast<float4*>(part)[i] = reinterpret_cast<const float4*>(wl)[i];
   if (!loader && k < C) part[(long)K * C + k] = db;
-#ifdef CRNN_DSB_TRACE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  DSB_STAMP(5);
-#endif
 }
 
 // second stage: out[i] = sum over the workgroups' partial rows, in row order (8 interleaved chains, combined in order), double accumulation as
@@ -297,10 +274,6 @@ DsbGeom dsb_geom(long M, int K, int C) {
 
 }  // namespace
 
-#ifdef CRNN_DSB_TRACE
-static unsigned long long* g_dsb_trace = nullptr;
-extern "C" void crnn_dense_bwd_small_set_trace(unsigned long long* t) { g_dsb_trace = t; }
-#endif
 extern "C" int crnn_dense_bwd_small_supported(long M, int K, int C) {
   return (M > 0 && K >= 128 && K % 128 == 0 && K <= kDsbMaxThreads && C >= 1 && C <= kDsbClasses) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
 }
@@ -324,9 +297,6 @@ extern "C" int crnn_dense_bwd_small(const float* x, const float* dy, const float
   DsbParams p;
   p.x = x; p.dy = dy; p.W = W; p.dx = dx; p.part = scratch; p.keep = drop_rate > 0.f ? static_cast<const unsigned char*>(keep) : nullptr; p.M = M; p.K = K; p.C = C; p.ldx = ldx; p.lddx = lddx;
   p.rows_per_wg = g.rows_per_wg; p.part_stride = g.part_stride; p.rate = drop_rate; p.seed = seed; p.layer = layer;
-#ifdef CRNN_DSB_TRACE
-  p.trace = g_dsb_trace;
-#endif
   const int lds = dsb_lds_bytes(K, C);      // <= 154 KiB (K = 512, C = 40)
   if (lds > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)dense_bwd_small_kernel<kDsbClasses>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);

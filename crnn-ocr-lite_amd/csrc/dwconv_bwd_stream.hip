@@ -22,21 +22,11 @@
 // the DX waves, each for its own column: spread over five waves it fits next to their ~70 operations per step, where one dedicated
 // wave for all five column groups became the critical path (profiles/r04_*: + 23 % kernel time).
 #include "common.h"
+#include "stream_ops.h"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define BN_EPS_F 1e-3f
-
-#ifndef CRNN_DBS_EXP
-#define CRNN_DBS_EXP 0      // experiment builds: 1 = no DMA, 2 = no stores, 4 = no dk fmas, 8 = no dx fmas
-#endif
-#ifndef CRNN_DBS_D
-#define CRNN_DBS_D 3
-#endif
-#ifndef CRNN_DBS_F32_WGS
-#define CRNN_DBS_F32_WGS 1  // workgroups per CU the fp32 form is compiled for (2 = 6 waves per SIMD = 80 registers: the DK waves spill 81 -- not used)
-#endif
 
 struct DbsParams {
   const unsigned char *d, *da, *xin; unsigned char* dx; const float *bnstate, *coef, *k; float* partials;
@@ -45,33 +35,9 @@ struct DbsParams {
   const float* pro_bn; const unsigned char* keep; float rate; float* bn2_partials;
 };
 
-#ifndef CRNN_DBS_NT
-#define CRNN_DBS_NT 1      // round 5: d, da, xin are read here for the last time in the step -> nontemporal LDS-DMA (they do not push the kernel's own output,
-#endif                     // which the next BatchNorm backward reads at once, out of the last-level cache): -0.07 ms per step, same bits (profiles/r05_nt_loads_ab.txt)
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, CRNN_DBS_NT ? 2 : 0);
-}
-__device__ __forceinline__ void widen8(const u32x4& u, float (&f)[8]) {
-  f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
-  f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-  f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
-  f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
-}
-
-// element forms of a 16-byte chunk: 8 bf16 (EPC = 8) or 4 fp32 (EPC = 4) -- the fp32 form runs the same schedule on half as many channels
-// per lane and twice as many channel ranges per row (round 4: the parity mode's depthwise-stage backward)
-template <int EPC> __device__ __forceinline__ void widenE(const u32x4& u, float (&f)[EPC]);
-template <> __device__ __forceinline__ void widenE<8>(const u32x4& u, float (&f)[8]) { widen8(u, f); }
-template <> __device__ __forceinline__ void widenE<4>(const u32x4& u, float (&f)[4]) {
-  f[0] = __uint_as_float(u.x); f[1] = __uint_as_float(u.y); f[2] = __uint_as_float(u.z); f[3] = __uint_as_float(u.w);
-}
-template <int EPC> __device__ __forceinline__ u32x4 packE(const float (&f)[EPC]);
-template <> __device__ __forceinline__ u32x4 packE<8>(const float (&f)[8]) {
-  u32x4 o; o.x = pack2_bf16(f[0], f[1]); o.y = pack2_bf16(f[2], f[3]); o.z = pack2_bf16(f[4], f[5]); o.w = pack2_bf16(f[6], f[7]); return o;
-}
-template <> __device__ __forceinline__ u32x4 packE<4>(const float (&f)[4]) {
-  u32x4 o; o.x = __float_as_uint(f[0]); o.y = __float_as_uint(f[1]); o.z = __float_as_uint(f[2]); o.w = __float_as_uint(f[3]); return o;
-}
+// round 5: d, da, xin are read here for the last time in the step -> nontemporal LDS-DMA (they do not push the kernel's own output, which the next
+// BatchNorm backward reads at once, out of the last-level cache): -0.07 ms per step, same bits (profiles/r05_nt_loads_ab.txt)
+constexpr int kDbsPolicy = 2;
 
 constexpr int kCW = 5;                       // compute waves per group (320 columns)
 constexpr int kSub = 5 * 1024;               // one row of one tensor in a ring stage (5 DMA instructions)
@@ -94,7 +60,7 @@ struct DbsLds {
   static_assert(!DXS || NR * kStageB >= SredOff + 5 * 2 * 256 * 4, "statistics records inside the ring");
   static_assert((KD - 1) * kNI <= 63, "vmcnt is a 6-bit counter");
 };
-constexpr int kD = CRNN_DBS_D;
+constexpr int kD = 3;                        // stages in flight (2 and 5 measured: profiles/r03_dw_bwd_stream_bench.txt)
 
 // role of wave slot w (11 waves; SIMD = w mod 4): DK work is about twice DX work per step
 //   SIMD 3: w3 w7 = DK DK;  SIMD 0: w0 w4 w8 = DK DX DX;  SIMD 1: w1 w5 w9 = DK DX DX;  SIMD 2: w2 w6 w10 = DK DX loader
@@ -124,7 +90,7 @@ __device__ __forceinline__ int role_of_stats(int w, int& idx) {   // 0 = DK, 1 =
 // this kernel + 0.24 ms (the one wave's ~400 operations per step are the critical path); done by the DX waves themselves + 0.65 (36
 // spilled registers); gating in the DX waves and sums in the twelfth + 0.35 -- so it is not the default schedule.
 template <int KD, bool PRO, bool DROP, bool STATS = false, bool F32 = false>
-__global__ __launch_bounds__((STATS && !F32) ? 768 : 704, (F32 && CRNN_DBS_F32_WGS > 1) ? 3 * CRNN_DBS_F32_WGS : 1) void dw_bwd_stream_kernel(DbsParams p) {
+__global__ __launch_bounds__((STATS && !F32) ? 768 : 704, 1) void dw_bwd_stream_kernel(DbsParams p) {
   static_assert(!STATS || PRO, "the statistics form is a prologue form");
   // fp32 tensors: half the elements per step leave the DX waves the issue slots and registers to take the statistics themselves (their dx values are
   // in registers: no LDS round trip, no twelfth wave whose ~250 operations per step were the critical path: + 0.25 ms over four launches at batch 256)
@@ -181,11 +147,9 @@ __global__ __launch_bounds__((STATS && !F32) ? 768 : 704, (F32 && CRNN_DBS_F32_W
       unsigned char* dst = lds + slot * kStageB;
 #pragma unroll
       for (int i = 0; i < 5; ++i) {
-        if (!(CRNN_DBS_EXP & 1)) {
-          glds16(gd + od + goff[i], dst + i * 1024);
-          glds16(gg + od + goff[i], dst + kSub + i * 1024);
-          glds16(gxx + ox + goff[i], dst + 2 * kSub + i * 1024);
-        }
+        glds16<kDbsPolicy>(gd + od + goff[i], dst + i * 1024);
+        glds16<kDbsPolicy>(gg + od + goff[i], dst + kSub + i * 1024);
+        glds16<kDbsPolicy>(gxx + ox + goff[i], dst + 2 * kSub + i * 1024);
       }
       if (DROP) {
 #pragma unroll
@@ -420,24 +384,19 @@ __global__ __launch_bounds__((STATS && !F32) ? 768 : 704, (F32 && CRNN_DBS_F32_W
       const u32x4 vL = *reinterpret_cast<const u32x4*>(hasL ? sb + offC - pitch : lds + kZOff);
       const u32x4 vC = *reinterpret_cast<const u32x4*>(sb + offC);
       const u32x4 vR = *reinterpret_cast<const u32x4*>(hasR ? sb + offC + pitch : lds + kZOff);
-      if (!(CRNN_DBS_EXP & 8)) {
-        float f[EPC];
-        widenE<EPC>(vL, f);
+      float f[EPC];
+      widenE<EPC>(vL, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[6][e], A[e]); Bc[e] = fmaf(f[e], kw[3][e], Bc[e]); Cn[e] = fmaf(f[e], kw[0][e], 0.f); }
-        widenE<EPC>(vC, f);
+      for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[6][e], A[e]); Bc[e] = fmaf(f[e], kw[3][e], Bc[e]); Cn[e] = fmaf(f[e], kw[0][e], 0.f); }
+      widenE<EPC>(vC, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[7][e], A[e]); Bc[e] = fmaf(f[e], kw[4][e], Bc[e]); Cn[e] = fmaf(f[e], kw[1][e], Cn[e]); }
-        widenE<EPC>(vR, f);
+      for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[7][e], A[e]); Bc[e] = fmaf(f[e], kw[4][e], Bc[e]); Cn[e] = fmaf(f[e], kw[1][e], Cn[e]); }
+      widenE<EPC>(vR, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[8][e], A[e]); Bc[e] = fmaf(f[e], kw[5][e], Bc[e]); Cn[e] = fmaf(f[e], kw[2][e], Cn[e]); }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { A[e] += __uint_as_float(vL[e]); A[(e + 4) % EPC] += __uint_as_float(vC[e]); Bc[e] += __uint_as_float(vR[e]); }
-      }
+      for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[8][e], A[e]); Bc[e] = fmaf(f[e], kw[5][e], Bc[e]); Cn[e] = fmaf(f[e], kw[2][e], Cn[e]); }
       if (a >= 2 && act) {
         const u32x4 o = packE<EPC>(A);
-        if (!(CRNN_DBS_EXP & 2)) *reinterpret_cast<u32x4*>(orow + (long)(a - 2) * p.rowbytes) = o;
+        *reinterpret_cast<u32x4*>(orow + (long)(a - 2) * p.rowbytes) = o;
 #undef orow
         if (SW) *reinterpret_cast<u32x4*>(lds + kDxrOff + (a & 1) * kSub + offC) = o;   // (for the statistics wave, one step later)
         if (DXS) dxstats(A);
@@ -562,22 +521,17 @@ __global__ __launch_bounds__((STATS && !F32) ? 768 : 704, (F32 && CRNN_DBS_F32_W
         const int g = r0 - 2 + s;
         if (g < 0 || g >= p.H) { vL = (u32x4)(0u); vC = (u32x4)(0u); vR = (u32x4)(0u); }
       }
-      if (!(CRNN_DBS_EXP & 4)) {
-        float f[EPC], dn[EPC], dm1[EPC], dm2[EPC];
-        widenE<EPC>(Dn, dn); widenE<EPC>(Dm1, dm1); widenE<EPC>(Dm2, dm2);
-        widenE<EPC>(vL, f);
+      float f[EPC], dn[EPC], dm1[EPC], dm2[EPC];
+      widenE<EPC>(Dn, dn); widenE<EPC>(Dm1, dm1); widenE<EPC>(Dm2, dm2);
+      widenE<EPC>(vL, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { dk[0][e] = fmaf(f[e], dn[e], dk[0][e]); dk[3][e] = fmaf(f[e], dm1[e], dk[3][e]); dk[6][e] = fmaf(f[e], dm2[e], dk[6][e]); }
-        widenE<EPC>(vC, f);
+      for (int e = 0; e < EPC; ++e) { dk[0][e] = fmaf(f[e], dn[e], dk[0][e]); dk[3][e] = fmaf(f[e], dm1[e], dk[3][e]); dk[6][e] = fmaf(f[e], dm2[e], dk[6][e]); }
+      widenE<EPC>(vC, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { dk[1][e] = fmaf(f[e], dn[e], dk[1][e]); dk[4][e] = fmaf(f[e], dm1[e], dk[4][e]); dk[7][e] = fmaf(f[e], dm2[e], dk[7][e]); }
-        widenE<EPC>(vR, f);
+      for (int e = 0; e < EPC; ++e) { dk[1][e] = fmaf(f[e], dn[e], dk[1][e]); dk[4][e] = fmaf(f[e], dm1[e], dk[4][e]); dk[7][e] = fmaf(f[e], dm2[e], dk[7][e]); }
+      widenE<EPC>(vR, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { dk[2][e] = fmaf(f[e], dn[e], dk[2][e]); dk[5][e] = fmaf(f[e], dm1[e], dk[5][e]); dk[8][e] = fmaf(f[e], dm2[e], dk[8][e]); }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { dk[0][e] += __uint_as_float(vL[e] + Dn[e]); dk[1][e] += __uint_as_float(vC[e] + Dm1[e]); dk[2][e] += __uint_as_float(vR[e] + Dm2[e]); }
-      }
+      for (int e = 0; e < EPC; ++e) { dk[2][e] = fmaf(f[e], dn[e], dk[2][e]); dk[5][e] = fmaf(f[e], dm1[e], dk[5][e]); dk[8][e] = fmaf(f[e], dm2[e], dk[8][e]); }
     }
   };
   step(0, H0, H2, H1, true);
@@ -652,13 +606,11 @@ DbsGeom dbs_geom(int B, int H, int W, int C, int epc = 8) {   // epc: elements p
   // below a wave (shuffle reduction)
   if (cols <= 2 * 64 || (cppw & (cppw - 1)) || cppw > 32) return g;
   int nwgb = 1;
-#ifndef CRNN_DBS_WGS
-#define CRNN_DBS_WGS 256
-#endif
+  constexpr int want = 256;                        // workgroups asked for: one per CU
   for (int n = 1; n <= H; ++n) {
     if (H % n || H / n < 8) continue;
     nwgb = n;
-    if ((long)B * n * ns >= CRNN_DBS_WGS) break;
+    if ((long)B * n * ns >= want) break;
   }
   if (H % nwgb) return g;
   g.nsplit = ns; g.nwgb = nwgb; g.HB = H / nwgb; g.cols = cols; g.cppw = cppw; g.ok = true;

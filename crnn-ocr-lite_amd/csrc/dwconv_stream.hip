@@ -29,53 +29,21 @@
 // transform waves themselves 0.35 (a vmcnt wait per row); the re-forming done by the nine compute waves on their own chunks 0.50
 // (two dependent LDS round trips per row in every wave, register spills); keep bytes through the loader's DMA: this version.
 #include "common.h"
+#include "stream_ops.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#ifndef CRNN_DWS_EXP
-#define CRNN_DWS_EXP 0      // experiment builds: 1 = no DMA, 2 = no stores, 4 = no fmas, 8 = nontemporal stores, 16 = nontemporal loads, 32 = no transform (prologue form)
-#endif
 
 struct DwsParams {
   const unsigned char* x; const float* k; unsigned char* out; float* partials; const float* bnstate;
   int H, W, C, HB, NS, nwgb, flip, cols, rowbytes, wmaj;
   int nsplit, cppw;          // channel ranges per row (fp32 form: 2 for rows of 18 KiB), 16-byte columns per pixel of one range
   int xstride = 1;           // workgroup-id distance between the channel ranges of one band (see the kernel)
-#ifdef CRNN_DWS_TRACE
-  unsigned long long* trace = nullptr; // timing build only: [workgroup][4] s_memrealtime stamps (entry, first row landed, last step done, statistics written)
-#endif
   // prologue form: BatchNorm state [mean|var|scale|shift] of the producer, dropout of its output
   const float* pro_bn; const unsigned char* keep; float rate;
 };
 
-#ifndef CRNN_DWS_NT
-#define CRNN_DWS_NT 1       // round 5: the input map is not read again before the backward pass -> nontemporal LDS-DMA (cache policy only; see conv.hip)
-#endif
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, (CRNN_DWS_NT != 0 || (CRNN_DWS_EXP & 16) != 0) ? 2 : 0);
-}
-__device__ __forceinline__ void widen8(const u32x4& u, float (&f)[8]) {
-  f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
-  f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-  f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
-  f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
-}
-
-// element forms of a 16-byte chunk: 8 bf16 (EPC = 8) or 4 fp32 (EPC = 4; round 4, the parity mode's prologue form)
-template <int EPC> __device__ __forceinline__ void widenE(const u32x4& u, float (&f)[EPC]);
-template <> __device__ __forceinline__ void widenE<8>(const u32x4& u, float (&f)[8]) { widen8(u, f); }
-template <> __device__ __forceinline__ void widenE<4>(const u32x4& u, float (&f)[4]) {
-  f[0] = __uint_as_float(u.x); f[1] = __uint_as_float(u.y); f[2] = __uint_as_float(u.z); f[3] = __uint_as_float(u.w);
-}
-template <int EPC> __device__ __forceinline__ u32x4 packE(const float (&f)[EPC]);
-template <> __device__ __forceinline__ u32x4 packE<8>(const float (&f)[8]) {
-  u32x4 o; o.x = pack2_bf16(f[0], f[1]); o.y = pack2_bf16(f[2], f[3]); o.z = pack2_bf16(f[4], f[5]); o.w = pack2_bf16(f[6], f[7]); return o;
-}
-template <> __device__ __forceinline__ u32x4 packE<4>(const float (&f)[4]) {
-  u32x4 o; o.x = __float_as_uint(f[0]); o.y = __float_as_uint(f[1]); o.z = __float_as_uint(f[2]); o.w = __float_as_uint(f[3]); return o;
-}
+// round 5: the input map is not read again before the backward pass -> nontemporal LDS-DMA (cache policy only; profiles/r05_nt_loads_ab.txt)
+constexpr int kDwsPolicy = 2;
 
 constexpr int kDwsMaxWaves = 9;     // compute waves (576 columns of 16 bytes)
 
@@ -122,7 +90,6 @@ struct DwsXform {
     ik = DROP ? 1.f / (1.f - p.rate) : 1.f;                     // (spelled as bn_act_pool_drop_kernel spells it: the same bits)
   }
   __device__ __forceinline__ void run(unsigned char* sb, const unsigned char* kbp) const {
-    if (CRNN_DWS_EXP & 32) return;                               // experiment build: no re-forming
     u32x4 v[kDwsProChunks]; uint32_t kc[kDwsProChunks];
     // keep bytes: one per group of 8 elements = per chunk (bf16) | per pair of chunks (fp32: the chunk's nibble)
 #pragma unroll
@@ -200,13 +167,6 @@ __global__ __launch_bounds__((NI + (PRO ? 3 : 1)) * 64) void dw_fwd_stream_kerne
   const int steps = p.HB + 2;                      // input rows r0-1 .. r0+HB of every sub-band
   const int zoff = NR * SLOT;                      // 16 zero bytes (the pixels left of x = 0 and right of x = W-1)
   if (tid < 4) reinterpret_cast<unsigned*>(lds + zoff)[tid] = 0u;
-#ifdef CRNN_DWS_TRACE
-  unsigned long long* const trc = (p.trace && tid == 0) ? p.trace + (long)blockIdx.x * 4 : nullptr;
-  if (trc) trc[0] = __builtin_amdgcn_s_memrealtime();
-#define DWS_TRC(i) do { if (trc) trc[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define DWS_TRC(i) do {} while (0)
-#endif
 
   if (PRO && role == 1) {
     // ------------------------------------------------------------------ transform waves (prologue form): half of every row each
@@ -256,7 +216,7 @@ __global__ __launch_bounds__((NI + (PRO ? 3 : 1)) * 64) void dw_fwd_stream_kerne
       for (int i = 0; i < NI; ++i) {
         int row = rowfirst[i] + t;
         row = row < 0 ? 0 : (row >= p.H ? p.H - 1 : row);      // rows outside the image: any valid row (the compute waves substitute zeros)
-        if (!(CRNN_DWS_EXP & 1)) glds16(gx + (long)row * p.rowbytes + within[i], lds + slot * SLOT + i * 1024);
+        glds16<kDwsPolicy>(gx + (long)row * p.rowbytes + within[i], lds + slot * SLOT + i * 1024);
       }
       if (DROP) {
 #pragma unroll
@@ -334,21 +294,16 @@ __global__ __launch_bounds__((NI + (PRO ? 3 : 1)) * 64) void dw_fwd_stream_kerne
         const int g = rsub - 1 + t;
         if (g < 0 || g >= p.H) { vL = (u32x4)(0u); vC = (u32x4)(0u); vR = (u32x4)(0u); }
       }
-      if (!(CRNN_DWS_EXP & 4)) {
-        float f[EPC];
-        widenE<EPC>(vL, f);
+      float f[EPC];
+      widenE<EPC>(vL, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[6][e], A[e]); Bc[e] = fmaf(f[e], kw[3][e], Bc[e]); Cn[e] = fmaf(f[e], kw[0][e], 0.f); }
-        widenE<EPC>(vC, f);
+      for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[6][e], A[e]); Bc[e] = fmaf(f[e], kw[3][e], Bc[e]); Cn[e] = fmaf(f[e], kw[0][e], 0.f); }
+      widenE<EPC>(vC, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[7][e], A[e]); Bc[e] = fmaf(f[e], kw[4][e], Bc[e]); Cn[e] = fmaf(f[e], kw[1][e], Cn[e]); }
-        widenE<EPC>(vR, f);
+      for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[7][e], A[e]); Bc[e] = fmaf(f[e], kw[4][e], Bc[e]); Cn[e] = fmaf(f[e], kw[1][e], Cn[e]); }
+      widenE<EPC>(vR, f);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[8][e], A[e]); Bc[e] = fmaf(f[e], kw[5][e], Bc[e]); Cn[e] = fmaf(f[e], kw[2][e], Cn[e]); }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { A[e] += __uint_as_float(vL[e]); A[(e + 4) % EPC] += __uint_as_float(vC[e]); Bc[e] += __uint_as_float(vR[e]); }
-      }
+      for (int e = 0; e < EPC; ++e) { A[e] = fmaf(f[e], kw[8][e], A[e]); Bc[e] = fmaf(f[e], kw[5][e], Bc[e]); Cn[e] = fmaf(f[e], kw[2][e], Cn[e]); }
       if (t >= 2 && act) {
         if (EPI) {
 #pragma unroll
@@ -360,13 +315,11 @@ __global__ __launch_bounds__((NI + (PRO ? 3 : 1)) * 64) void dw_fwd_stream_kerne
         const u32x4 o = packE<EPC>(A);
         unsigned char* dst = orow + (long)(t - 2) * p.rowbytes;
         if (EPI && p.wmaj) { const int y = rsub + t - 2; dst = owin + (long)(y >> 1) * 2 * p.rowbytes + (y & 1) * 2 * gpitch; }
-        if (CRNN_DWS_EXP & 8) __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(dst));
         // (write-through stores -- sc0 sc1, sc1 or sc0 -- were measured in round 5: 3.2-3.3 TB/s instead of 4.3 cold, +0.15 ms in the step; plain stores stay)
-        else if (!(CRNN_DWS_EXP & 2)) *reinterpret_cast<u32x4*>(dst) = o;
+        *reinterpret_cast<u32x4*>(dst) = o;
       }
     };
     step(0, X1, X2, X0, true);
-    DWS_TRC(1);
     step(1, X2, X0, X1, false);
     int t = 2;
     for (; t + 3 <= steps - 1; t += 3) {          // whole groups of three that do not contain the last step
@@ -379,7 +332,6 @@ __global__ __launch_bounds__((NI + (PRO ? 3 : 1)) * 64) void dw_fwd_stream_kerne
       else if (r == 1) step(t, X1, X2, X0, true);
       else step(t, X2, X0, X1, true);
     }
-    DWS_TRC(2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (!EPI && p.partials) {
@@ -434,7 +386,6 @@ __global__ __launch_bounds__((NI + (PRO ? 3 : 1)) * 64) void dw_fwd_stream_kerne
         }
       }
     }
-    DWS_TRC(3);
   }
 }
 
@@ -462,10 +413,7 @@ DwsGeom dws_geom(int B, int H, int W, int C, int es = 2) {
   g.nsplit = ns; g.cppw = C / epc / ns;
   // bands per image over workgroups: enough workgroups for the chip, bands of at least 8 rows
   int nwgb = 1;
-#ifndef CRNN_DWS_WGS
-#define CRNN_DWS_WGS 256
-#endif
-  const int want = CRNN_DWS_WGS;
+  constexpr int want = 256;                        // workgroups asked for: one per CU
   for (int n = 1; n <= H / NS; ++n) {
     if ((H / NS) % n || H / NS / n < 8) continue;
     nwgb = n;
@@ -478,10 +426,7 @@ DwsGeom dws_geom(int B, int H, int W, int C, int es = 2) {
   return g;
 }
 
-#ifndef CRNN_DWS_D
-#define CRNN_DWS_D 4
-#endif
-constexpr int kDwsD = CRNN_DWS_D;     // rows in flight per workgroup (2..7 measured: 4.4 / 4.6 / 4.6 / 4.5 TB/s at 2 / 3 / 4 / 7)
+constexpr int kDwsD = 4;              // rows in flight per workgroup (profiles/r03_dw_fwd_stream_experiments.txt; 2..7 measured: 4.4 / 4.6 / 4.6 / 4.5 TB/s at 2 / 3 / 4 / 7)
 
 template <int NI, bool EPI, bool F32>
 int dws_launch_ni(const DwsParams& p, const DwsGeom& g, int B, hipStream_t stream) {
@@ -544,9 +489,6 @@ extern "C" int crnn_dwconv3x3_fwd_stream_ex(const void* x, const float* k, void*
   p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.NS = g.NS; p.nwgb = g.nwgb; p.flip = flip; p.cols = g.cols; p.rowbytes = W * C * 2; p.wmaj = out_order;
   p.nsplit = g.nsplit; p.cppw = g.cppw; p.xstride = g.xstride;
   p.pro_bn = nullptr; p.keep = nullptr; p.rate = 0.f;
-#ifdef CRNN_DWS_TRACE
-  { const char* e = getenv("CRNN_DWS_TRACE_PTR"); p.trace = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
-#endif
   return bnstate ? dws_launch<true>(p, g, B, stream) : dws_launch<false>(p, g, B, stream);
 }
 // Prologue form (training): `q` is the previous block's pointwise output, pro_bnstate its BatchNorm-2 state [mean|var|scale|shift]; the

@@ -24,9 +24,7 @@
 //     staging, no barrier in the epilogue.
 // Numerics: the same MFMA, the same k order (64-k chunks, 16-k steps) as gemm_bf16.hip.
 #include "common.h"
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#include "stream_ops.h"
 
 namespace {
 
@@ -39,10 +37,6 @@ struct NtParams {
 };
 
 constexpr int kStageA = 128 * 128;          // 128 pixel rows x 64 k x 2 B
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // R = ring depth (slots per operand): chunk i is consumed while chunks i+1 .. i+R-2 are in flight / landed and chunk i+R-1 is issued
 template <int BN, int R>
@@ -80,14 +74,14 @@ __global__ __launch_bounds__(384) void gemm_nt_kernel(NtParams p) {
         int row = r0 + 8 * j + rsub;
         row = row < p.M ? row : p.M - 1;
         const int c = pos ^ ((4 * j + (lane >> 4)) & 7);
-        glds16(p.X + row * ldk + kc * 64 + c * 8, da + j * 1024);
+        glds16<0>(p.X + row * ldk + kc * 64 + c * 8, da + j * 1024);
       }
 #pragma unroll
       for (int jj = 0; jj < BN / 16; ++jj) {
         const int j = lw * (BN / 16) + jj;
         const int row = tn * BN + 8 * j + rsub;
         const int c = pos ^ ((4 * j + (lane >> 4)) & 7);
-        glds16(p.W + row * ldk + kc * 64 + c * 8, db + j * 1024);
+        glds16<0>(p.W + row * ldk + kc * 64 + c * 8, db + j * 1024);
       }
     };
 #pragma unroll
@@ -174,14 +168,13 @@ extern "C" int crnn_gemm_nt_bf16(const void* X, const void* W, void* Y, int M, i
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
   const int grid = p.stripes < cus ? p.stripes : cus;
-  const int variant = crnn_knob("CRNN_NT_VARIANT", 0);   // 1: 128 channels per pass + 4 slots, 2: 128 + 3 slots (experiment builds)
-  if (N % 256 == 0 && variant != 1) {
+  // (256 channels per pass wherever N allows it; 128 + 3 slots lost: profiles/r02_gemm_nt_bench.txt)
+  if (N % 256 == 0) {
     p.nt = N / 256;
     hipLaunchKernelGGL((gemm_nt_kernel<256, 3>), dim3(grid), dim3(384), 0, stream, p);
   } else {
     p.nt = N / 128;
-    if (variant == 2) hipLaunchKernelGGL((gemm_nt_kernel<128, 3>), dim3(grid), dim3(384), 0, stream, p);
-    else hipLaunchKernelGGL((gemm_nt_kernel<128, 4>), dim3(grid), dim3(384), 0, stream, p);
+    hipLaunchKernelGGL((gemm_nt_kernel<128, 4>), dim3(grid), dim3(384), 0, stream, p);
   }
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;

@@ -24,16 +24,9 @@
 // v_mfma_f32_32x32x16_bf16 that accumulates onto the one before it issues every 32 cycles like an independent one: scripts/probes/mfma_probe.hip).  The
 // statistics are the same sums in another order (per-lane fp32 chains, crnn_bn_bwd_finalize_folded in double).
 #include "common.h"
+#include "stream_ops.h"
 #include <type_traits>
 #include <utility>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-#ifndef PRES_EXP
-#define PRES_EXP 0   // timing experiments (wrong results): 1 no drain, 2 no MFMAs, 4 no fragment reads, 8 no ring DMA, 16 no stage barriers, 32 no end-of-stripe tile writes, 64 no stage waits, 128 trace, 256 no da stores, 512 no statistics
-#endif
 
 namespace {
 
@@ -56,17 +49,6 @@ __device__ __forceinline__ bf16x8_t pr_pin_a(bf16x8_t v) { asm volatile("" : "+a
 __device__ __forceinline__ bf16x8_t pr_pin_v(bf16x8_t v) { asm volatile("" : "+v"(v)); return v; }   // ... or keep where it is (opaque only)
 template <int N, class F> __device__ __forceinline__ void pr_for(F&& f) { pr_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
-__device__ __forceinline__ unsigned pr_lds_addr(const void* p) { return (unsigned)(uintptr_t)((__attribute__((address_space(3))) const unsigned char*)p); }
-// LDS-DMA the compiler does not see: 16 bytes per lane from each lane's own global address to lds_dst (wave-uniform) + 16 lane
-__device__ __forceinline__ void pr_dma16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void pr_wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ bf16x8_t pr_frag(const unsigned char* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(p)); }
 
 // stages whose issue lies between the issue of stage lin + 1 and the wait for it (iterations lin + 3 - R .. lin - 1) that open a stripe (and so carry that
 // stripe's d pieces): d = 1 .. R - 3 with (j - d) % KST == 0
@@ -93,7 +75,6 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
   static_assert(JD < KST, "the drain fills the stripe");
   static_assert(R >= 4 && OPG >= 1, "ring depth / drain gaps");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // ring [R][planes][PB][32][128 B] | transposition tiles [4 waves][PB][4 KiB] | d [4 waves][DB][PB][4 KiB]
-  const unsigned long long re0 = (PRES_EXP & 128) ? __builtin_amdgcn_s_memrealtime() : 0ull;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wg = blockIdx.x;
@@ -117,8 +98,8 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
   }
   unsigned char* const Tt = smem + R * STAGE + wave * (PB * 4096);
   unsigned char* const Db = smem + R * STAGE + 4 * PB * 4096 + wave * (DB * PB * 4096);
-  const unsigned ring_a = __builtin_amdgcn_readfirstlane(pr_lds_addr(smem));
-  const unsigned db_a = __builtin_amdgcn_readfirstlane(pr_lds_addr(Db));
+  const unsigned ring_a = __builtin_amdgcn_readfirstlane(lds_addr(smem));
+  const unsigned db_a = __builtin_amdgcn_readfirstlane(lds_addr(Db));
   const int half = lane >> 5, l31 = lane & 31, sw = (l31 >> 1) & 7;
 
   // ---- the slice's planes, once: lane (l31, half) holds k = 64 j + 16 ks + 8 half + 0..7 of channel slice * 128 + 32 wave + l31.  The wave's 32 rows of W
@@ -132,16 +113,16 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
     constexpr int ROWB = KH * 4, RPP = 1024 / ROWB, CPRW = ROWB / 16;      // bytes per staged row, rows per 1-KiB DMA piece, 16-byte chunks per row
     static_assert(LDSB >= 4 * 32 * ROWB, "staging area");
     unsigned char* const wst = smem + wave * (32 * ROWB);       // this wave's staging area
-    const unsigned wst_a = __builtin_amdgcn_readfirstlane(pr_lds_addr(wst));
+    const unsigned wst_a = __builtin_amdgcn_readfirstlane(lds_addr(wst));
 #pragma unroll
     for (int H = 0; H < NH; ++H) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (the previous pass's fragment reads are done)
 #pragma unroll
       for (int pc = 0; pc < 32 / RPP; ++pc) {                   // piece pc = rows RPP pc .. : lane -> row RPP pc + lane / CPRW, chunk position lane % CPRW
         const int row = RPP * pc + lane / CPRW;
-        pr_dma16(p.W + (long)(slice * 128 + 32 * wave + row) * p.ldw + KH * H + 4 * ((lane % CPRW) ^ (row & 15)), wst_a + pc * 1024);
+        dma16_m0(p.W + (long)(slice * 128 + 32 * wave + row) * p.ldw + KH * H + 4 * ((lane % CPRW) ^ (row & 15)), wst_a + pc * 1024);
       }
-      pr_wait_vm<0>();
+      wait_vm<0>();
 #pragma unroll
       for (int jj = 0; jj < KH / 64; ++jj)
 #pragma unroll
@@ -188,11 +169,11 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
   auto issue_ring = [&](int its, int js, int slot, int t) __attribute__((always_inline)) {
     if (its >= mine) { its = mine - 1; js = KST - 1; }
     const long uo = ((long)(first + its * step) * PX + 32 * (t % PB)) * p.K + 64 * js + (long)(t / PB) * p.xps;   // wave-uniform
-    if (!(PRES_EXP & 8)) pr_dma16(xlane + uo, ring_a + slot * STAGE + wave * 1024 + t * 4096);
+    dma16_m0(xlane + uo, ring_a + slot * STAGE + wave * 1024 + t * 4096);
   };
   auto issue_d = [&](int it, int i) __attribute__((always_inline)) {   // piece i of 4 PB: block i / 4, rows 8 (i % 4) + (lane >> 3)
     const long uo = ((long)(first + it * step) * PX + 32 * (i / 4)) * p.N;
-    pr_dma16(dlane[i % 4] + uo, db_a + ((it & (DB - 1)) * PB + i / 4) * 4096 + (i % 4) * 1024);
+    dma16_m0(dlane[i % 4] + uo, db_a + ((it & (DB - 1)) * PB + i / 4) * 4096 + (i % 4) * 1024);
   };
   // ---- a drain step = rows r16 + 16 t of block b of a finished stripe: da, statistics, planes of a -- as NQ operations of four INDEPENDENT instructions
   // each, issued in the shadow of one MFMA each.  (A wave alone on its SIMD issues in order: an instruction that waits for the one before it -- the
@@ -217,10 +198,9 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
       dd0 = *reinterpret_cast<const float4*>(dp + (((2 * c8) ^ rsw) << 4)); dd1 = *reinterpret_cast<const float4*>(dp + (((2 * c8 + 1) ^ rsw) << 4));
       dro = ((long)(first + itd * step) * PX + 32 * b + 16 * t) * p.N;   // wave-uniform
     } else if constexpr (op == 2) {
-      if (!(PRES_EXP & 256)) *reinterpret_cast<float4*>(ylane + dro) = dv0;
+      *reinterpret_cast<float4*>(ylane + dro) = dv0;
     } else if constexpr (op == 3) {
-      if (!(PRES_EXP & 256)) *reinterpret_cast<float4*>(ylane + dro + 4) = dv1;
-    } else if constexpr (op < 22 && (PRES_EXP & 512)) {
+      *reinterpret_cast<float4*>(ylane + dro + 4) = dv1;
     } else if constexpr (op < 6) {                              // tt = d * scale + shift (scalar VALU forms: packed fp32 contends with the matrix pipe)
 #pragma unroll
       for (int e = 4 * (op - 4); e < 4 * (op - 4) + 4; ++e) dtt[e] = fma_unpacked(DE(e), bsc[e], bsh[e]);
@@ -277,7 +257,6 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
   bf16x8_t fx[NPL][PB];
   const int lofs = l31 * 128;
   int cbase = 0;                                               // ring slot of the stripe's first stage
-  const unsigned long long tr0 = (PRES_EXP & 128) ? __builtin_amdgcn_s_memtime() : 0ull, rr0 = (PRES_EXP & 128) ? __builtin_amdgcn_s_memrealtime() : 0ull;
   // one stripe; DRAINS: the stripe before it leaves meanwhile (all but the first), WARMC: the steady-state load counts hold -- compile-time, so that the
   // gaps between the MFMAs carry straight-line code
   auto stripe = [&](int it, auto DRAINS, auto WARMC) __attribute__((always_inline)) {
@@ -288,8 +267,8 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
       constexpr int NOPD = j == JD ? 4 * PB : 0, NOP = NOPD + PPW, OSTR = (4 * NM) / NOP;
       static_assert(OSTR >= 1, "more DMA pieces than gaps");
       // every piece of stage lin + 1 this wave issued has landed: the loads issued since are (R - 3) stages + the d pieces of the stripes opened meanwhile
-      if (!(PRES_EXP & 64)) pr_wait_vm<(R - 3) * PPW + (warm ? 4 * PB * pr_opens(j - JD, R, KST) : 0)>();
-      if (!(PRES_EXP & 16)) __builtin_amdgcn_s_barrier();      // stage lin + 1 is in LDS (all waves); stage lin - 1's slot is free
+      wait_vm<(R - 3) * PPW + (warm ? 4 * PB * pr_opens(j - JD, R, KST) : 0)>();
+      __builtin_amdgcn_s_barrier();      // stage lin + 1 is in LDS (all waves); stage lin - 1's slot is free
       const int cslot = cbase + j >= R ? cbase + j - R : cbase + j, nslot = cslot + 1 == R ? 0 : cslot + 1, islot = cslot == 0 ? R - 1 : cslot - 1;
       const unsigned char* A = smem + cslot * STAGE + lofs;
       const unsigned char* An = smem + nslot * STAGE + lofs;
@@ -298,7 +277,7 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
 #pragma unroll
           for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
-            for (int b = 0; b < PB; ++b) fx[pl][b] = pr_frag(A + (pl * PB + b) * 4096 + ((half ^ sw) << 4));
+            for (int b = 0; b < PB; ++b) fx[pl][b] = frag16(A + (pl * PB + b) * 4096 + ((half ^ sw) << 4));
         }
       }
       pr_for<4>([&](auto KS) __attribute__((always_inline)) {
@@ -308,14 +287,12 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
-          for (int b = 0; b < PB; ++b) { if (PRES_EXP & 4) nx[pl][b] = fx[pl][b]; else nx[pl][b] = pr_frag(src + (pl * PB + b) * 4096); }
+          for (int b = 0; b < PB; ++b) nx[pl][b] = frag16(src + (pl * PB + b) * 4096);
         __builtin_amdgcn_sched_barrier(0);                     // reads of the next k-step first, then this k-step's MFMAs, each followed by what issues in its shadow
         pr_for<NM>([&](auto MI) __attribute__((always_inline)) {
           constexpr int m = decltype(MI)::value, t = T0 + m / PB, b = m % PB;
-          if (!(PRES_EXP & 2)) {
-            if (sl == 0 && m < PB) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[PWp[t]][j][ks], fx[PXp[t]][b], zero16, 0, 0, 0);   // C = 0: no clearing pass
-            else acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[PWp[t]][j][ks], fx[PXp[t]][b], acc[b], 0, 0, 0);
-          } else if (sl == 0 && m < PB) acc[b] = zero16;
+          if (sl == 0 && m < PB) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[PWp[t]][j][ks], fx[PXp[t]][b], zero16, 0, 0, 0);   // C = 0: no clearing pass
+          else acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[PWp[t]][j][ks], fx[PXp[t]][b], acc[b], 0, 0, 0);
           constexpr int gs = ks * NM + m;                      // gap of the stage
           if constexpr (gs % OSTR == 0 && gs / OSTR < NOP) {
             constexpr int o = gs / OSTR;
@@ -324,13 +301,11 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
           }
           constexpr int dg = sl * NM + m - NM;                 // gap of the stripe, counted from its second k-step: the previous stripe's drain
           if constexpr (drains && dg >= 0 && dg * OPG < NQ * NDR) {
-            if (!(PRES_EXP & 1)) {
-              if constexpr (dg == 0) pr_wait_vm<ND>();         // its rows of d have landed (issued a whole stripe ago)
-              pr_for<OPG>([&](auto OI) __attribute__((always_inline)) {
-                constexpr int dq = dg * OPG + decltype(OI)::value;
-                if constexpr (dq < NQ * NDR) drain_op(it - 1, (dq / NQ) / 2, (dq / NQ) % 2, std::integral_constant<int, dq % NQ>{});
-              });
-            }
+            if constexpr (dg == 0) wait_vm<ND>();           // its rows of d have landed (issued a whole stripe ago)
+            pr_for<OPG>([&](auto OI) __attribute__((always_inline)) {
+              constexpr int dq = dg * OPG + decltype(OI)::value;
+              if constexpr (dq < NQ * NDR) drain_op(it - 1, (dq / NQ) / 2, (dq / NQ) % 2, std::integral_constant<int, dq % NQ>{});
+            });
           }
           __builtin_amdgcn_sched_barrier(0);
         });
@@ -345,7 +320,6 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
     // pixel l31: 16-byte piece 2 g + half of row l31 at position piece ^ ((l31 >> 1) & 7)
 #pragma unroll
     for (int b = 0; b < PB; ++b) {
-      if (PRES_EXP & 32) { if (acc[b][0] + acc[b][5] + acc[b][10] == 1.2345f) Tt[0] = 1; continue; }
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         *reinterpret_cast<float4*>(Tt + b * 4096 + lofs + (((2 * g + half) ^ sw) << 4)) = make_float4(acc[b][4 * g], acc[b][4 * g + 1], acc[b][4 * g + 2], acc[b][4 * g + 3]);
@@ -357,18 +331,12 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
     for (; it < mine && it < WARM; ++it) stripe(it, std::true_type{}, std::false_type{});
     for (; it < mine; ++it) stripe(it, std::true_type{}, std::true_type{});
   }
-  if ((PRES_EXP & 128) && tid == 0) {   // [workgroup]: shader cycles, 100 MHz ticks, stripes of the main loop, ticks of the prologue
-    unsigned long long* tr = reinterpret_cast<unsigned long long*>(p.Y) + 4 * wg;
-    tr[0] = __builtin_amdgcn_s_memtime() - tr0; tr[1] = __builtin_amdgcn_s_memrealtime() - rr0; tr[2] = (unsigned long long)mine; tr[3] = rr0 - re0;
-  }
   // ---- the last stripe
-  pr_wait_vm<0>();
-  if (!(PRES_EXP & 1)) {
-    pr_for<NDR>([&](auto MI) __attribute__((always_inline)) {
-      constexpr int m = decltype(MI)::value;
-      pr_for<NQ>([&](auto OPC) __attribute__((always_inline)) { drain_op(mine - 1, m / 2, m % 2, OPC); });
-    });
-  }
+  wait_vm<0>();
+  pr_for<NDR>([&](auto MI) __attribute__((always_inline)) {
+    constexpr int m = decltype(MI)::value;
+    pr_for<NQ>([&](auto OPC) __attribute__((always_inline)) { drain_op(mine - 1, m / 2, m % 2, OPC); });
+  });
   // lanes with the same channels: lane, lane + 4, + 8, ...
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -384,21 +352,20 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
   }
 }
 
-#ifndef PRES_R8
-#define PRES_R8 6     // ring stages at K = 512 (16 KiB each with two planes and 64-pixel stripes)
-#define PRES_PB8 2    // 32-pixel blocks per stripe at K = 512: consecutive MFMAs go to different result blocks
-#define PRES_DB8 1    // buffers for the rows of d at K = 512
-#define PRES_R4 4     // K = 256
-#define PRES_PB4 2    // 32-pixel blocks per stripe at K = 256
-#define PRES_OCC4 1   // workgroups per CU at K = 256
-#endif
+// the two-plane shapes: profiles/r06_pres_bench.txt
+constexpr int kPresR8 = 6;     // ring stages at K = 512 (16 KiB each with two planes and 64-pixel stripes)
+constexpr int kPresPb8 = 2;    // 32-pixel blocks per stripe at K = 512: consecutive MFMAs go to different result blocks
+constexpr int kPresDb8 = 1;    // buffers for the rows of d at K = 512
+constexpr int kPresR4 = 4;     // K = 256
+constexpr int kPresPb4 = 2;    // 32-pixel blocks per stripe at K = 256
+constexpr int kPresOcc4 = 1;   // workgroups per CU at K = 256
 
 struct PresShape { int kst, pb, occ, r; };
 bool pres_shape(int N, int K, int planes, PresShape& s) {
   if (K != 256 && K != 512) return false;
   if (planes == 3 && K == 512) return false;                   // 384 registers of planes + three chains: not built
   s.kst = K / 64;
-  s.pb = K == 512 ? PRES_PB8 : PRES_PB4; s.occ = K == 512 ? 1 : PRES_OCC4; s.r = K == 512 ? PRES_R8 : PRES_R4;
+  s.pb = K == 512 ? kPresPb8 : kPresPb4; s.occ = K == 512 ? 1 : kPresOcc4; s.r = K == 512 ? kPresR8 : kPresR4;
   if (planes == 3) { s.pb = 1; s.occ = 1; s.r = 8; }
   return N >= 128 && N % 128 == 0 && N <= 1024;
 }
@@ -435,8 +402,8 @@ int pres_launch(const PresParams& p, int grid, hipStream_t stream) {
 template <int NPL, int NPA>
 int pres_dispatch(const PresParams& p, const PresShape& s, int grid, hipStream_t stream) {
   if constexpr (NPL == 2) {
-    if (s.kst == 8) return pres_launch<8, 2, PRES_PB8, PRES_R8, 1, NPA, PRES_DB8>(p, grid, stream);
-    return pres_launch<4, 2, PRES_PB4, PRES_R4, PRES_OCC4, NPA, 2>(p, grid, stream);
+    if (s.kst == 8) return pres_launch<8, 2, kPresPb8, kPresR8, 1, NPA, kPresDb8>(p, grid, stream);
+    return pres_launch<4, 2, kPresPb4, kPresR4, kPresOcc4, NPA, 2>(p, grid, stream);
   } else {
     if (s.kst == 4) return pres_launch<4, 3, 1, 8, 1, NPA, 2>(p, grid, stream);
     return CRNN_ERR_UNSUPPORTED;

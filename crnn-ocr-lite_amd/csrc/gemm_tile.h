@@ -6,13 +6,11 @@
 //   gemm_planes.hip  products from two / three bf16 planes on producer waves, crnn_split3_planes
 #pragma once
 #include "common.h"
+#include "stream_ops.h"
 
 #define HBK 64                 // fp32 k per chunk of the bf16-family kernels
 #define HLD (HBK + 8)          // bf16 row stride of the row-major-in-k layout (144 B)
-#ifndef CRNN_KLD_PAD
-#define CRNN_KLD_PAD 32
-#endif
-#define KLD(ROWS) ((ROWS) + CRNN_KLD_PAD)   // bf16 row stride of the k-major layout
+#define KLD(ROWS) ((ROWS) + 32)   // bf16 row stride of the k-major layout (pad 32 = 64 B: the transposing fragment reads stay conflict-free)
 #define TR_TAB 512             // channels the prologue's LDS table holds (K <= 512 in modes 0/1; the 128 tile rows in mode 2)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -110,7 +108,6 @@ __device__ __forceinline__ TileCoord gemm_tile_coord(const GemmParams& p) {
 }
 
 // fragment = the 8 bf16 (k = 16*ks + 8*half .. +7) of row r0 + l31
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 template <bool KM, int ROWS>
 __device__ __forceinline__ bf16x8 read_frag_h(const void* Xs, int r0, int ks, int half, int l31) {
   uint4 w;

@@ -18,14 +18,7 @@
 // Same products as the tile kernel (bf16 operands, fp32 accumulation); the reduction is grouped differently (other range
 // boundaries), so the result agrees to fp32 summation round-off, not bit for bit.
 #include "common.h"
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-#ifndef CRNN_WG_EXP
-#define CRNN_WG_EXP 0     // compile-time ablation mask (scripts/wgrad_bench.py --ablate): 1 no transform, 2 no fragment reads / MFMAs, 4 no global loads
-#endif
+#include "stream_ops.h"
 
 namespace {
 
@@ -40,9 +33,6 @@ struct WgParams {
   int lda, ldg;      // row strides of D and G in elements (bf16 convs: K and N)
   int flat;          // more tiles than an XCD has CUs (round 5, dense1: 36): grid = tiles * nsplit, id -> (tile = id % tiles, range = id / tiles) -- a range's
                      // tiles spread over the XCDs (one XCD would run 32 of them and then the other 4: twice the time, measured)
-#ifdef CRNN_WG_TRACE
-  unsigned long long* trace;   // [2][64][4] s_memrealtime stamps of workgroup 8: IO wave 4, MFMA wave 0
-#endif
 };
 
 constexpr int kLd = 128 + 32;                 // bf16 row stride of a k-major operand stage (320 B)
@@ -58,50 +48,17 @@ __device__ __forceinline__ unsigned wg_bnrelu6_pair(unsigned w, f32x2_t s, f32x2
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
 }
 
-// fragment = the 8 bf16 (k = 16 ks + 8 half .. +7) of tile row r0 + l31, from a k-major stage (as gemm_tile.h read_frag_h<true>)
-__device__ __forceinline__ bf16x8_t wg_frag(const unsigned char* Xs, int r0, int ks, int half, int l31) {
-  const int li = l31 & 15;
-  const unsigned short* X = reinterpret_cast<const unsigned short*>(Xs) + (ks * 16 + 8 * half + (li >> 2)) * kLd + r0 + (l31 & 16) + (li & 3) * 4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)X);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(X + 4 * kLd));
-  const uint2 a = __builtin_bit_cast(uint2, lo), b = __builtin_bit_cast(uint2, hi);
-  return __builtin_bit_cast(bf16x8_t, make_uint4(a.x, a.y, b.x, b.y));
-}
-
 // ---- GDMA (round 6, bf16 operands): g is only copied -- its stages come by LDS-DMA from four loader waves into a ring of their own instead of through the IO waves'
 // registers (as gemm_wgrad3.hip, where taking g off the IO waves was worth 11 %): a stage = 64 pixel rows x 256 B (128 channels, unpadded: the DMA's LDS image is
 // lane-linear), 16-byte chunk c of row r at position c ^ ((r & 3) << 2) on the source address, so that the transposing fragment reads stay conflict-free.
 constexpr int kOpB = 64 * 256;                // bytes of one g stage
-#ifndef WG_RINGB
-#define WG_RINGB 6
-#endif
-#ifndef WG_LOADERS
-#define WG_LOADERS 4
-#endif
-#ifndef WG_GDMA
-#define WG_GDMA 1
-#endif
-constexpr int kRingB = WG_RINGB;                     // stages of the g ring (5 in flight per CU: 80 KiB)
-constexpr int kLoaders = WG_LOADERS;                   // loader waves (one sustains ~25 GB/s per CU)
-__device__ __forceinline__ unsigned wg_lds_addr(const void* p) { return (unsigned)(uintptr_t)((__attribute__((address_space(3))) const unsigned char*)p); }
-__device__ __forceinline__ void wg_dma16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ bf16x8_t wg_frag_sw(const unsigned char* Xs, int r0, int ks, int half, int l31) {
-  const int li = l31 & 15;
-  const int row = ks * 16 + 8 * half + (li >> 2), col = r0 + (l31 & 16) + (li & 3) * 4;
-  const unsigned short* X = reinterpret_cast<const unsigned short*>(Xs) + row * 128 + ((((col >> 3) ^ ((row & 3) << 2)) << 3) | (col & 7));
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)X);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(X + 4 * 128));
-  const uint2 a = __builtin_bit_cast(uint2, lo), b = __builtin_bit_cast(uint2, hi);
-  return __builtin_bit_cast(bf16x8_t, make_uint4(a.x, a.y, b.x, b.y));
-}
+constexpr int kRingB = 6;                     // stages of the g ring (5 in flight per CU: 80 KiB); as gemm_wgrad3.hip: profiles/r06_wgrad3_ablate.txt
+constexpr int kLoaders = 4;                   // loader waves (one sustains ~25 GB/s per CU)
 
 // F32: both operands are fp32 tensors rounded to bf16 on the way in (v_cvt_pk_bf16_f32, RNE -- what the tile GEMM does while it stages
 // them), no BatchNorm transform: the weight gradients of the recurrent layers, dW = X^T dZ and dU = H^T dZ over the T*B rows
 // XF = false (bf16 operands): no BatchNorm transform either -- round 5, dense1's weight gradient dW1 = x7^T gbm over bf16 tensors
-template <int NIO, bool F32, bool XF = true, bool GDMA = false>   // IO waves (4 or 8): 16 / NIO 8-channel pieces of each operand per lane and chunk; GDMA: g by loader waves
+template <int NIO, bool F32, bool XF = true, bool GDMA = false>   // IO waves (8; the four-wave form is gone): 16 / NIO 8-channel pieces of each operand per lane and chunk; GDMA: g by loader waves
 __global__ __launch_bounds__(256 + 64 * NIO + (GDMA ? 64 * kLoaders : 0)) void pw_wgrad_stream_kernel(WgParams p) {
   static_assert(!GDMA || !F32, "the loader waves copy bf16 rows");
   constexpr int STA = GDMA ? kOp : 2 * kOp;                     // bytes of an IO-wave stage (GDMA: the a operand only)
@@ -124,12 +81,12 @@ __global__ __launch_bounds__(256 + 64 * NIO + (GDMA ? 64 * kLoaders : 0)) void p
       // ---------------------------------------------------------------------- loader waves: the 16 1-KiB pieces of a g stage (piece pi = rows 4 pi + (lane >> 4), chunk
       // position lane & 15), a quarter each, kRingB - 1 stages ahead; one counted wait and one barrier per chunk
       const int lw = wave - (4 + NIO);
-      const unsigned bring = __builtin_amdgcn_readfirstlane(wg_lds_addr(smem + kRing * kOp));
+      const unsigned bring = __builtin_amdgcn_readfirstlane(lds_addr(smem + kRing * kOp));
       const bf16_t* gl = p.G + (long)(lane >> 4) * p.ldg + tj * 128 + 8 * ((lane & 15) ^ (((lane >> 4) & 3) << 2));
       auto issue_b = [&](int st, int sb) __attribute__((always_inline)) {
         const long uo = (long)(c0 + (st < total ? st : total - 1)) * 64 * p.ldg;   // (past the end: the last chunk again, into a slot whose stage has been consumed)
 #pragma unroll
-        for (int q = 0; q < 16 / kLoaders; ++q) wg_dma16(gl + uo + (long)(4 * (lw + q * kLoaders)) * p.ldg, bring + sb * kOpB + (lw + q * kLoaders) * 1024);
+        for (int q = 0; q < 16 / kLoaders; ++q) dma16_m0(gl + uo + (long)(4 * (lw + q * kLoaders)) * p.ldg, bring + sb * kOpB + (lw + q * kLoaders) * 1024);
       };
 #pragma unroll
       for (int s0 = 0; s0 < kRingB - 1; ++s0) issue_b(s0, s0);
@@ -158,26 +115,18 @@ __global__ __launch_bounds__(256 + 64 * NIO + (GDMA ? 64 * kLoaders : 0)) void p
         for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
     int slot = 0, slotb = 0;
     for (int s = 0; s < total; ++s) {
-#ifdef CRNN_WG_TRACE
-      const bool tr = p.trace && wg == 8 && wave == 0 && lane == 0 && s < 64;
-      if (tr) p.trace[256 + s * 4 + 0] = __builtin_amdgcn_s_memrealtime();
-#endif
       __builtin_amdgcn_s_barrier();                             // stage s is in LDS; stage s-1's slot is released
-#ifdef CRNN_WG_TRACE
-      if (tr) p.trace[256 + s * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
       const unsigned char* As = smem + slot * STA;
       const unsigned char* Bs = GDMA ? smem + kRing * kOp + slotb * kOpB : As + kOp;
       slot = slot + 1 == kRing ? 0 : slot + 1;
       slotb = slotb + 1 == kRingB ? 0 : slotb + 1;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        if (CRNN_WG_EXP & 2) continue;
         bf16x8_t fa[2], fb[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) fa[i] = wg_frag(As, wm * 64 + i * 32, ks, half, l31);
+        for (int i = 0; i < 2; ++i) fa[i] = frag_tr<kLd>(As, wm * 64 + i * 32, ks, half, l31);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fb[j] = GDMA ? wg_frag_sw(Bs, wn * 64 + j * 32, ks, half, l31) : wg_frag(Bs, wn * 64 + j * 32, ks, half, l31);
+        for (int j = 0; j < 2; ++j) fb[j] = GDMA ? frag_tr_sw(Bs, wn * 64 + j * 32, ks, half, l31) : frag_tr<kLd>(Bs, wn * 64 + j * 32, ks, half, l31);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -215,7 +164,6 @@ __global__ __launch_bounds__(256 + 64 * NIO + (GDMA ? 64 * kLoaders : 0)) void p
   auto load1 = [&](int s, int u, u32x4* xa, u32x4* xg) {       // RW registers each
     s = s < total ? s : total - 1;                              // past the end: a valid address, the data lands in a consumed slot
     const long row = (long)(c0 + s) * 64 + pxl + 4 * NIO * u;
-    if (CRNN_WG_EXP & 4) { xa[0] = u32x4{(unsigned)s, 0u, 0u, 0u}; xg[0] = xa[0]; if (F32) { xa[RW - 1] = xa[0]; xg[RW - 1] = xa[0]; } return; }
     if constexpr (F32) {
       const float* pa = reinterpret_cast<const float*>(dbase) + row * p.lda; const float* pg = reinterpret_cast<const float*>(gbase) + row * p.ldg;
       xa[0] = *reinterpret_cast<const u32x4*>(pa); xa[1] = *reinterpret_cast<const u32x4*>(pa + 4);
@@ -241,7 +189,7 @@ __global__ __launch_bounds__(256 + 64 * NIO + (GDMA ? 64 * kLoaders : 0)) void p
     if constexpr (F32) { o = round8(xa[0], xa[1]); og = round8(xg[0], xg[1]); }
     else {
       og = xg[0];
-      if ((CRNN_WG_EXP & 1) || !XF) o = xa[0]; else {
+      if (!XF) o = xa[0]; else {
         o.x = wg_bnrelu6_pair(xa[0].x, sc[0], sh[0]); o.y = wg_bnrelu6_pair(xa[0].y, sc[1], sh[1]);
         o.z = wg_bnrelu6_pair(xa[0].z, sc[2], sh[2]); o.w = wg_bnrelu6_pair(xa[0].w, sc[3], sh[3]);
       }
@@ -266,22 +214,9 @@ __global__ __launch_bounds__(256 + 64 * NIO + (GDMA ? 64 * kLoaders : 0)) void p
   };
   // barrier s (s = 0 .. total): before it stage s is written; after it the slot of stage s-1 is free -> stage s+2 goes there
   auto step = [&](int s, u32x4 (&xa)[NP * RW], u32x4 (&xg)[NP * RW]) {   // xa/xg = buffer (s + 2) % kD
-#ifdef CRNN_WG_TRACE
-    const bool tr = p.trace && wg == 8 && w == 0 && lane == 0 && s < 64;
-    if (tr) p.trace[s * 4 + 0] = __builtin_amdgcn_s_memrealtime();
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef CRNN_WG_TRACE
-    if (tr) p.trace[s * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
     __builtin_amdgcn_s_barrier();
-#ifdef CRNN_WG_TRACE
-    if (tr) p.trace[s * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-#endif
     write_load(s + 2, s + 2 + kD, xa, xg);
-#ifdef CRNN_WG_TRACE
-    if (tr) p.trace[s * 4 + 3] = __builtin_amdgcn_s_memrealtime();
-#endif
   };
 #pragma unroll
   for (int k = 0; k < kD; ++k) load(k, ra[k], rg[k]);
@@ -367,25 +302,16 @@ template <bool F32, bool XF = true>
 int wg_launch(WgParams& p, long M, float* out, int ldc, float* scratch, size_t scratch_bytes, hipStream_t stream) {
   int grid;
   wg_geom(M, p.N, p.K, p, grid);
-#ifdef CRNN_WG_TRACE
-  { const char* e = getenv("CRNN_WG_TRACE"); p.trace = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
-#endif
   if ((size_t)p.nsplit * p.K * p.N * sizeof(float) > scratch_bytes) return CRNN_ERR_UNSUPPORTED;
-  const int lds = kRing * 2 * kOp;
-  bool done = false;
   if constexpr (!F32 && XF) {   // the pointwise convolutions' form (bf16 d with the BatchNorm transform, bf16 g): g by LDS-DMA from loader waves
-    if (crnn_knob("CRNN_WG_GDMA", WG_GDMA) && (p.ldg & 7) == 0 && (((uintptr_t)p.G) & 15) == 0) {
-      const int ldsd = kRing * kOp + kRingB * kOpB;
-      CRNN_LDS_ATTR((pw_wgrad_stream_kernel<8, false, true, true>), ldsd);
-      hipLaunchKernelGGL((pw_wgrad_stream_kernel<8, false, true, true>), dim3(grid), dim3(256 + 64 * 8 + 64 * kLoaders), ldsd, stream, p);
-      done = true;
-    }
-  }
-  if (!done) {
-  CRNN_LDS_ATTR((pw_wgrad_stream_kernel<4, F32, XF>), lds);
-  CRNN_LDS_ATTR((pw_wgrad_stream_kernel<8, F32, XF>), lds);
-  if (crnn_knob("CRNN_WG_NIO", 8) == 4) hipLaunchKernelGGL((pw_wgrad_stream_kernel<4, F32, XF>), dim3(grid), dim3(512), lds, stream, p);
-  else hipLaunchKernelGGL((pw_wgrad_stream_kernel<8, F32, XF>), dim3(grid), dim3(768), lds, stream, p);
+    // (its one caller has checked what the DMA needs: g 16-byte aligned, N = ldg a multiple of 128)
+    const int ldsd = kRing * kOp + kRingB * kOpB;
+    CRNN_LDS_ATTR((pw_wgrad_stream_kernel<8, false, true, true>), ldsd);
+    hipLaunchKernelGGL((pw_wgrad_stream_kernel<8, false, true, true>), dim3(grid), dim3(256 + 64 * 8 + 64 * kLoaders), ldsd, stream, p);
+  } else {
+    const int lds = kRing * 2 * kOp;
+    CRNN_LDS_ATTR((pw_wgrad_stream_kernel<8, F32, XF>), lds);
+    hipLaunchKernelGGL((pw_wgrad_stream_kernel<8, F32, XF>), dim3(grid), dim3(768), lds, stream, p);
   }
   CRNN_LAUNCH_CHECK();
   const long total = (long)p.K * p.N;
@@ -783,7 +709,7 @@ static int nts_launch(const float* A0, const void* W0, const float* A1, const vo
   CRNN_LDS_ATTR(gemm_nt_f32_stream_kernel<2>, kNtsRing * (64 * 128 + 256 * 128));
   CRNN_LDS_ATTR((gemm_nt_f32_stream_kernel<1, false, 2>), 2 * kNtsRing * (64 * 128 + 128 * 128));
   // 128-column slabs with an even number of chunks: two chunks per stage and barrier (144 KiB of ring; the 256-column slab's would not fit)
-  if (slab == 128 && ((K / 64) * p.npairs) % 2 == 0 && crnn_knob("CRNN_NTS_KC", 2) == 2)
+  if (slab == 128 && ((K / 64) * p.npairs) % 2 == 0)
     hipLaunchKernelGGL((gemm_nt_f32_stream_kernel<1, false, 2>), dim3(M / 64, N / slab), dim3(768), 2 * lds, stream, p);
   else if (slab == 128) hipLaunchKernelGGL(gemm_nt_f32_stream_kernel<1>, dim3(M / 64, N / slab), dim3(768), lds, stream, p);
   else hipLaunchKernelGGL(gemm_nt_f32_stream_kernel<2>, dim3(M / 64, N / slab), dim3(768), lds, stream, p);
@@ -810,9 +736,9 @@ extern "C" int crnn_dense_fwd_stream(const void* X, const void* WT, const float*
   // (drop_rate > 0: the dropout decision depends on the row index anyway) take it; inference launches walk the chunks in ascending order in every workgroup,
   // so that a sample's activations do not depend on its position in the batch or on the batch size (round 6, ADVICE; test_dense1_stream_inference_rows_do_
   // not_depend_on_their_position).
-  p.relu = relu; p.permP = permP; p.drop_rate = drop_rate; p.seed = seed; p.layer = layer; p.skew = drop_rate > 0.f ? crnn_knob("CRNN_NTS_SKEW", 3) : 0;
+  p.relu = relu; p.permP = permP; p.drop_rate = drop_rate; p.seed = seed; p.layer = layer; p.skew = drop_rate > 0.f ? 3 : 0;
   const int lds = kNtsRing * (64 * 128 + N * 128);
-  if (N == 128 && (K / 64) % 2 == 0 && crnn_knob("CRNN_NTS_KC", 2) == 2) {
+  if (N == 128 && (K / 64) % 2 == 0) {
     CRNN_LDS_ATTR((gemm_nt_f32_stream_kernel<1, true, 2>), 2 * lds);
     hipLaunchKernelGGL((gemm_nt_f32_stream_kernel<1, true, 2>), dim3((unsigned)(M / 64), 1), dim3(768), 2 * lds, stream, p);
   } else if (N == 128) { CRNN_LDS_ATTR((gemm_nt_f32_stream_kernel<1, true>), lds); hipLaunchKernelGGL((gemm_nt_f32_stream_kernel<1, true>), dim3((unsigned)(M / 64), 1), dim3(768), lds, stream, p); }

@@ -17,10 +17,7 @@
 //     [range][K][N] and a fixed-order second stage sums them (deterministic).
 // Same planes and products as the tile kernel; the reduction is grouped differently (other range boundaries): equal to fp32 summation round-off.
 #include "common.h"
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+#include "stream_ops.h"
 
 namespace {
 
@@ -37,24 +34,10 @@ struct Wg3Params {
 constexpr int kLd3 = 128 + 32;                // bf16 row stride of a k-major operand plane (320 B)
 constexpr int kPl3 = 32 * kLd3 * 2;           // bytes of one plane of one operand stage: 32 pixels x 160 x 2 B = 10 KiB
 constexpr int kStage3 = 4 * kPl3;             // A hi | A mid | B hi | B mid
-#ifndef W3G_RING
-#define W3G_RING 3
-#define W3G_D 3
-#define W3G_WGS 1
-#endif
-constexpr int kRing3 = W3G_RING;              // LDS stages (2: 80 KiB, two workgroups per CU)
-constexpr int kD3 = W3G_D;                    // chunks in flight in the IO waves' registers
+// 3 stages, 3 chunks in flight, one workgroup per CU (2 stages = 80 KiB with two workgroups per CU lost): profiles/r06_wgrad3_ablate.txt
+constexpr int kRing3 = 3;                     // LDS stages
+constexpr int kD3 = 3;                        // chunks in flight in the IO waves' registers
 constexpr int kLead3 = kRing3 - 1;            // stage stored after barrier s: s + kLead3
-
-// fragment = the 8 bf16 (k = 16 ks + 8 half .. +7) of tile row r0 + l31, from a k-major plane (as gemm_tile.h read_frag_h<true>)
-__device__ __forceinline__ bf16x8_t wg3_frag(const unsigned char* Xs, int r0, int ks, int half, int l31) {
-  const int li = l31 & 15;
-  const unsigned short* X = reinterpret_cast<const unsigned short*>(Xs) + (ks * 16 + 8 * half + (li >> 2)) * kLd3 + r0 + (l31 & 16) + (li & 3) * 4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)X);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(X + 4 * kLd3));
-  const uint2 a = __builtin_bit_cast(uint2, lo), b = __builtin_bit_cast(uint2, hi);
-  return __builtin_bit_cast(bf16x8_t, make_uint4(a.x, a.y, b.x, b.y));
-}
 
 // ---- GPL (g as planes): the planes of g come by LDS-DMA issued by two more waves that do nothing else (as gemm_wres.hip's loader waves; issued by the MFMA waves
 // themselves the 16 pieces of a chunk cost them as much as they saved the IO waves: 205 -> 188 us only, profiles/r06_wgrad3_ablate.txt), into a ring of
@@ -65,24 +48,9 @@ constexpr int kStageB3 = 2 * kPlB3;           // hi | mid
 constexpr int kRingB3 = 6;                    // stages of the g ring (5 in flight per CU: 80 KiB)
 constexpr int kLoaders3 = 4;                  // loader waves (one sustains ~25 GB/s per CU -- MI355X_MICROARCH.md, measured here: 314 us with one)
 constexpr int kStageA3 = 2 * kPl3;            // GPL: the IO waves' stages hold the planes of a only
-__device__ __forceinline__ unsigned wg3_lds_addr(const void* p) { return (unsigned)(uintptr_t)((__attribute__((address_space(3))) const unsigned char*)p); }
-__device__ __forceinline__ void wg3_dma16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// fragment of tile row r0 + l31 from a swizzled, unpadded plane (row = pixel, 128 channels)
-__device__ __forceinline__ bf16x8_t wg3_frag_sw(const unsigned char* Xs, int r0, int ks, int half, int l31) {
-  const int li = l31 & 15;
-  const int row = ks * 16 + 8 * half + (li >> 2), col = r0 + (l31 & 16) + (li & 3) * 4;
-  const unsigned short* X = reinterpret_cast<const unsigned short*>(Xs) + row * 128 + ((((col >> 3) ^ ((row & 3) << 2)) << 3) | (col & 7));
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)X);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(X + 4 * 128));
-  const uint2 a = __builtin_bit_cast(uint2, lo), b = __builtin_bit_cast(uint2, hi);
-  return __builtin_bit_cast(bf16x8_t, make_uint4(a.x, a.y, b.x, b.y));
-}
 
 template <bool XF, bool GPL>   // XF: the A operand is ReLU6(d * scale + shift); GPL: g arrives split (written as planes by the kernel that produced it)
-__global__ __launch_bounds__(GPL ? 512 + 64 * kLoaders3 : 512, GPL ? 1 : 2 * W3G_WGS) void pw_wgrad_planes_kernel(Wg3Params p) {
+__global__ __launch_bounds__(GPL ? 512 + 64 * kLoaders3 : 512, GPL ? 1 : 2) void pw_wgrad_planes_kernel(Wg3Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // kRing3 stages
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -101,13 +69,13 @@ __global__ __launch_bounds__(GPL ? 512 + 64 * kLoaders3 : 512, GPL ? 1 : 2 * W3G
       const int lw = wave - 8;                                    // this loader's share: pieces lw, lw + kLoaders3, ...
       // ---------------------------------------------------------------------- loader wave: the 16 1-KiB pieces of a stage's g planes -- piece pi -> plane pi >> 3,
       // rows 4 (pi & 7) + (lane >> 4), chunk position lane & 15 -- kRingB3 - 1 stages ahead, one counted wait and one barrier per chunk
-      const unsigned bring = __builtin_amdgcn_readfirstlane(wg3_lds_addr(smem + kRing3 * kStageA3));
+      const unsigned bring = __builtin_amdgcn_readfirstlane(lds_addr(smem + kRing3 * kStageA3));
       const unsigned short* gl = p.GP + (long)(lane >> 4) * p.ldg + tj * 128 + 8 * ((lane & 15) ^ (((lane >> 4) & 3) << 2));
       auto issue_b = [&](int st, int sb) __attribute__((always_inline)) {
         const long uo = (long)(c0 + (st < total ? st : total - 1)) * 32 * p.ldg;   // (past the end: the last chunk again, into a slot whose stage has been consumed)
 #pragma unroll
         for (int pi = lw; pi < 16; pi += kLoaders3)
-          wg3_dma16(gl + uo + (long)(pi >> 3) * p.gps + (long)(4 * (pi & 7)) * p.ldg, bring + sb * kStageB3 + (pi >> 3) * kPlB3 + (pi & 7) * 1024);
+          dma16_m0(gl + uo + (long)(pi >> 3) * p.gps + (long)(4 * (pi & 7)) * p.ldg, bring + sb * kStageB3 + (pi >> 3) * kPlB3 + (pi & 7) * 1024);
       };
 #pragma unroll
       for (int s0 = 0; s0 < kRingB3 - 1; ++s0) issue_b(s0, s0);
@@ -149,9 +117,9 @@ __global__ __launch_bounds__(GPL ? 512 + 64 * kLoaders3 : 512, GPL ? 1 : 2 * W3G
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            fa[pl][i] = wg3_frag(As + pl * kPl3, wm * 64 + i * 32, ks, half, l31);
-            if constexpr (GPL) fb[pl][i] = wg3_frag_sw(Bs + pl * kPlB3, wn * 64 + i * 32, ks, half, l31);
-            else fb[pl][i] = wg3_frag(Bs + pl * kPl3, wn * 64 + i * 32, ks, half, l31);
+            fa[pl][i] = frag_tr<kLd3>(As + pl * kPl3, wm * 64 + i * 32, ks, half, l31);
+            if constexpr (GPL) fb[pl][i] = frag_tr_sw(Bs + pl * kPlB3, wn * 64 + i * 32, ks, half, l31);
+            else fb[pl][i] = frag_tr<kLd3>(Bs + pl * kPl3, wn * 64 + i * 32, ks, half, l31);
           }
         // a_mid g_hi, a_hi g_mid, a_hi g_hi (the tile kernel's order: small terms first); consecutive MFMAs on different accumulators
         constexpr int PA[3] = {1, 0, 0}, PG[3] = {0, 1, 0};
@@ -285,7 +253,7 @@ void wg3_geom(long M, int N, int K, Wg3Params& p, int& grid) {
   const int tiles = p.TI * p.TJ;
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  int ns = (W3G_WGS * cus / tiles) & ~7;                                  // one workgroup per CU, a multiple of 8 ranges (8 XCDs)
+  int ns = (cus / tiles) & ~7;                                  // one workgroup per CU, a multiple of 8 ranges (8 XCDs)
   p.flat = tiles > cus / 8;
   if (p.flat) ns = cus / tiles < 1 ? 1 : cus / tiles;           // (round 6: dense1's 36 feature tiles -- cus / tiles ranges, one workgroup per CU)
   else if (ns < 8) ns = 8;

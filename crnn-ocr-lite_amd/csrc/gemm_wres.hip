@@ -26,10 +26,7 @@
 // Numerics: the same MFMA and the same k order (64-k chunks ascending, 16-k steps ascending) as gemm_nt.hip / gemm_bf16.hip --
 // results are bit-identical.
 #include "common.h"
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "stream_ops.h"
 
 namespace {
 
@@ -46,28 +43,13 @@ struct WresParams {
   // staged stripe and the matching rows of d -- the stand-alone statistics pass (bn_bwd_kernel<1>) would read Y and d again
   const bf16_t* D; const float* bnstate;      // d [M][N]; [mean | var | scale | shift] x N
   float* stats;                               // [2 * Q * nxcd][2][N] partial sums, one row per storer wave and stripe lane
-#ifdef CRNN_WRES_EXP
-  unsigned long long* trace;   // ablation build only: [64 iterations][4] s_memrealtime stamps of workgroup 0's first loader wave
-  int exp;       // unused (the ablation mask is the compile-time value of CRNN_WRES_EXP: 1 no pixel loads, 2 no fragment reads, 8 no MFMAs, 4 no stores, 32 free-running loaders only)
-#endif
 };
-#ifdef CRNN_WRES_EXP   // compile-time ablation mask: run-time tests between the MFMAs would change what is being measured
-#define WRES_EXP(p, bit) ((CRNN_WRES_EXP) & (bit))
-#else
-#define WRES_EXP(p, bit) 0
-#endif
 
 constexpr int kStage = 128 * 128;           // 128 pixel rows x 64 k x 2 B
 constexpr int kR = 6;                       // ring stages
 constexpr int kOut = 128 * 256;             // one staging tile: 128 pixels x 128 channels x 2 B
 
-#ifndef CRNN_WRESF_NT
-#define CRNN_WRESF_NT 1    // round 5: the training forward reads d with nontemporal loads (not read again before the backward pass; cache policy only)
-#endif
 // (round 5: the data-gradient form reading dq -- its last use in the step -- with nontemporal LDS-DMA was measured: no effect on the step; plain DMA stays)
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // The MFMA role shared by the kernels below: wave `wave` (0..3) of a workgroup keeps rows n0 .. n0+31 of W [N][K] as A-operand
 // fragments, multiplies them with every 128-pixel stage the producers put into the ring (R slots at smem), and leaves each
@@ -111,7 +93,7 @@ __device__ __forceinline__ void wres_compute(const unsigned char* smem, unsigned
         bf16x8_t nx[PB];
         const unsigned char* src = ks < 3 ? A + (((2 * (ks + 1) + half) ^ sw) * 16) : An + ((half ^ sw) * 16);
 #pragma unroll
-        for (int b = 0; b < PB; ++b) if (!WRES_EXP(p, 2)) nx[b] = *reinterpret_cast<const bf16x8_t*>(src + b * 32 * 128);
+        for (int b = 0; b < PB; ++b) nx[b] = *reinterpret_cast<const bf16x8_t*>(src + b * 32 * 128);
         // pin the order "reads of the next k-step, then this k-step's MFMAs": left alone the scheduler shares two fragment
         // registers between all reads and the MFMA pipe waits out an LDS round trip every second MFMA
         __builtin_amdgcn_sched_barrier(0);
@@ -119,7 +101,6 @@ __device__ __forceinline__ void wres_compute(const unsigned char* smem, unsigned
         for (int b = 0; b < PB; ++b)
 #pragma unroll
           for (int cb = 0; cb < CB; ++cb) {
-            if (WRES_EXP(p, 8)) continue;
             if (kc == 0 && ks == 0) acc[b][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[cb][kc][ks], fx[b], zero16, 0, 0, 0);   // C = 0: no clearing pass
             else acc[b][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[cb][kc][ks], fx[b], acc[b][cb], 0, 0, 0);
           }
@@ -280,12 +261,7 @@ __global__ __launch_bounds__(384 + 64 * NLW) void gemm_wres_kernel(WresParams p)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // workgroup -> (xcd, slice, stripe lane): consecutive ids go to consecutive XCDs
   const int wg = blockIdx.x;
-#ifdef CRNN_WRES_EXP
-  const int per = gridDim.x / p.nxcd;
-  const int x = WRES_EXP(p, 16) ? wg / per : wg % p.nxcd, j = WRES_EXP(p, 16) ? wg % per : wg / p.nxcd;
-#else
   const int x = wg % p.nxcd, j = wg / p.nxcd;
-#endif
   const int slice = j % p.S, q = j / p.S;
   const int step = p.Q * p.nxcd;                              // stripe stride between this workgroup's iterations
   const int first = q * p.nxcd + x;
@@ -334,11 +310,11 @@ __global__ __launch_bounds__(384 + 64 * NLW) void gemm_wres_kernel(WresParams p)
           const s16x8 a = __builtin_elementwise_max(__builtin_bit_cast(s16x8, v[0]), __builtin_bit_cast(s16x8, v[1]));
           const s16x8 b = __builtin_elementwise_max(__builtin_bit_cast(s16x8, v[2]), __builtin_bit_cast(s16x8, v[3]));
           if constexpr (POOL == 4) {
-            if (m0 + rb < p.M && !WRES_EXP(p, 4))
+            if (m0 + rb < p.M)
               *reinterpret_cast<u32x4*>(p.Y + (long)((m0 + rb) >> 2) * p.N + slice * 128 + c * 8) = __builtin_bit_cast(u32x4, __builtin_elementwise_max(a, b));
           } else {
-            if (m0 + rb < p.M && !WRES_EXP(p, 4)) *reinterpret_cast<u32x4*>(p.Y + (long)((m0 + rb) >> 1) * p.N + slice * 128 + c * 8) = __builtin_bit_cast(u32x4, a);
-            if (m0 + rb + 2 < p.M && !WRES_EXP(p, 4)) *reinterpret_cast<u32x4*>(p.Y + (long)(((m0 + rb) >> 1) + 1) * p.N + slice * 128 + c * 8) = __builtin_bit_cast(u32x4, b);
+            if (m0 + rb < p.M) *reinterpret_cast<u32x4*>(p.Y + (long)((m0 + rb) >> 1) * p.N + slice * 128 + c * 8) = __builtin_bit_cast(u32x4, a);
+            if (m0 + rb + 2 < p.M) *reinterpret_cast<u32x4*>(p.Y + (long)(((m0 + rb) >> 1) + 1) * p.N + slice * 128 + c * 8) = __builtin_bit_cast(u32x4, b);
           }
           continue;
         }
@@ -352,7 +328,7 @@ __global__ __launch_bounds__(384 + 64 * NLW) void gemm_wres_kernel(WresParams p)
         for (int u = 0; u < 4; ++u)
           if (t + u < t1) {
             const int r = (sw * 16 + t + u) * 4 + rsub;
-            if (m0 + r < p.M && !WRES_EXP(p, 4)) *reinterpret_cast<u32x4*>(p.Y + (long)(m0 + r) * p.N + slice * 128 + c * 8) = v[u];
+            if (m0 + r < p.M) *reinterpret_cast<u32x4*>(p.Y + (long)(m0 + r) * p.N + slice * 128 + c * 8) = v[u];
           }
       }
     };
@@ -383,35 +359,21 @@ __global__ __launch_bounds__(384 + 64 * NLW) void gemm_wres_kernel(WresParams p)
         int row = r0 + 8 * jrow + rsub;
         row = row < p.M ? row : p.M - 1;
         const int c = pos ^ ((4 * jrow + (lane >> 4)) & 7);
-        if (!WRES_EXP(p, 1)) glds16(p.X + row * ldk + kc * 64 + c * 8, dst + jrow * 1024);
+        glds16<0>(p.X + row * ldk + kc * 64 + c * 8, dst + jrow * 1024);
       }
     };
 #pragma unroll
     for (int s = 0; s < RR - 1; ++s) issue(s);
     for (int i = 0; i < total; ++i) {
-#ifdef CRNN_WRES_EXP
-      const bool tr = p.trace && wg == 8 && lw == 0 && lane == 0 && i < 64;
-      if (tr) p.trace[i * 4 + 0] = __builtin_amdgcn_s_memrealtime();
-#endif
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RR - 3) * kIPS) : "memory");   // stages i and i+1 have landed
-#ifdef CRNN_WRES_EXP
-      if (tr) p.trace[i * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
-      if (!WRES_EXP(p, 32)) __builtin_amdgcn_s_barrier();
-#ifdef CRNN_WRES_EXP
-      if (tr) p.trace[i * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-#endif
+      __builtin_amdgcn_s_barrier();
       issue(i + RR - 1);                                                        // into the slot stage i-1 has just released
-#ifdef CRNN_WRES_EXP
-      if (tr) p.trace[i * 4 + 3] = __builtin_amdgcn_s_memrealtime();
-#endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     return;
   }
 
   // -------------------------------------------------------------------- compute waves: 32 channels x K of W in registers
-  if (WRES_EXP(p, 32)) return;
   wres_compute<KCH, RR, 1, 4, EPI>(smem, outs, p.W, p.K, slice * 128 + wave * 32, wave, lane, mine, epi);
 }
 
@@ -446,12 +408,10 @@ __global__ __launch_bounds__(512) void gemm_wres_fwd_kernel(WresFwdParams p) {
   constexpr int CPL = PB;                                      // 16-byte stage chunks per IO lane and stage (PX rows x 8 chunks over 256 lanes)
   // stages in flight in the IO waves' registers: 64 KiB per CU for the deep-K shapes; the K <= 128 shapes are HBM-bound with a write
   // stream twice the read stream and run faster with 32 KiB (measured: 75 / 160 us against 85 / 178 us for blocks 2 / 3)
-#ifndef CRNN_WRESF_DEEP
-#define CRNN_WRESF_DEEP 1    // 1: stage depth trimmed for the deep-K shapes so that no register spills (round 4); 0: the round-2 depths
-#endif
   // (deep-K: 64 KiB in flight asked for pf[4][4] / pf[8][2] and left the K = 512 and K = 256 instantiations 5 and 8 registers short of their
   // 256-register ceiling -- scratch traffic in the IO waves' steady state; 48 KiB in flight fits)
-  constexpr int D = CRNN_WRESF_DEEP ? (KCH >= 8 ? 12 / PB : (KCH >= 4 ? (PB == 2 ? 6 : 4) : 8 / PB)) : (KCH >= 4 ? 16 : 8) / PB;
+  // (the round-2 depths (KCH >= 4 ? 16 : 8) / PB are gone; profiles/r04_wres_fwd_depth.txt)
+  constexpr int D = KCH >= 8 ? 12 / PB : (KCH >= 4 ? (PB == 2 ? 6 : 4) : 8 / PB);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // kRf stages | two staging tiles | scale[K] | shift[K]
   unsigned char* const outs = smem + kRf * stage;
   float* const tab = reinterpret_cast<float*>(outs + 2 * otile);
@@ -492,8 +452,8 @@ __global__ __launch_bounds__(512) void gemm_wres_fwd_kernel(WresFwdParams p) {
     const bf16_t* src = p.X + ((long)(first + it * step) * PX + 8 * PB * w + r8) * ldk + kc * 64 + c * 8;
 #pragma unroll
     for (int u = 0; u < CPL; ++u) {
-      if (CRNN_WRESF_NT) buf[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + (long)(8 * u) * ldk));
-      else buf[u] = *reinterpret_cast<const u32x4*>(src + (long)(8 * u) * ldk);
+      // nontemporal: d is not read again before the backward pass (cache policy only; profiles/r05_nt_loads_ab.txt)
+      buf[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + (long)(8 * u) * ldk));
     }
   };
   // (stages past the end are written too -- transformed junk from the clamped loads into a slot whose stage has been consumed:
@@ -507,12 +467,10 @@ __global__ __launch_bounds__(512) void gemm_wres_fwd_kernel(WresFwdParams p) {
     for (int u = 0; u < CPL; ++u) {
       const int row = 8 * (PB * w + u) + r8;
       u32x4 o;
-      if (WRES_EXP(p, 64)) o = buf[u]; else {
       o.x = wres_bnrelu6_pair(buf[u].x, f32x2_t{s0.x, s0.y}, f32x2_t{t0.x, t0.y});
       o.y = wres_bnrelu6_pair(buf[u].y, f32x2_t{s0.z, s0.w}, f32x2_t{t0.z, t0.w});
       o.z = wres_bnrelu6_pair(buf[u].z, f32x2_t{s1.x, s1.y}, f32x2_t{t1.x, t1.y});
       o.w = wres_bnrelu6_pair(buf[u].w, f32x2_t{s1.z, s1.w}, f32x2_t{t1.z, t1.w});
-      }
       *reinterpret_cast<u32x4*>(dst + row * 128 + ((c ^ ((row >> 1) & 7)) * 16)) = o;
     }
   };
@@ -532,11 +490,10 @@ __global__ __launch_bounds__(512) void gemm_wres_fwd_kernel(WresFwdParams p) {
     for (int t = t0; t < t1; ++t) {
       const int r = (w * 8 + t) * RG + rg;
       const u32x4 v = *reinterpret_cast<const u32x4*>(ob + r * orow + ((cN ^ (r & 15)) * 16));
-      if (!WRES_EXP(p, 4)) *reinterpret_cast<u32x4*>(p.Y + (m0 + r) * p.N + slice * NS + cN * 8) = v;
+      *reinterpret_cast<u32x4*>(p.Y + (m0 + r) * p.N + slice * NS + cN * 8) = v;
       const unsigned ww[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (WRES_EXP(p, 128)) { ssum[2 * e] = __uint_as_float(ww[e]); continue; }
         const float lo = __uint_as_float(ww[e] << 16), hi = __uint_as_float(ww[e] & 0xffff0000u);
         ssum[2 * e] += lo; ssq[2 * e] = fmaf(lo, lo, ssq[2 * e]);
         ssum[2 * e + 1] += hi; ssq[2 * e + 1] = fmaf(hi, hi, ssq[2 * e + 1]);
@@ -641,17 +598,9 @@ static int gemm_wres_impl(const void* X, const void* W, void* Y, int M, int N, i
     if (K == 256) return launch_wres<4, 2, false, true>(p, grid, stream);
     return launch_wres<8, 2, false, true>(p, grid, stream);
   }
-#ifdef CRNN_WRES_EXP
-  p.exp = crnn_knob("CRNN_WRES_EXP", 0);
-  { const char* e = getenv("CRNN_WRES_TRACE"); p.trace = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
-#endif
   p.cscale = cscale; p.cshift = cshift;
   if (pool != 1) {      // the two pooled blocks of the CRNN: 128 -> 256 channels with MaxPooling2D((2,2)), 256 -> 512 with (1,2); pooled by the storer waves
     if (!cscale || M % pool) return CRNN_ERR_ARG;
-#ifdef CRNN_WRES_POOL_NOEPI      // timing experiment: the pooled kernels without the BatchNorm + ReLU6 arithmetic in the MFMA waves (wrong values)
-    if (pool == 4 && K == 128) return launch_wres<2, 2, false, false, 4>(p, grid, stream);
-    if (pool == 2 && K == 256) return launch_wres<4, 2, false, false, 2>(p, grid, stream);
-#endif
     if (pool == 4 && K == 128) return launch_wres<2, 2, true, false, 4>(p, grid, stream);
     if (pool == 2 && K == 256) return launch_wres<4, 2, true, false, 2>(p, grid, stream);
     return CRNN_ERR_UNSUPPORTED;
@@ -726,7 +675,7 @@ namespace {
 // where the doubled weight fragments still fit the registers (K <= 256): half as many channel slices transform / read every pixel.
 // K = 64 stays on the narrow shape: its 8 drain pieces per stage beside the doubled accumulators left <1, 2, 2> at the 256-register
 // ceiling with 47 spilled registers (round 4's recompile), and no block of the CRNN has K = 64 with N a multiple of 256 (block 2: N = 128)
-bool wres_fwd_wide(int N, int K) { return N % 256 == 0 && K >= 128 && K <= 256 && crnn_knob("CRNN_WRES_WIDE", 1); }
+bool wres_fwd_wide(int N, int K) { return N % 256 == 0 && K >= 128 && K <= 256; }
 void wres_fwd_geom(long M, int N, int K, WresFwdParams& p, int& grid) {
   const bool wide = wres_fwd_wide(N, K);
   p.stripes = cdiv(M, wide ? 64 : 128); p.S = N / (wide ? 256 : 128);

@@ -22,14 +22,8 @@
 // fp32 accumulation chain as gemm_x3p_kernel (bit-identical results); KHN = 2 adds the two half-reduction chains at the end (summation order only).
 // The statistics are the same sums in another order (per-lane fp32 chains of at most kMaxLaneTerms terms, then crnn_bn_finalize / crnn_bn_bwd_finalize in double).
 #include "common.h"
+#include "stream_ops.h"
 #include <type_traits>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#ifndef W3_EXP
-#define W3_EXP 0   // timing experiments (scripts/wres3_variants.sh; wrong results): 1 no transform / split arithmetic, 2 no MFMAs, 4 no fragment reads, 8 no pixel loads, 16 no drain, 32 no plane writes
-#endif
 
 namespace {
 
@@ -45,8 +39,6 @@ struct W3Params {
 };
 
 constexpr int kMaxLaneTerms = 4096;   // longest fp32 chain of a statistics lane (rows per lane and launch); longer launches take the tile kernel
-
-__device__ __forceinline__ bf16x8_t w3_frag(const unsigned char* p) { return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(p)); }
 
 // ---------------------------------------------------------------------------------------------------------------- MFMA waves
 // wave (0..3) = (cb = wave % CBN, kh = wave / CBN): channels slice * NS + 32 cb .. + 31, reduction half kh.  Stage j of a stripe holds, per plane,
@@ -101,8 +93,8 @@ __device__ __forceinline__ void w3_compute(const unsigned char* ring, unsigned c
 #pragma unroll
   for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
-    for (int b = 0; b < PB; ++b) fx[pl][b] = w3_frag(ring + pl * PLANE + b * 4096 + lrow + ((cbase ^ sw) * 16));
-  if constexpr (WL) wlf = w3_frag(wl);
+    for (int b = 0; b < PB; ++b) fx[pl][b] = frag16(ring + pl * PLANE + b * 4096 + lrow + ((cbase ^ sw) * 16));
+  if constexpr (WL) wlf = frag16(wl);
   for (int it = 0; it < mine; ++it) {
 #pragma unroll
     for (int j = 0; j < KST; ++j) {
@@ -117,15 +109,14 @@ __device__ __forceinline__ void w3_compute(const unsigned char* ring, unsigned c
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
-          for (int b = 0; b < PB; ++b) { if (W3_EXP & 4) nx[pl][b] = fx[pl][b]; else nx[pl][b] = w3_frag(src + pl * PLANE + b * 4096); }
-        if constexpr (WL) { if (W3_EXP & 4) nwl = wlf; else nwl = w3_frag(wl + ((g + 1) % NG) * 1024); }
+          for (int b = 0; b < PB; ++b) nx[pl][b] = frag16(src + pl * PLANE + b * 4096);
+        if constexpr (WL) nwl = frag16(wl + ((g + 1) % NG) * 1024);
         __builtin_amdgcn_sched_barrier(0);                     // reads of the next k-step first, then this k-step's MFMAs (as wres_compute)
 #pragma unroll
         for (int t = T0; t < 6; ++t)
 #pragma unroll
           for (int b = 0; b < PB; ++b) {
             const bf16x8_t wa = (WL && PWp[t] == 2) ? wlf : wf[PWp[t] < NR ? PWp[t] : 0][j][ks];
-            if (W3_EXP & 2) { if (g == 0 && t - T0 < NC) acc[b][(t - T0) % NC] = zero16; continue; }
             const int ch = (t - T0) % NC;
             if (g == 0 && t - T0 < NC) acc[b][ch] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, fx[PXp[t]][b], zero16, 0, 0, 0);   // C = 0: no clearing pass
             else acc[b][ch] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, fx[PXp[t]][b], acc[b][ch], 0, 0, 0);
@@ -250,7 +241,6 @@ __global__ __launch_bounds__(512) void gemm_wres3_kernel(W3Params p) {
     const float* src = p.X + ((long)(first + it * step) * PX + r32) * ldk + kofs(j);
 #pragma unroll
     for (int u = 0; u < PB; ++u) {
-      if (W3_EXP & 8) { buf[u][0] = make_float4(1.f, 2.f, 3.f, (float)lin); buf[u][1] = buf[u][0]; continue; }
       buf[u][0] = *reinterpret_cast<const float4*>(src + (long)(32 * u) * ldk);
       buf[u][1] = *reinterpret_cast<const float4*>(src + (long)(32 * u) * ldk + 4);
     }
@@ -274,12 +264,6 @@ __global__ __launch_bounds__(512) void gemm_wres3_kernel(W3Params p) {
 #pragma unroll
     for (int u = 0; u < PB; ++u) {
       float v[8] = {buf[u][0].x, buf[u][0].y, buf[u][0].z, buf[u][0].w, buf[u][1].x, buf[u][1].y, buf[u][1].z, buf[u][1].w};
-      if (W3_EXP & 1) {
-        const u32x4 a = __builtin_bit_cast(u32x4, buf[u][0]), b = __builtin_bit_cast(u32x4, buf[u][1]);
-        pw[u][0] = a; pw[u][1] = b;
-        if constexpr (NPL == 3) pw[u][2] = a ^ b;
-        continue;
-      }
       if constexpr (MODE == 0) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = relu6f(fmaf(v[e], sc[e], sh[e]));
@@ -293,7 +277,6 @@ __global__ __launch_bounds__(512) void gemm_wres3_kernel(W3Params p) {
   };
   auto store = [&](int lin) {
     unsigned char* dst = smem + (lin % 3) * STAGE + r32 * 128 + csw;
-    if (W3_EXP & 32) { if (pw[0][0].x == 0x12345678u) dst[0] = 1; return; }
 #pragma unroll
     for (int u = 0; u < PB; ++u)
 #pragma unroll
@@ -357,11 +340,9 @@ __global__ __launch_bounds__(512) void gemm_wres3_kernel(W3Params p) {
     if (steady || jb < total) store(jb + 2);
     const int jd = jb - DLY + KST;                             // >= 0
     const int done = jd / KST - 2, t = jd % KST;
-    if (!(W3_EXP & 16)) {
-      if (steady || jb < total + DLY) {
-        if (PEV == 1 || t % PEV == 0) drain(done, (t / PEV) * PPS, std::integral_constant<int, PPS>{});
-      } else drain(done, 0, std::integral_constant<int, NP>{});    // the last stripe: everything at once
-    }
+    if (steady || jb < total + DLY) {
+      if (PEV == 1 || t % PEV == 0) drain(done, (t / PEV) * PPS, std::integral_constant<int, PPS>{});
+    } else drain(done, 0, std::integral_constant<int, NP>{});    // the last stripe: everything at once
     if (steady || jb < total) { compute(jb + 3, buf); load(jb + 3 + D, buf); }
   };
   static_assert(D >= 3, "three stages are formed before the first barrier");
@@ -394,20 +375,16 @@ __global__ __launch_bounds__(512) void gemm_wres3_kernel(W3Params p) {
   }
 }
 
-#ifndef W3_D1
-#define W3_PBS 2   // 32-pixel blocks per stripe of the K <= 128 shapes
-#define W3_D1 3     // K = 64 (64-pixel stripes)
-#define W3_D2 3     // K = 128 (64-pixel stripes)
-#define W3_D4F 6    // K = 256 forward
-#define W3_D4B 6    // K = 256 data gradient
-#define W3_D8 6     // K = 512
-#endif
+// stripe height and IO depth per shape (the deepest that does not spill): profiles/r06_wres3_bench.txt
+constexpr int kW3Pbs = 2;   // 32-pixel blocks per stripe of the K <= 128 shapes
+constexpr int kW3D12 = 3;   // stages in flight, K = 64 | 128 (64-pixel stripes)
+constexpr int kW3D48 = 6;   // stages in flight, K = 256 | 512
 // (K, N) -> the instantiation: KST = K / 64 stages per stripe; K = 512 in two reduction halves on 64-channel slices; 32-pixel stripes where the planes
 // fill the register file (192 VGPRs of W), 64-pixel stripes otherwise
 struct W3Shape { int kst, khn, pb; };
 bool w3_shape(int N, int K, W3Shape& s) {
   if (K != 64 && K != 128 && K != 256 && K != 512) return false;
-  s.kst = K / 64; s.khn = K == 512 ? 2 : 1; s.pb = K >= 256 ? 1 : W3_PBS;
+  s.kst = K / 64; s.khn = K == 512 ? 2 : 1; s.pb = K >= 256 ? 1 : kW3Pbs;
   const int ns = 128 / s.khn;
   return N >= ns && N % ns == 0 && N <= 1024;
 }
@@ -447,12 +424,12 @@ int w3_launch(const W3Params& p, int grid, hipStream_t stream) {
 template <int NPL, int MODE>
 int w3_dispatch(const W3Params& p, const W3Shape& s, int grid, hipStream_t stream) {
   if constexpr (MODE == 0) {
-    if (s.kst == 1) return w3_launch<1, 1, NPL, W3_PBS, MODE, W3_D1>(p, grid, stream);
-    if (s.kst == 2) return w3_launch<2, 1, NPL, W3_PBS, MODE, W3_D2>(p, grid, stream);
+    if (s.kst == 1) return w3_launch<1, 1, NPL, kW3Pbs, MODE, kW3D12>(p, grid, stream);
+    if (s.kst == 2) return w3_launch<2, 1, NPL, kW3Pbs, MODE, kW3D12>(p, grid, stream);
   }
   // (the data gradient's reductions are the blocks' OUTPUT channels: 256 or 512 wherever its result has a multiple of 128 channels)
-  if (s.kst == 4) return w3_launch<4, 1, NPL, 1, MODE, (MODE == 0 ? W3_D4F : W3_D4B)>(p, grid, stream);
-  if (s.kst == 8) return w3_launch<8, 2, NPL, 1, MODE, W3_D8>(p, grid, stream);
+  if (s.kst == 4) return w3_launch<4, 1, NPL, 1, MODE, kW3D48>(p, grid, stream);
+  if (s.kst == 8) return w3_launch<8, 2, NPL, 1, MODE, kW3D48>(p, grid, stream);
   return CRNN_ERR_UNSUPPORTED;
 }
 

@@ -12,6 +12,7 @@
 // Backward (BPTT) mirrors it: dh_{t-1} = dz_t * U^T as the per-step GEMM, the gate-gradient math as its
 // epilogue; dW/dU/dx/db are whole-sequence GEMMs afterwards.
 #include "common.h"
+#include "stream_ops.h"
 #include "rnn_cell.h"
 
 // ----------------------------------------------------------------------------------------------------------
@@ -104,7 +105,6 @@ static inline int step_sj(int gx) { return (gx % 4 == 0) ? 4 : (gx % 2 == 0 ? 2 
 // fp32 state rows are rounded to bf16 while they are packed (v_cvt_pk_bf16_f32) and one v_mfma_f32_16x16x32_bf16
 // covers 32 k (8 of the fp32 MFMAs).  Lane (r,q) holds k = kb+8q..8q+7 of row r for both operands.  Requires the
 // wave's K quarter to be a multiple of 32.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ bf16x8_t pack8_bf16(const float4& lo, const float4& hi) {
   uint4 w = make_uint4(pack2_bf16(lo.x, lo.y), pack2_bf16(lo.z, lo.w), pack2_bf16(hi.x, hi.y), pack2_bf16(hi.z, hi.w));
   return __builtin_bit_cast(bf16x8_t, w);

@@ -23,27 +23,17 @@
 // unsigned at byte 16 is the per-launch status word (all ones after a clean launch, bit 0 cleared on give-up).
 #pragma once
 #include "common.h"
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "stream_ops.h"
 
 namespace {
 
 constexpr unsigned kSentinel = 0xffffffffu;
 // Layout of xbuf: [0,4) sticky give-up counter (never reset by a launch) | [16,20) per-launch status (all ones = clean) | [kHelloOff, +kHelloBytes)
-// one word per workgroup of the launch for the XCD census | (trace build: time stamps) | the exchange ring.  Every launch fills
+// one word per workgroup of the launch for the XCD census | the exchange ring.  Every launch fills
 // [16, end) with 0xFF first.
 constexpr size_t kLaunchStatusOff = 16;
 constexpr size_t kHelloOff = 256, kHelloBytes = 4096;     // 1024 workgroups (a launch has at most 2 per CU)
-#ifdef CRNN_RNN_TRACE
-constexpr size_t kTraceOff = kHelloOff + kHelloBytes;
-constexpr size_t kStatusBytes = kTraceOff + 65536;        // trace build: per-step timestamps of two workgroups
-#define RNN_TRACE(slot) do { if (tid == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2 + 3)) \
-    reinterpret_cast<unsigned long long*>(xbuf + kTraceOff)[((blockIdx.x != 0) * 128 + TRACE_STEP) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
 constexpr size_t kStatusBytes = kHelloOff + kHelloBytes;
-#define RNN_TRACE(slot) do {} while (0)
-#endif
 constexpr unsigned long long kSpinTicks = 200ull * 1000 * 1000;   // a wait gives up after 2 s of the constant 100 MHz clock (s_memrealtime)
 // Cache policy of the exchange (aux bits of the buffer instructions: 1 = sc0, 16 = sc1).  Loads always bypass the L1 (sc1: a CU's L1
 // is never refreshed by other CUs' stores).  Stores: write-through to memory (sc1) unless the cluster has verified that all its members

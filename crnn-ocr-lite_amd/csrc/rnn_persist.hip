@@ -75,8 +75,6 @@ __global__ __launch_bounds__(kThreads) void lstm_fwd_persist_kernel(FwdDir d0, F
 #pragma unroll 1
   for (int s = 0; s < T; ++s) {
     const int t = dir ? T - 1 - s : s;
-#define TRACE_STEP s
-    RNN_TRACE(0);
     float xwv[4];                                        // x W + b, requested before the wait
     {
       const float* xw = d.xw + ((long)t * B + (b < b_end ? b : b_lo)) * 4 * U;
@@ -85,15 +83,12 @@ __global__ __launch_bounds__(kThreads) void lstm_fwd_persist_kernel(FwdDir d0, F
     }
     if (s > 0) {
       gather_rows<U>(slot(s - 1), As, LDA, tid, status, dead);   // h_{s-1} of the whole cluster
-      RNN_TRACE(1);
       __syncthreads();
-      RNN_TRACE(2);
       f32x4 acc[4];
 #pragma unroll
       for (int a = 0; a < 4; ++a) acc[a] = quarter_chain<WBF, KQ>(As, LDA, a * (U / 4), breg[a], r, q);
       put_frag(red[ug][gate], (acc[0] + acc[1]) + (acc[2] + acc[3]), r, q);
       __syncthreads();
-      RNN_TRACE(3);
     }
     float z[4];
 #pragma unroll
@@ -107,7 +102,6 @@ __global__ __launch_bounds__(kThreads) void lstm_fwd_persist_kernel(FwdDir d0, F
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the re-poisoning of step s-1 has landed before step s goes out
       publish_rows<16>(hout[ug], slot(s) + (long)sg * BT * 16, pch, local);
     }
-    RNN_TRACE(4);
     if (b < b_end) {   // what the next layer / the backward pass read: off the critical path
       float* gt = d.gates + ((long)t * B + b) * 4 * U;
       gt[j] = o.ig; gt[U + j] = o.fg; gt[2 * U + j] = o.gg; gt[3 * U + j] = o.og;
@@ -115,7 +109,6 @@ __global__ __launch_bounds__(kThreads) void lstm_fwd_persist_kernel(FwdDir d0, F
       d.h[((long)t * B + b) * d.ldh + j] = o.hn;
     }
     if (s + 1 < T) poison_rows<16>(slot(s + 2) + (long)sg * BT * 16, pch, local);   // last: nobody waits for it
-#undef TRACE_STEP
   }
 }
 

@@ -674,11 +674,6 @@ static size_t loc_bwd_lds(const LocDims& d) {
   return sizeof(float) * (LOC_K * LOC_K * LOC_CO * LOC_CO + 2 * np2 + d.F + 64 + (size_t)d.Hs1 * d.Ws1 + 16) + ((np2 + 15) & ~(size_t)15) +
          sizeof(int) * ((size_t)d.Ho2 * d.Wo2 + 4);   // k2 | pool2 | dpool2 | dflat | dfc1 | pool1 | arg bytes | pixel offsets
 }
-#ifdef CRNN_LOC_TRACE   // timing build: s_memrealtime stamps of workgroup 0 after every phase, behind the samples' terms
-#define LOC_TRC(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<unsigned long long*>(terms + (long)gridDim.x * LOC_TERMS)[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define LOC_TRC(i) do {} while (0)
-#endif
 __global__ __launch_bounds__(LOC_NTB) void loc_net_bwd_kernel(const float* __restrict__ dtheta, const float* __restrict__ fc1, const float* __restrict__ w1,
                                                           const float* __restrict__ w2, const float* __restrict__ k2, const float* __restrict__ pool1,
                                                           const float* __restrict__ c1, const float* __restrict__ pool2, float* __restrict__ dfc1,
@@ -696,7 +691,6 @@ __global__ __launch_bounds__(LOC_NTB) void loc_net_bwd_kernel(const float* __res
   int* const xo = reinterpret_cast<int*>(arg + ((np2 + 15) & ~15));   // offset of output pixel (ho, wo) of the second convolution inside pool2: (ho Ws2 + wo) 20
   const int img = blockIdx.x, tid = threadIdx.x;
   float* const tm = terms + (long)img * LOC_TERMS;
-  LOC_TRC(0);
   for (int i = tid; i < d.Ho2 * d.Wo2 + 4; i += LOC_NTB) xo[i] = (i < d.Ho2 * d.Wo2) ? ((i / d.Wo2) * d.Ws2 + i % d.Wo2) * LOC_CO : 0;
   for (int i = tid; i < NK2 / 4; i += LOC_NTB) reinterpret_cast<float4*>(k2s)[i] = reinterpret_cast<const float4*>(k2)[i];
   for (int i = tid; i < np2 / 4; i += LOC_NTB) reinterpret_cast<float4*>(p2)[i] = reinterpret_cast<const float4*>(pool2 + (long)img * np2)[i];
@@ -722,7 +716,6 @@ __global__ __launch_bounds__(LOC_NTB) void loc_net_bwd_kernel(const float* __res
     dfc1[(long)img * LOC_H1 + tid] = a;
   }
   __syncthreads();
-  LOC_TRC(1);
   for (int k = tid; k < F; k += LOC_NTB) {
     const float2* wr = reinterpret_cast<const float2*>(w1 + (long)k * LOC_H1);    // the row's 25 loads issued together (same sums, same order)
     float2 wv[LOC_H1 / 2];
@@ -734,7 +727,6 @@ __global__ __launch_bounds__(LOC_NTB) void loc_net_bwd_kernel(const float* __res
     df[k] = a0 + a1;
   }
   __syncthreads();
-  LOC_TRC(2);
   // ---- second convolution: data gradient (loc_conv_dgrad_kernel's chain) into LDS ...
   // (threads 0..511: the data gradient; threads 512..1011: the weight-gradient term below -- independent work side by side)
   for (int t = tid; t < d.Hs2 * d.Ws2 * (LOC_CO / 4) && tid < 512; t += 512) {
@@ -792,7 +784,6 @@ __global__ __launch_bounds__(LOC_NTB) void loc_net_bwd_kernel(const float* __res
     for (int j = 0; j < LOC_K; ++j) *reinterpret_cast<float4*>(tm + ((tg * LOC_K + j) * LOC_CO + c) * LOC_CO + 4 * og) = a[j];
   }
   __syncthreads();
-  LOC_TRC(3);
   // ---- first convolution: dc1 is dpool2 at the first maximum of each window, zero elsewhere -- its weight-gradient term straight from the windows
   float* const t1p = tm + NK2 + LOC_CO;
   float* const qs = k2s;                                           // (the kernel of the second convolution is not needed any more) [4][125][4] partial sums
@@ -830,7 +821,6 @@ __global__ __launch_bounds__(LOC_NTB) void loc_net_bwd_kernel(const float* __res
     *reinterpret_cast<float4*>(qs + (qd * NT1 + t) * 4) = make_float4(a[0], a[1], a[2], a[3]);
   }
   __syncthreads();
-  LOC_TRC(4);
   if (tid < NT1) {                                                 // the four quarters in a fixed order
     const int og = tid % (LOC_CO / 4), tap = tid / (LOC_CO / 4);
     float4 v = *reinterpret_cast<const float4*>(qs + tid * 4);
@@ -851,7 +841,6 @@ __global__ __launch_bounds__(LOC_NTB) void loc_net_bwd_kernel(const float* __res
     for (int pix = 0; pix < d.Ho2 * d.Wo2; ++pix) a += df[pix * LOC_CO + o];
     tm[NK2 + o] = a;
   }
-  LOC_TRC(5);
 }
 // Second launch: blocks [0, nred): the samples' terms summed in sample order (4 interleaved chains) -> dk2 | db2c | dk1 | db1c;
 // blocks [nred, nred + nw1): rows of dW1 (+ db1) = flat^T dfc1 over the batch; last block: dW2, db2 = fc1^T dtheta.

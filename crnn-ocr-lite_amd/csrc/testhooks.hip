@@ -1,11 +1,8 @@
 // Measurement / test hooks -- NOT part of the product library: built into libcrnn_testhooks.so (include/crnn_testhooks.h), loaded only by
 // bench.py's copy reference, scripts/ and tests/.  Nothing under crnn_mi355x/ or libcrnn_mi355x.so depends on it.
 #include "common.h"
+#include "stream_ops.h"
 #include "crnn_testhooks.h"
-
-namespace {
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-}
 
 // ---- measurement reference (bench.py depthwise_roofline "copy_reference"): what a plain copy of the same bytes achieves -----------------
 // pattern 0: grid-stride, the resident workgroups sweep ONE window of the buffer together (16 KiB per workgroup and iteration);

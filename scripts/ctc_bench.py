@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""crnn_ctc_loss_grad at the benchmark shape (B x 52 x 38, labels up to 23): product library and the phase-ablation builds scripts/_trace/libctc_exp<n>.so
-(-DCRNN_CTC_EXP=n: 3 stop before the log-softmax phase, 1 after it, 2 after the two recursions).  usage: ctc_bench.py [B]"""
+"""crnn_ctc_loss_grad at the benchmark shape (B x 52 x 38, labels up to 23): product library and any variant builds of ctc.hip found as
+scripts/_trace/libctc_*.so (the phase-ablation builds are gone: profiles/r05_ctc_bench.txt).  usage: ctc_bench.py [B]"""
 import ctypes, glob, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "crnn-ocr-lite_amd")]

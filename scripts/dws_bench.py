@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Depthwise 3x3 forward (with BatchNorm statistics) of blocks 2-7 at batch B: the halo-tile kernel against the row-stream kernel, the six
 launches issued round-robin on their own buffers (1.7 GB working set at batch 256: cold like in the step), each timed with its own
-events.  Optional experiment builds scripts/_trace/libdws_*.so (-DCRNN_DWS_EXP=1 no DMA | 2 no stores | 4 no fmas)."""
+events.  Also times any variant builds of dwconv_stream.hip found as scripts/_trace/libdws_*.so (the ablation builds are gone: profiles/r03_dw_fwd_stream_experiments.txt)."""
 import ctypes, glob, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "crnn-ocr-lite_amd")]

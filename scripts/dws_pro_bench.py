@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Prologue form of the depthwise row-stream kernels against the two-pass path, per shape (the un-pooled block outputs feeding blocks 2, 3, 5, 7)
 at batch B: forward = crnn_bn_act_pool_drop_ex + crnn_dwconv3x3_fwd_stream vs crnn_dwconv3x3_fwd_stream_pro (rate .1 and 0); backward =
-crnn_dwconv3x3_bwd_stream vs crnn_dwconv3x3_bwd_stream_pro.  Optional experiment builds scripts/_trace/libdwsp_*.so / libdbsp_*.so."""
+crnn_dwconv3x3_bwd_stream vs crnn_dwconv3x3_bwd_stream_pro.  Also times any variant builds found as scripts/_trace/libdwsp_*.so / libdbsp_*.so."""
 import ctypes, glob, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "crnn-ocr-lite_amd")]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the fused depthwise-stage backward on the step's shapes (batch 256), optionally over experiment builds
-(scripts/_trace/libfused_*.so: -DFUSED_WPE=waves/SIMD -DFUSED_ABL=1 no global loads | 2 fill only | 3 no weight gradient)."""
+(any scripts/_trace/libfused_*.so; the ablation builds are gone: profiles/r02_dw_bwd_fused_bench.txt)."""
 import ctypes, glob, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "crnn-ocr-lite_amd")]

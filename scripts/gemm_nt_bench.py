@@ -30,7 +30,6 @@ for name, M, N, K in shapes:
         r = L.crnn_gemm_wres_bf16(P(X), P(W), P(Y), M, N, K, S()); assert r == 0, r
     tw = t(wres) if L.crnn_gemm_wres_supported(N, K) == 0 else float("nan")
     tn, to = t(new), t(old)
-    os.environ["CRNN_NT_VARIANT"] = "1"; tn1 = t(new); os.environ["CRNN_NT_VARIANT"] = "2"; tn2 = t(new); os.environ["CRNN_NT_VARIANT"] = "0"
     by = 2.0 * (M * K + M * N)
-    res[name] = {"M": M, "N": N, "K": K, "wres_us": round(tw, 1), "wres_TBps": round(by / tw / 1e6, 2), "persist_us": round(tn, 1), "tile_us": round(to, 1), "bn128_r4_us": round(tn1, 1), "bn128_r3_us": round(tn2, 1), "persist_TBps": round(by / tn / 1e6, 2), "tile_TBps": round(by / to / 1e6, 2)}
+    res[name] = {"M": M, "N": N, "K": K, "wres_us": round(tw, 1), "wres_TBps": round(by / tw / 1e6, 2), "persist_us": round(tn, 1), "tile_us": round(to, 1), "persist_TBps": round(by / tn / 1e6, 2), "tile_TBps": round(by / to / 1e6, 2)}
     print(name, res[name], flush=True)

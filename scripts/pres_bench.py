@@ -63,13 +63,6 @@ for planes in planes_list:
                                             P(bf["ap"]) if emit else None, M * sh[1], emit, S())
         for bf in bufs: bf["da2"].zero_(); bf["parts2"].zero_()
         t1 = run("dgrad, %d planes, from planes%s" % (planes, ", writes %d planes of a" % emit if emit else ""), f)
-        if os.environ.get("PRES_TRACE"):   # a PRES_EXP & 128 build left [workgroup][cycles, 100 MHz ticks, stripes] of its main loop in da2
-            for sh, bf in zip(shapes, bufs):
-                g = min(2048, bf["da2"].numel() // 8)
-                tr = bf["da2"].view(-1).view(torch.int64)[:4 * g].view(g, 4)[:, :4].cpu().numpy().astype(np.float64)
-                tr = tr[(tr[:, 2] > 0) & (tr[:, 2] < 1e6) & (tr[:, 1] > 0) & (tr[:, 1] < 1e9)][:512]
-                print("      %d<%d: %d workgroups, stripes %.1f, prologue %.1f us, main loop %.1f us, %.0f cycles per stripe, clock %.2f GHz" % (
-                    sh[1], sh[2], len(tr), tr[:, 2].mean(), tr[:, 3].mean() / 100, tr[:, 1].mean() / 100, (tr[:, 0] / tr[:, 2]).mean(), (tr[:, 0] / tr[:, 1]).mean() / 10))
         dev, sdev, adev = [], [], []
         for sh, bf, m in zip(shapes, bufs, t1):
             if np.isnan(m): dev.append(float("nan")); sdev.append(float("nan")); adev.append(float("nan")); continue

@@ -19,11 +19,6 @@ for name, M, N, K in [("b3", 958464, 256, 128), ("b4", 239616, 256, 256), ("b5",
         lib = ctypes.CDLL(os.path.join(ROOT, "scripts/_trace/libwg_%s.so" % path))
         lib.crnn_pwconv_bnrelu6_wgrad_stream.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         fns.append(lib.crnn_pwconv_bnrelu6_wgrad_stream)
-    if "--ablate" in sys.argv:
-        for m in (1, 2, 3, 4, 7):
-            lib = ctypes.CDLL(os.path.join(ROOT, "scripts/_trace/libwg_exp%d.so" % m))
-            lib.crnn_pwconv_bnrelu6_wgrad_stream.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-            fns.append(lib.crnn_pwconv_bnrelu6_wgrad_stream)
     for fn in fns:
         run = lambda: fn(P(d), P(st), P(g), P(dw), M, N, K, P(scratch), ctypes.c_size_t(scratch.numel() * 4), S())
         for _ in range(2): assert run() == 0
@@ -35,5 +30,5 @@ for name, M, N, K in [("b3", 958464, 256, 128), ("b4", 239616, 256, 256), ("b5",
     by = 2.0 * M * (N + K)
     tot[0] += res[0]; tot[1] += res[1]
     print("%s M=%7d N=%3d K=%3d: stream %6.1f us (%.2f TB/s)   tile %6.1f us (%.2f TB/s)  %s" % (name, M, N, K, res[0], by / res[0] / 1e6, res[1], by / res[1] / 1e6,
-          "  ".join("%s %.1f" % (m, t) for m, t in zip(list(filter(None, os.environ.get("WG_LIBS", "").split(","))) + ["exp%d" % m for m in (1, 2, 3, 4, 7)], res[2:]))), flush=True)
+          "  ".join("%s %.1f" % (m, t) for m, t in zip(filter(None, os.environ.get("WG_LIBS", "").split(",")), res[2:]))), flush=True)
 print("sum: stream %.0f us, tile %.0f us" % tuple(tot))

@@ -271,7 +271,7 @@ def test_weights_resident_gemms_and_row_stream_kernels_have_no_spilled_vector_re
         pytest.skip("hipcc not on PATH")
     csrc = os.path.join(os.path.dirname(native.LIB_PATH), "csrc")
     inc = os.path.dirname(native.HEADER)
-    for src, minimum, allowed in (("gemm_wres.hip", 15, 0), ("gemm_wres3.hip", 12, 0), ("gemm_pres.hip", 9, 0), ("gemm_wgrad3.hip", 4, 0), ("gemm_wgrad.hip", 2, 0), ("dwconv_stream.hip", 7, 4), ("dwconv_bwd_stream.hip", 7, 4),
+    for src, minimum, allowed in (("gemm_wres.hip", 15, 0), ("gemm_wres3.hip", 12, 0), ("gemm_pres.hip", 9, 0), ("gemm_wgrad3.hip", 4, 0), ("gemm_wgrad.hip", 11, 0), ("dwconv_stream.hip", 7, 4), ("dwconv_bwd_stream.hip", 7, 4),
                                   ("dense.hip", 2, 0)):
         with tempfile.TemporaryDirectory() as td:
             r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", inc, "-c", os.path.join(csrc, src), "-o", os.path.join(td, "k.o"),
@@ -280,6 +280,8 @@ def test_weights_resident_gemms_and_row_stream_kernels_have_no_spilled_vector_re
         names = re.findall(r"Function Name: (\S+)", r.stderr)
         spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
         assert len(names) == len(spills) and len(names) >= minimum, (src, len(names), len(spills))
+        if src == "gemm_wgrad.hip":   # exact: its instantiations that no launcher could reach are gone (profiles/stream_scaffold_refactor.txt)
+            assert len(names) == minimum, (src, len(names))
         bad = {n: v for n, v in zip(names, spills) if v > allowed}
         assert not bad, "%s: instantiations with spilled vector registers: %s" % (src, bad)
         if src == "dwconv_bwd_stream.hip":
@@ -287,6 +289,22 @@ def test_weights_resident_gemms_and_row_stream_kernels_have_no_spilled_vector_re
             # dx row offset are re-formed where they are used; what is left are two column constants of the DK waves the allocator parks across the row loop)
             step = [v for n, v in zip(names, spills) if "dw_bwd_stream_kernelILi3ELb0ELb0ELb0ELb0E" in n]
             assert step and step[0] <= 2, step
+
+
+def test_native_sources_read_no_environment_and_have_no_experiment_hooks():
+    """include/crnn_mi355x.h promises "no global mutable state: the library reads no environment variable".  That rests on the sources: no file under
+    csrc/ calls getenv or carries the run-time knobs of the old experiment builds (crnn_knob, CRNN_EXPERIMENT_HOOKS)."""
+    csrc = os.path.join(os.path.dirname(native.LIB_PATH), "csrc")
+    files = sorted(os.listdir(csrc))
+    assert "common.h" in files and "stream_ops.h" in files and len([f for f in files if f.endswith(".hip")]) >= 29
+    bad = []
+    for name in files:
+        path = os.path.join(csrc, name)
+        if not os.path.isfile(path) or not name.endswith((".hip", ".h", ".inc", ".cpp")):
+            continue
+        text = open(path).read()
+        bad += [(name, word) for word in ("getenv", "crnn_knob", "CRNN_EXPERIMENT_HOOKS") if word in text]
+    assert not bad, bad
 
 
 def test_bench_counter_traffic_lookup_and_contract_fields():
