@@ -11,7 +11,10 @@ csrc/detect.hip on pages that are already on the device (the arena `DeviceIngest
 The defaults of gap_x, gap_y and the filter are PLACEHOLDERS: no labelled page set was at hand to tune them.  gap_x must exceed the gaps
 between the letters of a word and stay below the gaps between words; both scale with the resolution of the scan.
 
-Out of scope: adaptive (local) thresholds, deskewing, learned detectors, anything that would make the result depend on arrival order."""
+On unevenly lit pages (photographs) one threshold per page fails: `adaptive=` puts the Sauvola binarisation of crnn_mi355x/binarize.py in front
+of the rule, on the host and on the device alike.
+
+Out of scope: deskewing, learned detectors, anything that would make the result depend on arrival order."""
 import ctypes
 import re
 import warnings
@@ -160,10 +163,29 @@ def filter_boxes(rects, min_w=0, min_h=0, min_ink=0, max_w=0, max_h=0):
     return keep
 
 
+def adaptive_setup(adaptive, threshold, polarity):
+    """adaptive (None, True or a dict: binarize.adaptive_params) -> (the binarisation parameters or None, threshold, polarity of the detection
+    that follows).  The binarised page holds 0 for ink and 255 elsewhere, so the detection on it runs with threshold 127 and dark ink;
+    ValueError when `adaptive` comes with a threshold or a polarity of the caller's own (the polarity of the ink goes into `adaptive`)."""
+    if adaptive is None or adaptive is False:
+        return None, threshold, polarity
+    if threshold != DEFAULTS["threshold"] or polarity != DEFAULTS["polarity"]:
+        raise ValueError("adaptive binarisation decides what is ink: it goes with neither threshold (%r) nor polarity (%r); the ink's polarity "
+                         "is adaptive['polarity']" % (threshold, polarity))
+    from .binarize import adaptive_params
+    return adaptive_params(adaptive), 127, 1
+
+
 def detect_words_host(page, threshold=-1, polarity=0, gap_x=DEFAULTS["gap_x"], gap_y=DEFAULTS["gap_y"], min_w=DEFAULTS["min_w"],
-                      min_h=DEFAULTS["min_h"], min_ink=DEFAULTS["min_ink"], max_w=0, max_h=0, cap=None):
+                      min_h=DEFAULTS["min_h"], min_ink=DEFAULTS["min_ink"], max_w=0, max_h=0, cap=None, adaptive=None):
     """The detection rule in NumPy (the host path, and the oracle of the device kernels): -> (rects (kept, 5) int32 = r0 r1 c0 c1 ink,
-    info (4,) int32 = found kept threshold ink_is_dark).  cap=None keeps every box.  gap_x, gap_y and the filter's defaults are placeholders."""
+    info (4,) int32 = found kept threshold ink_is_dark).  cap=None keeps every box.  gap_x, gap_y and the filter's defaults are placeholders.
+    adaptive (True, or a dict of radius, k256, polarity): the page goes through binarize.sauvola_host first and the rule runs on the result
+    with threshold 127 and dark ink, so `ink` counts the binarised ink pixels of a box."""
+    adaptive, threshold, polarity = adaptive_setup(adaptive, threshold, polarity)
+    if adaptive is not None:
+        from .binarize import sauvola_host
+        page = sauvola_host(page, **adaptive)
     p = check_params(dict(threshold=threshold, polarity=polarity, gap_x=gap_x, gap_y=gap_y, min_w=min_w, min_h=min_h, min_ink=min_ink,
                           max_w=max_w, max_h=max_h, cap=1 if cap is None else cap))
     ink, t, dark = ink_mask(page, p["threshold"], p["polarity"])
@@ -211,20 +233,28 @@ def page_table(pages, offsets):
 class WordDetector:
     """detect_words_host on the device: pages go up once (ingest.upload_pages, or an arena `DeviceIngest.upload` already made), one launch
     sequence finds the boxes of every page, one copy brings rects and info back.  Parameters as detect_words_host; `cap` bounds the boxes
-    per page (a page with more warns once, by its index).  The defaults of gap_x, gap_y and the filter are placeholders."""
+    per page (a page with more warns once, by its index).  The defaults of gap_x, gap_y and the filter are placeholders.
+    adaptive (True, or a dict of radius, k256, polarity): binarize.Binarizer makes a binarised arena on the device first and the launch
+    sequence reads that one, with threshold 127 and dark ink; the arena passed in stays as it is (the crops are cut from it)."""
 
-    def __init__(self, device=None, **params):
+    def __init__(self, device=None, adaptive=None, **params):
         import torch
         unknown = set(params) - set(PARAMS)
         if unknown:
             raise TypeError("unknown detection parameters: %s" % sorted(unknown))
-        self.params = check_params(dict(DEFAULTS, **params))
+        self.adaptive, threshold, polarity = adaptive_setup(adaptive, params.get("threshold", DEFAULTS["threshold"]),
+                                                            params.get("polarity", DEFAULTS["polarity"]))
+        self.params = check_params(dict(DEFAULTS, **dict(params, threshold=threshold, polarity=polarity)))
         if not torch.cuda.is_available():
             raise RuntimeError("WordDetector needs an AMD GPU (gfx950); the host path is detect_words_host")
         self.lib = native.lib()
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self._prm = crnn_detect_params(**self.params)
         self._warned = False
+        self._binarizer = None
+        if self.adaptive is not None:
+            from .binarize import Binarizer
+            self._binarizer = Binarizer(self.device, **self.adaptive)
 
     def detect(self, pages, arena=None):
         """pages: list of (H, W) uint8 arrays, or None with an `arena` that holds them -> [(rects (kept, 5) int32, info (4,) int32) per page]."""
@@ -236,6 +266,8 @@ class WordDetector:
         P, cap = len(arena.pages), self.params["cap"]
         if P == 0:
             return []
+        if self._binarizer is not None:
+            arena = self._binarizer.run(None, arena=arena)                 # a new arena on the device; the caller's is not written
         table = page_table(arena.pages, arena.offsets)
         with torch.cuda.device(self.device):
             table_dev = torch.from_numpy(table.view(np.uint8)).to(self.device)

@@ -10,7 +10,9 @@ on the network's time axis and its log-probability.
 --nbest K (with --result_path) also writes nbest.csv: per image the K best paths of the beam with their scores.
 --detect treats every image under --image_path as a page and finds its word boxes itself (crnn_mi355x.detect: threshold, smearing, connected
 components) instead of reading them from --boxes; with --device_ingest the boxes are found on the GPU, on the same upload the crops are cut from.
-prediction.csv then carries every box next to its prediction."""
+prediction.csv then carries every box next to its prediction.
+--detect_adaptive RADIUS (with --detect) binarises every page adaptively first (Sauvola, crnn_mi355x.binarize), for unevenly lit pages; the boxes come
+from the binarised page, the crops from the grey one."""
 import argparse
 import os
 import pickle
@@ -69,6 +71,12 @@ def build_parser():
     parser.add_argument('--detect_min_ink', type=int, default=None, help='with --detect: fewest ink pixels of a box kept (a placeholder default: tune it)')
     parser.add_argument('--detect_threshold', type=int, default=None, help='with --detect: ink threshold 0..254, or -1 for Otsu per page (the default)')
     parser.add_argument('--detect_cap', type=int, default=None, help='with --detect: most boxes kept per page (default 1024)')
+    parser.add_argument('--detect_adaptive', type=int, default=None, metavar='RADIUS',
+                        help='with --detect: binarise every page adaptively first (Sauvola, crnn_mi355x.binarize) over windows of 2 RADIUS + 1 pixels, '
+                             'RADIUS 1..31 (15 is a placeholder: tune it), for unevenly lit pages; it takes the place of --detect_threshold. '
+                             'Only the boxes come from the binarised page: the crops are cut from the original grey page, which is what the recogniser was trained on')
+    parser.add_argument('--detect_adaptive_k', type=float, default=None, metavar='K',
+                        help='with --detect_adaptive: Sauvola\'s k, used as round(K * 256) / 256 in 0..255/256 (the default 0.2 is a placeholder: tune it)')
     return parser
 
 
@@ -79,7 +87,12 @@ DETECT_FLAGS = ("gap_x", "gap_y", "min_w", "min_h", "min_ink", "threshold", "cap
 
 def detect_params(args):
     """The --detect_* flags that were given -> keyword arguments of detect_words_host / WordDetector."""
-    return {k: getattr(args, "detect_" + k) for k in DETECT_FLAGS if getattr(args, "detect_" + k) is not None}
+    p = {k: getattr(args, "detect_" + k) for k in DETECT_FLAGS if getattr(args, "detect_" + k) is not None}
+    if args.detect_adaptive is not None:
+        p["adaptive"] = dict(radius=args.detect_adaptive, **({} if args.detect_adaptive_k is None else {"k": args.detect_adaptive_k}))
+    elif args.detect_adaptive_k is not None:
+        p["adaptive"] = dict(k=args.detect_adaptive_k)       # (parse_args refuses it: k tunes --detect_adaptive)
+    return p
 
 
 def parse_args(argv=None):
@@ -115,10 +128,14 @@ def parse_args(argv=None):
         parser.error("--detect has no truth to validate against: it does not go with --validate")
     if not args.detect and detect_params(args):
         parser.error("the --detect_* flags tune --detect: they need it")
+    if args.detect_adaptive_k is not None and args.detect_adaptive is None:
+        parser.error("--detect_adaptive_k tunes --detect_adaptive: it needs it")
     if args.detect:
-        from crnn_mi355x.detect import check_params, DEFAULTS
+        from crnn_mi355x.detect import adaptive_setup, check_params, DEFAULTS
         try:
-            check_params(dict(DEFAULTS, **detect_params(args)))
+            given = detect_params(args)
+            adaptive_setup(given.pop("adaptive", None), given.get("threshold", DEFAULTS["threshold"]), DEFAULTS["polarity"])
+            check_params(dict(DEFAULTS, **given))
         except ValueError as e:
             parser.error(str(e))
     return args
@@ -126,7 +143,8 @@ def parse_args(argv=None):
 
 def detect_on_device(args, names, model, img_size, U):
     """--detect --device_ingest: groups of pages go up once; the detector finds the boxes in the arena and the crops are cut from the same
-    arena, batch by batch -> ({page: boxes}, softmax maps of every box in order).  Pages without boxes are left out."""
+    arena, batch by batch -> ({page: boxes}, softmax maps of every box in order).  Pages without boxes are left out.  With --detect_adaptive the
+    detector binarises the arena into a second one and finds the boxes there; the crops still come from the grey arena uploaded here."""
     det = U.WordDetector(**detect_params(args))
     ing = U.DeviceIngest(img_size, normed=True)
     bboxs, maps = {}, []

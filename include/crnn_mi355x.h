@@ -350,6 +350,33 @@ size_t crnn_detect_workspace_bytes(const crnn_page_item* pages, int P, const crn
 int crnn_detect_words(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int P,
                       const crnn_detect_params* prm, int* rects, int* info, void* ws, size_t ws_bytes, crnn_stream_t stream);
 
+/* ---- adaptive (Sauvola) binarisation of page images, for word detection on unevenly lit pages (csrc/binarize.hip; the same rule in NumPy:
+ * crnn_mi355x.binarize.sauvola_host) ---- */
+/* radius 1..31; k256 0..255 (Sauvola's k = k256 / 256); polarity 1 dark ink / 2 light ink.  The dynamic range is fixed at R = 128. */
+typedef struct { int radius, k256, polarity; } crnn_binarize_params;
+#define CRNN_BINARIZE_STRIP_C 192  /* a workgroup writes a strip of this many columns (256 loaded: 32 columns of halo either side) ... */
+#define CRNN_BINARIZE_BAND_R 64    /* ... of a band of this many rows (it reads `radius` rows more above and below) */
+/* The rule, integers throughout, for pixel (i, j) of a page p of rows x cols uint8 values, with r = radius:
+ *   v = p[i][j] (polarity 1) or 255 - p[i][j] (polarity 2); every sum below is over v.
+ *   The window is rows max(0, i - r) .. min(rows - 1, i + r) and columns max(0, j - r) .. min(cols - 1, j + r): CLIPPED to the page;
+ *   n = its pixel count (<= 3969), S = sum v, Q = sum v^2, D = n Q - S^2 (0 <= D < 2^40).
+ *   sd = floor(sqrt(D)): the double-precision square root, truncated, then `while (s*s > D) --s; while ((s+1)*(s+1) <= D) ++s;` -- exact
+ *   whatever the rounding of sqrt.
+ *   INK  <=>  v n^2 32768  <  S n 128 (256 - k256) + S k256 sd        (int64; both sides < 2^49)
+ *   which is v < m (1 + k (sigma / R - 1)), m = S / n, sigma = sqrt(D) / n, multiplied through by n^2 R 256.  The comparison is strict: a
+ *   constant page has no ink.
+ * out_arena[page_off + i stride + j] = 0 for ink, 255 otherwise, for both polarities: crnn_detect_words with threshold 127, polarity 1 on the
+ * result sees the ink.  out_arena has the layout of arena and is described by the same table; only the rows x cols bytes of each page are
+ * written -- row padding (stride > cols) and the bytes between pages keep what they held.  No float decision, no atomics, nothing that
+ * depends on arrival order: two calls agree bit for bit and equal sauvola_host.
+ * pages is the table in HOST memory, validated before anything is launched; pages_dev the same n_pages entries in device memory (the kernel
+ * clamps every row and column into the page on its own, and leaves alone a page whose device entry does not fit both arenas).  No workspace.
+ * -2, nothing launched, out_arena untouched: a null pointer, n_pages < 0, a parameter outside its range, rows or cols < 1 or > 4096,
+ * stride < cols, a page that does not fit arena_bytes or out_bytes, [arena, arena + arena_bytes) and [out_arena, out_arena + out_bytes)
+ * overlapping.  -3: n_pages > 65535.  n_pages == 0 launches nothing and returns 0. */
+int crnn_binarize_pages(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int n_pages,
+                        const crnn_binarize_params* prm, void* out_arena, long out_bytes, crnn_stream_t stream);
+
 /* ---- individual operators (unit-tested one by one; the drivers above chain them) --------------------------- */
 /* mode 0: C=A[M,K]*B[K,N]; 1: C=A[M,K]*Bt[N,K]^T; 2: C=At[K,M]^T*B[K,N].  bias[N]|NULL, act 0|1(relu),
  * accumulate: C+=, permP: out_row=(m%P)*(M/P)+m/P (0=off), scratch: split-reduction partials (may be NULL) */
