@@ -14,7 +14,10 @@ between the letters of a word and stay below the gaps between words; both scale 
 On unevenly lit pages (photographs) one threshold per page fails: `adaptive=` puts the Sauvola binarisation of crnn_mi355x/binarize.py in front
 of the rule, on the host and on the device alike.
 
-Out of scope: deskewing, learned detectors, anything that would make the result depend on arrival order."""
+The rule assumes that the text lines run along the pixel rows; a skewed page (a photograph) goes through crnn_mi355x/deskew.py first, and
+the boxes then refer to the deskewed page.
+
+Out of scope: learned detectors, anything that would make the result depend on arrival order."""
 import ctypes
 import re
 import warnings

@@ -27,6 +27,7 @@
 // launch; everything one workgroup must see from another crosses a kernel boundary.
 #include "common.h"
 #pragma clang fp contract(off)
+#include "otsu.h"                           // the histogram and the threshold decision, shared with deskew.hip
 
 #define DET_THREADS 256
 #define DET_WAVES (DET_THREADS / 64)
@@ -36,7 +37,8 @@ static_assert(DET_TILE_C == 64 && DET_TILE_R % 2 == 0 && DET_TILE_R % (DET_THREA
 #define DET_MAX_DIM 4096
 #define DET_MAX_GAP_X 64                    // <= DET_TILE_C: one halo word either side
 #define DET_MAX_GAP_Y 16
-#define DET_HIST_CHUNK 65536
+#define DET_HIST_CHUNK OTSU_HIST_CHUNK
+static_assert(DET_THREADS == OTSU_THREADS, "otsu.h's workgroups are the detector's");
 #define DET_REC 6                           // r0 r1 c0 c1 ink root
 #define DET_TILE_SLOTS ((DET_TILE_R / 2) * (DET_TILE_C / 2))
 #define DET_INT_MAX 0x7fffffff
@@ -50,82 +52,21 @@ struct DetPage {
 static_assert(sizeof(DetPage) == 64, "DetPage is one 64-byte record");
 
 static inline size_t det_up16(size_t n) { return (n + 15) & ~(size_t)15; }
-__host__ __device__ __forceinline__ int det_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ __forceinline__ int det_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int det_lds_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-// the page's pixel, every read inside the page and inside the arena whatever the table holds
-__device__ __forceinline__ int det_pixel(const unsigned char* arena, long arena_bytes, long off, int stride, int r, int c) {
-  long a = off + (long)r * stride + c;
-  a = a < 0 ? 0 : (a > arena_bytes - 1 ? arena_bytes - 1 : a);
-  return arena[a];
-}
-
 __global__ __launch_bounds__(DET_THREADS) void det_hist_kernel(const unsigned char* __restrict__ arena, long arena_bytes,
                                                                const crnn_page_item* __restrict__ pages, int* __restrict__ hist) {
-  __shared__ int bins[256];
-  const int p = blockIdx.y, tid = threadIdx.x;
-  const crnn_page_item pg = pages[p];
-  const int rows = det_clampi(pg.rows, 0, DET_MAX_DIM), cols = det_clampi(pg.cols, 0, DET_MAX_DIM);
-  const long n = (long)rows * cols, lo = (long)blockIdx.x * DET_HIST_CHUNK;
-  if (lo >= n) return;
-  const long hi = lo + DET_HIST_CHUNK < n ? lo + DET_HIST_CHUNK : n;
-  bins[tid] = 0;
-  __syncthreads();
-  for (long i = lo + tid; i < hi; i += DET_THREADS) {          // i grows by DET_THREADS up to hi
-    const int r = (int)(i / cols), c = (int)(i - (long)r * cols);
-    atomicAdd(&bins[det_pixel(arena, arena_bytes, pg.page_off, pg.stride, r, c)], 1);
-  }
-  __syncthreads();
-  if (bins[tid]) atomicAdd(&hist[(long)p * 256 + tid], bins[tid]);
+  otsu_hist(arena, arena_bytes, pages, hist, DET_MAX_DIM);
 }
 
 __global__ __launch_bounds__(DET_THREADS) void det_threshold_kernel(const crnn_page_item* __restrict__ pages, const int* __restrict__ hist,
                                                                     DetPage* __restrict__ meta, int threshold, int polarity, long total_pix,
                                                                     long total_slots, long total_rows) {
-  __shared__ long long sw[2][256], ss[2][256];
-  __shared__ double sc[256];
-  __shared__ int st[256];
   const int p = blockIdx.x, tid = threadIdx.x;
-  // inclusive prefix sums of h and v * h (Hillis-Steele, exact integers: any order gives the same sums)
-  const long long h = hist[(long)p * 256 + tid];
-  sw[0][tid] = h;
-  ss[0][tid] = h * tid;
-  __syncthreads();
-  int cur = 0;
-  for (int o = 1; o < 256; o <<= 1) {                           // o doubles up to 256
-    sw[cur ^ 1][tid] = sw[cur][tid] + (tid >= o ? sw[cur][tid - o] : 0);
-    ss[cur ^ 1][tid] = ss[cur][tid] + (tid >= o ? ss[cur][tid - o] : 0);
-    cur ^= 1;
-    __syncthreads();
-  }
-  const long long N = sw[cur][255], S = ss[cur][255];
-  const long long w0 = sw[cur][tid], s0 = ss[cur][tid], w1 = N - w0;
-  double score = -1.0;                                          // not admissible
-  if (tid < 255 && w0 > 0 && w1 > 0) {
-    const long long d = s0 * w1 - (S - s0) * w0;
-    const double a = (double)d / (double)w0;
-    const double b = (double)d / (double)w1;
-    score = a * b;
-  }
-  sc[tid] = score;
-  st[tid] = tid;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {                           // o halves down to 0; the first t of the strictly greatest score
-    if (tid < o) {
-      const double s2 = sc[tid + o];
-      const int t2 = st[tid + o];
-      if (s2 > sc[tid] || (s2 == sc[tid] && t2 < st[tid])) { sc[tid] = s2; st[tid] = t2; }
-    }
-    __syncthreads();
-  }
+  int t = -1, dark = 0;
+  otsu_decide(hist + (long)p * 256, threshold, polarity, t, dark);   // (otsu.h: the answer is thread 0's)
   if (tid != 0) return;
-  int t = threshold;
-  if (threshold < 0) t = sc[0] >= 0.0 ? st[0] : -1;
-  t = det_clampi(t, -1, 254);
-  int dark = polarity != 2;
-  if (t >= 0 && polarity == 0) dark = sw[cur][t] <= N - sw[cur][t];
   // this page's place in the workspace: the sums over the pages before it, from the same table the host validated
   long pix = 0, slot = 0, row = 0;
   for (int q = 0; q < p; ++q) {                                 // q counts up to p

@@ -12,7 +12,10 @@ on the network's time axis and its log-probability.
 components) instead of reading them from --boxes; with --device_ingest the boxes are found on the GPU, on the same upload the crops are cut from.
 prediction.csv then carries every box next to its prediction.
 --detect_adaptive RADIUS (with --detect) binarises every page adaptively first (Sauvola, crnn_mi355x.binarize), for unevenly lit pages; the boxes come
-from the binarised page, the crops from the grey one."""
+from the binarised page, the crops from the grey one.
+--deskew (with --detect) estimates every page's skew first and rotates the page by it (crnn_mi355x.deskew: sheared projection profiles, a
+fixed-point bilinear resampling); the boxes are found on, the crops cut from and the box columns of prediction.csv refer to the DESKEWED page.
+Every page's candidate index and angle are printed, and saved as skew.csv next to prediction.csv."""
 import argparse
 import os
 import pickle
@@ -77,6 +80,13 @@ def build_parser():
                              'Only the boxes come from the binarised page: the crops are cut from the original grey page, which is what the recogniser was trained on')
     parser.add_argument('--detect_adaptive_k', type=float, default=None, metavar='K',
                         help='with --detect_adaptive: Sauvola\'s k, used as round(K * 256) / 256 in 0..255/256 (the default 0.2 is a placeholder: tune it)')
+    parser.add_argument('--deskew', action='store_true',
+                        help='with --detect: estimate every page\'s skew (sheared projection profiles) and rotate the page by it before the boxes are '
+                             'found; boxes and crops then refer to the deskewed page.  With --device_ingest on the GPU, in a second arena')
+    parser.add_argument('--deskew_steps', type=int, default=None, metavar='N',
+                        help='with --deskew: the candidates are the slopes a * Q / 65536 for a = -N..N, N 0..64 (48 is a placeholder: tune it)')
+    parser.add_argument('--deskew_slope_step', type=int, default=None, metavar='Q',
+                        help='with --deskew: the distance Q / 65536 between two candidate slopes, Q 1..1024 with N * Q <= 16384 (256 is a placeholder: tune it)')
     return parser
 
 
@@ -92,6 +102,17 @@ def detect_params(args):
         p["adaptive"] = dict(radius=args.detect_adaptive, **({} if args.detect_adaptive_k is None else {"k": args.detect_adaptive_k}))
     elif args.detect_adaptive_k is not None:
         p["adaptive"] = dict(k=args.detect_adaptive_k)       # (parse_args refuses it: k tunes --detect_adaptive)
+    return p
+
+
+def deskew_params(args):
+    """--deskew and its flags -> keyword arguments of deskew_host / Deskewer (the ink is the detector's: its threshold or its adaptive
+    binarisation), or None without --deskew."""
+    if not args.deskew:
+        return None
+    p = {k: getattr(args, "deskew_" + k) for k in ("steps", "slope_step") if getattr(args, "deskew_" + k) is not None}
+    given = detect_params(args)
+    p.update({k: given[k] for k in ("threshold", "adaptive") if k in given})
     return p
 
 
@@ -130,6 +151,16 @@ def parse_args(argv=None):
         parser.error("the --detect_* flags tune --detect: they need it")
     if args.detect_adaptive_k is not None and args.detect_adaptive is None:
         parser.error("--detect_adaptive_k tunes --detect_adaptive: it needs it")
+    if args.deskew and not args.detect:
+        parser.error("--deskew straightens the pages --detect reads: it needs --detect")
+    if (args.deskew_steps is not None or args.deskew_slope_step is not None) and not args.deskew:
+        parser.error("--deskew_steps and --deskew_slope_step tune --deskew: they need it")
+    if args.deskew:
+        from crnn_mi355x import deskew
+        try:
+            deskew.check_params(**{k: v for k, v in deskew_params(args).items() if k in ("steps", "slope_step")})
+        except ValueError as e:
+            parser.error(str(e))
     if args.detect:
         from crnn_mi355x.detect import adaptive_setup, check_params, DEFAULTS
         try:
@@ -143,15 +174,21 @@ def parse_args(argv=None):
 
 def detect_on_device(args, names, model, img_size, U):
     """--detect --device_ingest: groups of pages go up once; the detector finds the boxes in the arena and the crops are cut from the same
-    arena, batch by batch -> ({page: boxes}, softmax maps of every box in order).  Pages without boxes are left out.  With --detect_adaptive the
-    detector binarises the arena into a second one and finds the boxes there; the crops still come from the grey arena uploaded here."""
+    arena, batch by batch -> ({page: boxes}, softmax maps of every box in order, {page: skew index} or None).  Pages without boxes are left
+    out.  With --detect_adaptive the detector binarises the arena into a second one and finds the boxes there; the crops still come from the
+    grey arena uploaded here.  With --deskew every uploaded arena is deskewed into a second one first (Deskewer.run): the boxes are found in
+    and the crops cut from that one."""
     det = U.WordDetector(**detect_params(args))
     ing = U.DeviceIngest(img_size, normed=True)
-    bboxs, maps = {}, []
+    deskewer = U.Deskewer(**deskew_params(args)) if args.deskew else None
+    bboxs, maps, skew = {}, [], ({} if args.deskew else None)
 
     def flush(group):
         pages = [U.read_img(n) for n in group]
         arena = ing.upload(pages)
+        if deskewer is not None:
+            arena = deskewer.run(None, arena=arena)              # boxes and crops refer to the deskewed pages from here on
+            skew.update(zip(group, arena.index.cpu().tolist()))
         index, rects = [], []
         for k, (name, boxes) in enumerate(zip(group, det.boxes(None, arena=arena))):
             if boxes:
@@ -164,7 +201,27 @@ def detect_on_device(args, names, model, img_size, U):
             maps.append(model.predict_on_batch(x)[:len(index[part])])
     for i in range(0, len(names), PAGES_PER_UPLOAD):
         flush(names[i:i + PAGES_PER_UPLOAD])
-    return bboxs, (np.concatenate(maps, 0) if maps else None)
+    return bboxs, (np.concatenate(maps, 0) if maps else None), skew
+
+
+def detect_on_host_deskewed(args, names, model, reader, img_size, U):
+    """--detect --deskew without --device_ingest: every page goes through deskew_host, the boxes are found on its result and the crops are
+    cut from its result (the reader would cut them from the file) -> ({page: boxes}, softmax maps of every box in order, {page: skew index})."""
+    bboxs, crops, skew = {}, [], {}
+    for name in names:
+        flat, skew[name] = U.deskew_host(U.read_img(name), **deskew_params(args))
+        rects, _ = U.detect_words_host(flat, **dict({"cap": DETECT_CAP}, **detect_params(args)))
+        if len(rects):
+            bboxs[name] = [(None, int(r[0]), int(r[2]), int(r[1]), int(r[3])) for r in rects[U.reading_order(rects)]]
+            for b in bboxs[name]:
+                pixels, _ = U.open_img(flat[b[1]:b[3], b[2]:b[4]], img_size, p=0.)
+                crops.append((U.norm(pixels, reader.mean, reader.std) if reader.normed else pixels)[:, :, np.newaxis])
+    maps = []
+    for i in range(0, len(crops), args.batch_size):
+        x = np.zeros((args.batch_size,) + tuple(img_size))
+        x[:len(crops[i:i + args.batch_size])] = np.stack(crops[i:i + args.batch_size])
+        maps.append(model.predict_on_batch(x)[:len(crops[i:i + args.batch_size])])
+    return bboxs, (np.concatenate(maps, 0) if maps else None), skew
 
 
 def main(argv=None):
@@ -221,15 +278,24 @@ def main(argv=None):
     length = len(fnames)
     bboxs = {}
     predicted = None
+    skew = None
     if args.detect:
         fnames = sorted(str(f) for f in walk())                   # every image is a page; no halving of the page set
         if args.device_ingest:
-            bboxs, predicted = detect_on_device(args, fnames, model, img_size, U)
+            bboxs, predicted, skew = detect_on_device(args, fnames, model, img_size, U)
+        elif args.deskew:
+            bboxs, predicted, skew = detect_on_host_deskewed(args, fnames, model, reader, img_size, U)
         else:
             for name in fnames:
                 rects, _ = U.detect_words_host(U.read_img(name), **dict({"cap": DETECT_CAP}, **detect_params(args)))
                 if len(rects):
                     bboxs[name] = [(None, int(r[0]), int(r[2]), int(r[1]), int(r[3])) for r in rects[U.reading_order(rects)]]
+        if skew is not None:
+            from crnn_mi355x.deskew import DEFAULTS as DESKEW_DEFAULTS, angle_of
+            q = args.deskew_slope_step if args.deskew_slope_step is not None else DESKEW_DEFAULTS["slope_step"]
+            skew = [(f, skew[f], angle_of(skew[f], q)) for f in fnames]
+            for f, a, deg in skew:
+                print(" [INFO] Skew of %s: index %d, %.2f degrees " % (os.path.basename(f), a, deg))
         empty = [f for f in fnames if f not in bboxs]
         if empty:
             print(" [INFO] %d page(s) without a word box left out: %s " % (len(empty), ", ".join(os.path.basename(f) for f in empty[:5])))
@@ -277,6 +343,8 @@ def main(argv=None):
         pd.DataFrame(table).to_csv(out_name)
         print(" [INFO] Prediction example: \n", predicted_text[:10])
         print(" [INFO] Result store in: ", out_name)
+        if skew is not None:                                 # the boxes above refer to the pages rotated by these angles
+            pd.DataFrame(skew, columns=["fname", "index", "degrees"]).to_csv(os.path.join(args.result_path, "skew.csv"))
         if args.nbest is not None:
             nbest = decoder.decode_topk(predicted[:length])
             pd.DataFrame([{"fname": f, "rank": k, "text": t, "score": v} for f, paths in zip(fnames, nbest) for k, (t, v) in enumerate(paths)],

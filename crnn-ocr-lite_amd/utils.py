@@ -17,6 +17,7 @@ from crnn_mi355x.data import (Readf, open_img, read_img, norm, parse_mjsynth, ge
 from crnn_mi355x.ingest import DeviceIngest, DeviceReadf, plan_crop, box_slices  # noqa: F401  (beyond the reference: batches built on the device)
 from crnn_mi355x.detect import WordDetector, detect_words_host, reading_order  # noqa: F401  (beyond the reference: the word boxes, found on the device)
 from crnn_mi355x.binarize import Binarizer, sauvola_host  # noqa: F401  (beyond the reference: adaptive binarisation in front of the detector)
+from crnn_mi355x.deskew import Deskewer, deskew_host, estimate_skew_host, rotate_host  # noqa: F401  (beyond the reference: page deskew in front of the detector)
 from crnn_mi355x.metrics import levenshtein, edit_distance, normalized_edit_distance  # noqa: F401
 from crnn_mi355x.metrics import Score, device_edit_distances, check_label_metric  # noqa: F401  (beyond the reference: scored on the device)
 from crnn_mi355x.callbacks import Callback, EarlyStoppingIter, ModelCheckpoint  # noqa: F401

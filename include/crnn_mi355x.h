@@ -377,6 +377,47 @@ typedef struct { int radius, k256, polarity; } crnn_binarize_params;
 int crnn_binarize_pages(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int n_pages,
                         const crnn_binarize_params* prm, void* out_arena, long out_bytes, crnn_stream_t stream);
 
+/* ---- page deskew: the skew by sheared projection profiles, the page resampled into a second arena (csrc/deskew.hip; the same rules in NumPy:
+ * crnn_mi355x.deskew) ---- */
+/* threshold, polarity: as in crnn_detect_params (-1 for Otsu per page, or 0..254; 0 auto / 1 dark ink / 2 bright ink).  The candidates are the
+ * slopes a * slope_step / 65536 (rows per column) for a = -steps .. steps: steps 0..64, slope_step 1..1024, steps * slope_step <= 16384 (a
+ * slope of at most 0.25, about 14 degrees).  fill 0..255: the value of a sample outside the page, or -1: the nearest page pixel.  The package's
+ * defaults steps = 48, slope_step = 256 (0.22 degrees apart, up to +-10.6 degrees), fill = -1 are PLACEHOLDERS, as the detection defaults. */
+typedef struct { int threshold, polarity, steps, slope_step, fill; } crnn_deskew_params;
+#define CRNN_DESKEW_STRIPS 4       /* a workgroup of the estimate takes this many 64-column strips (one ballot word per row each) ... */
+#define CRNN_DESKEW_BAND_R 192     /* ... of a band of this many rows: 192 + 16 * 4 bins of a candidate's profile, one per lane of 256 */
+/* ESTIMATE, integers throughout.  The ink of a page is the ink crnn_detect_words sees at the same threshold / polarity (THRESHOLD and POLARITY
+ * above, Otsu and the auto polarity included).  For each candidate a, with s = a * slope_step: an ink pixel (r, c) falls into bin r - off,
+ *   off = ((c - (cols >> 1)) * s + 32768) >> 16          (an arithmetic shift: the floor; |off| <= 512)
+ * P_a[b] = the number of ink pixels of bin b (<= cols: one per column), score_a = sum_b P_a[b]^2 in int64 (< 2^12 * 2^24 = 2^36).  The
+ * answer is the a of the greatest score; among equal scores the smallest |a|, then the negative one.  A page without ink: all scores 0,
+ * answer 0.  index [P] int32 = the signed a, scores [P][2 steps + 1] int64 = score_{-steps} .. score_{steps}: both in DEVICE memory.
+ * Integer atomics only (add on histogram and profile words): two calls agree bit for bit and equal estimate_skew_host.
+ * ws: crnn_deskew_workspace_bytes(pages, P, prm) bytes, 16-byte aligned, no zeroing owed: P * 1088 + 4 B per candidate and bin, a page
+ * having rows + 2 ((((cols >> 1) + 1) * 16384 >> 16) + 2) bins (0 for a table or parameters that crnn_deskew_estimate refuses).
+ *
+ * ROTATE.  For a page of index a (read from index_dev [P] int32 in device memory: estimate -> rotate needs no read-back; an index outside
+ * -steps .. steps counts as 0), s = a * slope_step, t = s / 65536: C = rint(65536 / sqrt(1 + t^2)), S = rint(s / sqrt(1 + t^2)), computed on
+ * the host in IEEE double (sqrt and / are correctly rounded: the C library and NumPy agree).  For the output pixel (r, c):
+ *   dr = 2 r - (rows - 1), dc = 2 c - (cols - 1)
+ *   X = C dc - S dr + ((cols - 1) << 16), Y = S dc + C dr + ((rows - 1) << 16)       (int32: see csrc/deskew.hip)
+ *   c0 = X >> 17, r0 = Y >> 17, fx = (X >> 9) & 255, fy = (Y >> 9) & 255
+ *   out = ((256 - fx) (256 - fy) p[r0][c0] + fx (256 - fy) p[r0][c0 + 1] + (256 - fx) fy p[r0 + 1][c0] + fx fy p[r0 + 1][c0 + 1] + 32768) >> 16
+ * where a sample outside the page is `fill`, or for fill = -1 the page's pixel at the coordinates clamped into it.  Index 0 reproduces the
+ * page byte for byte.  out_arena has the layout of arena and is described by the same table; only the rows x cols bytes of each page are
+ * written.  No atomics: two calls agree bit for bit and equal rotate_host.
+ *
+ * Both: pages is the table in HOST memory, validated before anything is launched; pages_dev the same P entries in device memory (the kernels
+ * clamp every read into the page and the arena on their own; a page whose device entry does not fit the validated layout scores 0 / is left
+ * alone).  -2, nothing launched, outputs untouched: a null pointer, P < 0, a parameter outside its range, rows or cols < 1, stride < cols, a
+ * page that does not fit arena_bytes (or out_bytes), a short or misaligned workspace, [arena, arena + arena_bytes) and [out_arena, out_arena
+ * + out_bytes) overlapping.  -3: a page above 4096 in either direction, P > 65535.  P == 0 launches nothing and returns 0. */
+size_t crnn_deskew_workspace_bytes(const crnn_page_item* pages, int P, const crnn_deskew_params* prm);
+int crnn_deskew_estimate(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int P,
+                         const crnn_deskew_params* prm, int* index, long long* scores, void* ws, size_t ws_bytes, crnn_stream_t stream);
+int crnn_rotate_pages(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int P,
+                      const int* index_dev, const crnn_deskew_params* prm, void* out_arena, long out_bytes, crnn_stream_t stream);
+
 /* ---- individual operators (unit-tested one by one; the drivers above chain them) --------------------------- */
 /* mode 0: C=A[M,K]*B[K,N]; 1: C=A[M,K]*Bt[N,K]^T; 2: C=At[K,M]^T*B[K,N].  bias[N]|NULL, act 0|1(relu),
  * accumulate: C+=, permP: out_row=(m%P)*(M/P)+m/P (0=off), scratch: split-reduction partials (may be NULL) */
