@@ -15,12 +15,12 @@ import ctypes
 import numpy as np
 
 from . import native
-from .detect import MAX_DIM, _header_int, page_table
+from .pages import check_page, device_lib, header_int, upload_pages
 
 MAX_RADIUS, RANGE = 31, 128
 PARAMS = ("radius", "k256", "polarity")
 DEFAULTS = dict(radius=15, k256=51, polarity=1)              # placeholders: tune them on labelled pages
-STRIP_C, BAND_R = _header_int("CRNN_BINARIZE_STRIP_C"), _header_int("CRNN_BINARIZE_BAND_R")   # csrc/binarize.hip: a workgroup's columns and rows
+STRIP_C, BAND_R = header_int("CRNN_BINARIZE_STRIP_C"), header_int("CRNN_BINARIZE_BAND_R")   # csrc/binarize.hip: a workgroup's columns and rows
 
 
 class crnn_binarize_params(ctypes.Structure):
@@ -79,9 +79,7 @@ def sauvola_host(page, radius=DEFAULTS["radius"], k256=DEFAULTS["k256"], polarit
     is ink and 255 elsewhere.  Summed-area tables in int64, windows clipped to the page, the exact integer square root, one int64
     comparison.  radius and k256 default to placeholders."""
     p = check_params(radius, k256, polarity, k)
-    page = np.asarray(page)
-    if page.ndim != 2 or page.dtype != np.uint8 or page.size == 0 or max(page.shape) > MAX_DIM:
-        raise ValueError("a page is a non-empty (H, W) uint8 array of at most %d x %d, not %s %s" % (MAX_DIM, MAX_DIM, page.dtype, page.shape))
+    page = check_page(page)
     r, kk = p["radius"], p["k256"]
     rows, cols = page.shape
     v = page.astype(np.int64) if p["polarity"] == 1 else 255 - page.astype(np.int64)
@@ -104,27 +102,20 @@ class Binarizer:
     read back and no host copy of the result is made (`host` of the returned arena is None).  radius and k256 default to placeholders."""
 
     def __init__(self, device=None, radius=DEFAULTS["radius"], k256=DEFAULTS["k256"], polarity=DEFAULTS["polarity"], k=None):
-        import torch
         self.params = check_params(radius, k256, polarity, k)
-        if not torch.cuda.is_available():
-            raise RuntimeError("Binarizer needs an AMD GPU (gfx950); the host path is sauvola_host")
-        self.lib = native.lib()
-        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        self.lib, self.device = device_lib("Binarizer", "sauvola_host", device)
         self._prm = crnn_binarize_params(**self.params)
 
     def run(self, pages, arena=None):
         import torch
         from .engine import _ptr, _stream
-        from .ingest import PageArena, upload_pages
         if arena is None:
             arena = upload_pages(pages, self.device)
         with torch.cuda.device(self.device):
-            out = torch.zeros(max(arena.nbytes, 1), dtype=torch.uint8, device=self.device)
+            out = arena.blank()
             P = len(arena.pages)
             if P:
-                table = page_table(arena.pages, arena.offsets)
-                table_dev = torch.from_numpy(table.view(np.uint8)).to(self.device)
-                native.check(self.lib.crnn_binarize_pages(ctypes.c_void_p(arena.dev.data_ptr()), arena.nbytes, table.ctypes.data_as(ctypes.c_void_p),
-                                                          _ptr(table_dev), P, ctypes.byref(self._prm), _ptr(out), arena.nbytes, _stream()),
+                native.check(self.lib.crnn_binarize_pages(ctypes.c_void_p(arena.dev.data_ptr()), arena.nbytes, arena.table.ctypes.data_as(ctypes.c_void_p),
+                                                          _ptr(arena.table_dev), P, ctypes.byref(self._prm), _ptr(out.dev), arena.nbytes, _stream()),
                              "binarize_pages")
-        return PageArena(arena.pages, arena.offsets, arena.nbytes, None, out)
+        return out

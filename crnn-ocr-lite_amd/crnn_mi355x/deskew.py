@@ -20,12 +20,14 @@ import math
 import numpy as np
 
 from . import native
-from .detect import DEFAULTS as DETECT_DEFAULTS, MAX_DIM, _header_int, adaptive_setup, ink_mask, page_table
+from .binarize import Binarizer, sauvola_host
+from .detect import DEFAULTS as DETECT_DEFAULTS, adaptive_setup, ink_mask
+from .pages import MAX_DIM, check_page, device_lib, header_int, upload_pages
 
 MAX_STEPS, MAX_SLOPE_STEP, MAX_SLOPE = 64, 1024, 16384       # steps * slope_step <= 16384: a slope of at most 0.25
 PARAMS = ("threshold", "polarity", "steps", "slope_step", "fill")
 DEFAULTS = dict(threshold=DETECT_DEFAULTS["threshold"], polarity=DETECT_DEFAULTS["polarity"], steps=48, slope_step=256, fill=-1)   # placeholders
-STRIPS, BAND_R = _header_int("CRNN_DESKEW_STRIPS"), _header_int("CRNN_DESKEW_BAND_R")   # csrc/deskew.hip: a workgroup's 64-column strips and rows
+STRIPS, BAND_R = header_int("CRNN_DESKEW_STRIPS"), header_int("CRNN_DESKEW_BAND_R")   # csrc/deskew.hip: a workgroup's 64-column strips and rows
 
 
 class crnn_deskew_params(ctypes.Structure):
@@ -67,18 +69,10 @@ def rotation_pair(index, slope_step=DEFAULTS["slope_step"]):
     return int(np.rint(65536.0 / root)), int(np.rint(float(s) / root))
 
 
-def _check_page(page):
-    page = np.asarray(page)
-    if page.ndim != 2 or page.dtype != np.uint8 or page.size == 0 or max(page.shape) > MAX_DIM:
-        raise ValueError("a page is a non-empty (H, W) uint8 array of at most %d x %d, not %s %s" % (MAX_DIM, MAX_DIM, page.dtype, page.shape))
-    return page
-
-
 def _estimate_input(page, threshold, polarity, adaptive):
     """-> (the page the estimate reads, threshold, polarity): the Sauvola-binarised page with threshold 127 and dark ink under `adaptive`."""
     adaptive, threshold, polarity = adaptive_setup(adaptive, threshold, polarity)
     if adaptive is not None:
-        from .binarize import sauvola_host
         page = sauvola_host(page, **adaptive)
     return page, threshold, polarity
 
@@ -87,7 +81,7 @@ def skew_scores_host(page, threshold=DEFAULTS["threshold"], polarity=DEFAULTS["p
                      slope_step=DEFAULTS["slope_step"], adaptive=None):
     """The estimate's scores in NumPy: (2 steps + 1,) int64, score[a + steps] = sum_b P_a[b]^2 of the sheared row profile of the page's ink
     (detect.ink_mask at the same threshold / polarity)."""
-    page, threshold, polarity = _estimate_input(_check_page(page), threshold, polarity, adaptive)
+    page, threshold, polarity = _estimate_input(check_page(page), threshold, polarity, adaptive)
     p = check_params(threshold, polarity, steps, slope_step)
     ink, _, _ = ink_mask(page, p["threshold"], p["polarity"])
     rows, cols = page.shape
@@ -120,7 +114,7 @@ def rotate_host(page, index, slope_step=DEFAULTS["slope_step"], fill=DEFAULTS["f
     """The rotation in NumPy (the host path, and the oracle of the device kernel): the page resampled about its centre by atan(index *
     slope_step / 65536), fixed-point bilinear weights of 8 bits; a sample outside the page is `fill`, or the nearest page pixel for
     fill = -1.  Index 0 returns the page's bytes."""
-    page = _check_page(page)
+    page = check_page(page)
     p = check_params(steps=0, slope_step=slope_step, fill=fill)
     if int(index) != index or abs(int(index)) * p["slope_step"] > MAX_SLOPE:
         raise ValueError("index * slope_step is an integer of at most %d in magnitude, not %r * %r" % (MAX_SLOPE, index, slope_step))
@@ -162,71 +156,57 @@ class Deskewer:
     rotated is always the grey arena.  steps, slope_step and fill default to placeholders."""
 
     def __init__(self, device=None, adaptive=None, **params):
-        import torch
         unknown = set(params) - set(PARAMS)
         if unknown:
             raise TypeError("unknown deskew parameters: %s" % sorted(unknown))
         self.adaptive, threshold, polarity = adaptive_setup(adaptive, params.get("threshold", DEFAULTS["threshold"]),
                                                             params.get("polarity", DEFAULTS["polarity"]))
         self.params = check_params(**dict(DEFAULTS, **dict(params, threshold=threshold, polarity=polarity)))
-        if not torch.cuda.is_available():
-            raise RuntimeError("Deskewer needs an AMD GPU (gfx950); the host path is deskew_host")
-        self.lib = native.lib()
-        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        self.lib, self.device = device_lib("Deskewer", "deskew_host", device)
         self._prm = crnn_deskew_params(**self.params)
-        self._binarizer = None
-        if self.adaptive is not None:
-            from .binarize import Binarizer
-            self._binarizer = Binarizer(self.device, **self.adaptive)
+        self._binarizer = None if self.adaptive is None else Binarizer(self.device, **self.adaptive)
 
     def _estimate(self, arena):
-        """-> (table, table_dev, out): out holds the P int64 score rows, then the P int32 indices (device)."""
+        """-> the P int64 score rows, then the P int32 indices, in one device tensor."""
         import torch
         from .engine import _ptr, _stream
         P, n = len(arena.pages), 2 * self.params["steps"] + 1
         source = arena if self._binarizer is None else self._binarizer.run(None, arena=arena)   # a new arena; the caller's is not written
-        table = page_table(arena.pages, arena.offsets)
-        table_dev = torch.from_numpy(table.view(np.uint8)).to(self.device)
-        host = table.ctypes.data_as(ctypes.c_void_p)
+        host = arena.table.ctypes.data_as(ctypes.c_void_p)
         need = self.lib.crnn_deskew_workspace_bytes(host, P, ctypes.byref(self._prm))
         if need == 0:
             raise native.CrnnError("libcrnn_mi355x deskew_estimate: a page above %d x %d, or too many pages in one call" % (MAX_DIM, MAX_DIM))
         ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         out = torch.empty(P * n * 8 + P * 4, dtype=torch.uint8, device=self.device)
         index_ptr = ctypes.c_void_p(out.data_ptr() + P * n * 8)
-        native.check(self.lib.crnn_deskew_estimate(ctypes.c_void_p(source.dev.data_ptr()), source.nbytes, host, _ptr(table_dev), P,
+        native.check(self.lib.crnn_deskew_estimate(ctypes.c_void_p(source.dev.data_ptr()), source.nbytes, host, _ptr(arena.table_dev), P,
                                                    ctypes.byref(self._prm), index_ptr, _ptr(out), _ptr(ws), need, _stream()), "deskew_estimate")
-        return table, table_dev, out
+        return out
 
     def estimate(self, pages, arena=None):
         import torch
-        from .ingest import upload_pages
         if arena is None:
             arena = upload_pages(pages, self.device)
         P, n = len(arena.pages), 2 * self.params["steps"] + 1
         if P == 0:
             return []
         with torch.cuda.device(self.device):
-            back = self._estimate(arena)[2].cpu().numpy()                  # the one read-back
+            back = self._estimate(arena).cpu().numpy()                     # the one read-back
         scores, index = back[:P * n * 8].view(np.int64).reshape(P, n), back[P * n * 8:].view(np.int32)
         return [(int(index[k]), scores[k].copy()) for k in range(P)]
 
     def run(self, pages, arena=None):
         import torch
         from .engine import _ptr, _stream
-        from .ingest import PageArena, upload_pages
         if arena is None:
             arena = upload_pages(pages, self.device)
         P, n = len(arena.pages), 2 * self.params["steps"] + 1
         with torch.cuda.device(self.device):
-            out = torch.zeros(max(arena.nbytes, 1), dtype=torch.uint8, device=self.device)
-            index = torch.zeros(P, dtype=torch.int32, device=self.device)
+            flat = arena.blank()
+            flat.index = torch.zeros(P, dtype=torch.int32, device=self.device)
             if P:
-                table, table_dev, est = self._estimate(arena)
-                index = est[P * n * 8:].view(torch.int32)
-                native.check(self.lib.crnn_rotate_pages(ctypes.c_void_p(arena.dev.data_ptr()), arena.nbytes, table.ctypes.data_as(ctypes.c_void_p),
-                                                        _ptr(table_dev), P, _ptr(index), ctypes.byref(self._prm), _ptr(out), arena.nbytes,
-                                                        _stream()), "rotate_pages")
-        flat = PageArena(arena.pages, arena.offsets, arena.nbytes, None, out)
-        flat.index = index
+                flat.index = self._estimate(arena)[P * n * 8:].view(torch.int32)
+                native.check(self.lib.crnn_rotate_pages(ctypes.c_void_p(arena.dev.data_ptr()), arena.nbytes, arena.table.ctypes.data_as(ctypes.c_void_p),
+                                                        _ptr(arena.table_dev), P, _ptr(flat.index), ctypes.byref(self._prm), _ptr(flat.dev),
+                                                        arena.nbytes, _stream()), "rotate_pages")
         return flat

@@ -19,40 +19,25 @@ the boxes then refer to the deskewed page.
 
 Out of scope: learned detectors, anything that would make the result depend on arrival order."""
 import ctypes
-import re
 import warnings
 
 import numpy as np
 
 from . import native
+from .binarize import Binarizer, adaptive_params, sauvola_host
+from .pages import MAX_DIM, PAGE_DTYPE, check_page, device_lib, header_int, upload_pages  # noqa: F401  (PAGE_DTYPE: the GPU tests' earlier versions take it from here)
 
-MAX_DIM, MAX_GAP_X, MAX_GAP_Y = 4096, 64, 16
+MAX_GAP_X, MAX_GAP_Y = 64, 16
 PARAMS = ("threshold", "polarity", "gap_x", "gap_y", "min_w", "min_h", "min_ink", "max_w", "max_h", "cap")
 DEFAULTS = dict(threshold=-1, polarity=0, gap_x=8, gap_y=0, min_w=3, min_h=3, min_ink=6, max_w=0, max_h=0, cap=1024)
 
 
-def _header_int(name):
-    m = re.search(r"#define\s+%s\s+(\d+)" % name, open(native.HEADER).read())
-    if m is None:
-        raise RuntimeError("%s is not defined in %s" % (name, native.HEADER))
-    return int(m.group(1))
-
-
-TILE_R, TILE_C = _header_int("CRNN_DETECT_TILE_R"), _header_int("CRNN_DETECT_TILE_C")   # csrc/detect.hip labels tiles of this size in LDS
-
-
-class crnn_page_item(ctypes.Structure):
-    """include/crnn_mi355x.h: crnn_page_item."""
-    _fields_ = [("page_off", ctypes.c_long), ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("stride", ctypes.c_int)]
+TILE_R, TILE_C = header_int("CRNN_DETECT_TILE_R"), header_int("CRNN_DETECT_TILE_C")   # csrc/detect.hip labels tiles of this size in LDS
 
 
 class crnn_detect_params(ctypes.Structure):
     """include/crnn_mi355x.h: crnn_detect_params."""
     _fields_ = [(n, ctypes.c_int) for n in PARAMS]
-
-
-PAGE_DTYPE = np.dtype([("page_off", np.dtype("l")), ("rows", np.intc), ("cols", np.intc), ("stride", np.intc)], align=True)
-assert PAGE_DTYPE.itemsize == ctypes.sizeof(crnn_page_item)
 
 
 def check_params(p):
@@ -83,9 +68,7 @@ def otsu_threshold(hist):
 
 def ink_mask(page, threshold=-1, polarity=0):
     """-> (ink (rows, cols) bool, t, ink_is_dark)."""
-    page = np.asarray(page)
-    if page.ndim != 2 or page.dtype != np.uint8 or page.size == 0 or max(page.shape) > MAX_DIM:
-        raise ValueError("a page is a non-empty (H, W) uint8 array of at most %d x %d, not %s %s" % (MAX_DIM, MAX_DIM, page.dtype, page.shape))
+    page = check_page(page)
     h = np.bincount(page.ravel(), minlength=256)
     t = int(threshold) if threshold >= 0 else otsu_threshold(h)
     if t < 0:
@@ -175,7 +158,6 @@ def adaptive_setup(adaptive, threshold, polarity):
     if threshold != DEFAULTS["threshold"] or polarity != DEFAULTS["polarity"]:
         raise ValueError("adaptive binarisation decides what is ink: it goes with neither threshold (%r) nor polarity (%r); the ink's polarity "
                          "is adaptive['polarity']" % (threshold, polarity))
-    from .binarize import adaptive_params
     return adaptive_params(adaptive), 127, 1
 
 
@@ -187,7 +169,6 @@ def detect_words_host(page, threshold=-1, polarity=0, gap_x=DEFAULTS["gap_x"], g
     with threshold 127 and dark ink, so `ink` counts the binarised ink pixels of a box."""
     adaptive, threshold, polarity = adaptive_setup(adaptive, threshold, polarity)
     if adaptive is not None:
-        from .binarize import sauvola_host
         page = sauvola_host(page, **adaptive)
     p = check_params(dict(threshold=threshold, polarity=polarity, gap_x=gap_x, gap_y=gap_y, min_w=min_w, min_h=min_h, min_ink=min_ink,
                           max_w=max_w, max_h=max_h, cap=1 if cap is None else cap))
@@ -225,45 +206,29 @@ def to_boxes(rects):
     return [(None, int(rects[k, 0]), int(rects[k, 2]), int(rects[k, 1]), int(rects[k, 3])) for k in reading_order(rects)]
 
 
-def page_table(pages, offsets):
-    """The crnn_page_item table of pages packed as ingest.pack_arena packs them."""
-    t = np.zeros(len(pages), PAGE_DTYPE)
-    for k, (pg, off) in enumerate(zip(pages, offsets)):
-        t[k] = (off, pg.shape[0], pg.shape[1], pg.shape[1])
-    return t
-
-
 class WordDetector:
-    """detect_words_host on the device: pages go up once (ingest.upload_pages, or an arena `DeviceIngest.upload` already made), one launch
+    """detect_words_host on the device: pages go up once (pages.upload_pages, or an arena `DeviceIngest.upload` already made), one launch
     sequence finds the boxes of every page, one copy brings rects and info back.  Parameters as detect_words_host; `cap` bounds the boxes
     per page (a page with more warns once, by its index).  The defaults of gap_x, gap_y and the filter are placeholders.
     adaptive (True, or a dict of radius, k256, polarity): binarize.Binarizer makes a binarised arena on the device first and the launch
     sequence reads that one, with threshold 127 and dark ink; the arena passed in stays as it is (the crops are cut from it)."""
 
     def __init__(self, device=None, adaptive=None, **params):
-        import torch
         unknown = set(params) - set(PARAMS)
         if unknown:
             raise TypeError("unknown detection parameters: %s" % sorted(unknown))
         self.adaptive, threshold, polarity = adaptive_setup(adaptive, params.get("threshold", DEFAULTS["threshold"]),
                                                             params.get("polarity", DEFAULTS["polarity"]))
         self.params = check_params(dict(DEFAULTS, **dict(params, threshold=threshold, polarity=polarity)))
-        if not torch.cuda.is_available():
-            raise RuntimeError("WordDetector needs an AMD GPU (gfx950); the host path is detect_words_host")
-        self.lib = native.lib()
-        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        self.lib, self.device = device_lib("WordDetector", "detect_words_host", device)
         self._prm = crnn_detect_params(**self.params)
         self._warned = False
-        self._binarizer = None
-        if self.adaptive is not None:
-            from .binarize import Binarizer
-            self._binarizer = Binarizer(self.device, **self.adaptive)
+        self._binarizer = None if self.adaptive is None else Binarizer(self.device, **self.adaptive)
 
     def detect(self, pages, arena=None):
         """pages: list of (H, W) uint8 arrays, or None with an `arena` that holds them -> [(rects (kept, 5) int32, info (4,) int32) per page]."""
         import torch
         from .engine import _ptr, _stream
-        from .ingest import upload_pages
         if arena is None:
             arena = upload_pages(pages, self.device)
         P, cap = len(arena.pages), self.params["cap"]
@@ -271,17 +236,15 @@ class WordDetector:
             return []
         if self._binarizer is not None:
             arena = self._binarizer.run(None, arena=arena)                 # a new arena on the device; the caller's is not written
-        table = page_table(arena.pages, arena.offsets)
         with torch.cuda.device(self.device):
-            table_dev = torch.from_numpy(table.view(np.uint8)).to(self.device)
-            host = table.ctypes.data_as(ctypes.c_void_p)
+            host = arena.table.ctypes.data_as(ctypes.c_void_p)
             need = self.lib.crnn_detect_workspace_bytes(host, P, ctypes.byref(self._prm))
             if need == 0:
                 raise native.CrnnError("libcrnn_mi355x detect_words: a page above %d x %d, or more than 2^31 pixels in one call" % (MAX_DIM, MAX_DIM))
             ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             out = torch.empty(P * cap * 5 + P * 4, dtype=torch.int32, device=self.device)
             info_ptr = ctypes.c_void_p(out.data_ptr() + 4 * P * cap * 5)
-            native.check(self.lib.crnn_detect_words(ctypes.c_void_p(arena.dev.data_ptr()), arena.nbytes, host, _ptr(table_dev), P, ctypes.byref(self._prm),
+            native.check(self.lib.crnn_detect_words(ctypes.c_void_p(arena.dev.data_ptr()), arena.nbytes, host, _ptr(arena.table_dev), P, ctypes.byref(self._prm),
                                                     _ptr(out), info_ptr, _ptr(ws), need, _stream()), "detect_words")
             back = out.cpu().numpy()                                       # the one read-back
         rects, info = back[:P * cap * 5].reshape(P, cap, 5), back[P * cap * 5:].reshape(P, 4)

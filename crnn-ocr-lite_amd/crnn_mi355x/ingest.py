@@ -14,6 +14,7 @@ import numpy as np
 
 from . import native
 from .data import Readf, norm, read_img, _word_of
+from .pages import arena_layout, device_lib, pack_arena, upload_pages
 
 
 class crnn_crop_item(ctypes.Structure):
@@ -26,7 +27,6 @@ class crnn_crop_item(ctypes.Structure):
 ITEM_DTYPE = np.dtype([(n, {ctypes.c_long: np.dtype("l"), ctypes.c_int: np.intc, ctypes.c_double: np.float64}[t])
                        for n, t in crnn_crop_item._fields_], align=True)
 assert ITEM_DTYPE.itemsize == ctypes.sizeof(crnn_crop_item)
-_ARENA_ALIGN = 16
 
 
 def _place(size, target, axis, p, strict):
@@ -97,49 +97,6 @@ def box_slices(box, shape):
     return r0, r1, c0, c1
 
 
-def arena_layout(pages):
-    """-> ([byte offset per page], arena size): pages back to back, each one row-major without row padding, on 16-byte boundaries."""
-    offs, pos = [], 0
-    for pg in pages:
-        if pg.ndim != 2 or pg.dtype != np.uint8 or pg.size == 0:
-            raise ValueError("a page is a non-empty (H, W) uint8 array, not %s %s" % (pg.dtype, pg.shape))
-        offs.append(pos)
-        pos += -(-pg.size // _ARENA_ALIGN) * _ARENA_ALIGN
-    return offs, pos
-
-
-def pack_arena(pages, out=None):
-    """Copy the pages into one uint8 arena (a view of `out` when given) -> (arena, offsets)."""
-    offs, total = arena_layout(pages)
-    arena = np.zeros(total, np.uint8) if out is None else out[:total]
-    for pg, o in zip(pages, offs):
-        arena[o:o + pg.size].reshape(pg.shape)[...] = pg
-    return arena, offs
-
-
-class PageArena:
-    """Pages on the device: `dev` is the uint8 arena (pack_arena's layout), `pages` / `offsets` what it holds.  One upload serves the word
-    detector (detect.WordDetector) and any number of crop launches (DeviceIngest.crops(arena=...)); the page-locked source of the copy
-    lives as long as the arena."""
-
-    def __init__(self, pages, offsets, nbytes, host, dev):
-        self.pages, self.offsets, self.nbytes, self.host, self.dev = pages, offsets, nbytes, host, dev
-
-
-def upload_pages(pages, device):
-    """list of (H, W) uint8 arrays -> PageArena on `device`: one page-locked buffer, one asynchronous copy on the current stream."""
-    import torch
-    pages = [np.ascontiguousarray(pg) for pg in pages]
-    offs, nbytes = arena_layout(pages)
-    device = torch.device(device)
-    with torch.cuda.device(device):
-        host = torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
-        pack_arena(pages, out=host.numpy())
-        dev = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-        dev.copy_(host, non_blocking=True)
-    return PageArena(pages, offs, nbytes, host, dev)
-
-
 def build_table(pages, offsets, page_index, rects, plans, img_size, out=None):
     """The crnn_crop_item table of n crops: page_index (n,), rects (n, 4) = r0, r1, c0, c1, plans = (upscale, s0, s1, b0, b1, p0, p1) arrays
     as plan_crops returns them.  The scale factors are n_in / float(n_out) in Python arithmetic, as data._linear_taps computes them."""
@@ -179,12 +136,9 @@ class DeviceIngest:
 
     def __init__(self, img_size, normed=True, mean=118.24236953981779, std=36.72835353999682, device=None):
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("DeviceIngest needs an AMD GPU (gfx950); the host path is data.Readf")
-        self.lib = native.lib()
+        self.lib, self.device = device_lib("DeviceIngest", "data.Readf", device)
         self.img_size = tuple(img_size)
         self.T0, self.T1 = int(img_size[0]), int(img_size[1])
-        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.table = torch.from_numpy(norm_table(normed, mean, std)).to(self.device)
         self._slots = [{"host": None, "dev": None, "copied": torch.cuda.Event()} for _ in range(self._SLOTS)]
         self._next = 0
@@ -202,8 +156,8 @@ class DeviceIngest:
         return s
 
     def upload(self, pages):
-        """Pages -> PageArena on this ingest's device, for crops(..., arena=) and WordDetector.detect(arena=): the pages go up once, and
-        each crop launch afterwards uploads its box table only."""
+        """Pages -> PageArena (pages.py: the arena every page stage shares) on this ingest's device, for crops(..., arena=) and
+        WordDetector.detect(arena=): the pages go up once, and each crop launch afterwards uploads its box table only."""
         return upload_pages(pages, self.device)
 
     def crops(self, pages, page_index, rects, plans, batch=None, return_u8=False, arena=None):

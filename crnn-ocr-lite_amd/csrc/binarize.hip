@@ -1,4 +1,4 @@
-// Adaptive (Sauvola) binarisation of page images on the device: uint8 pages in the arena crnn_detect_words reads -> 0 (ink) / 255 pages in an
+// Adaptive (Sauvola) binarisation of page images on the device: uint8 pages in an arena (pages.h defines it) -> 0 (ink) / 255 pages in an
 // arena of the same layout.  Integer-only (the rule: include/crnn_mi355x.h; the same rule in NumPy: crnn_mi355x/binarize.py): the window sums
 // S = sum v and Q = sum v^2 over the (2 r + 1)^2 window clipped to the page, D = n Q - S^2, sd = floor(sqrt(D)) made exact by two correction
 // loops, and one int64 comparison.  No float decision, no atomics: two calls agree bit for bit and equal the host.
@@ -16,7 +16,7 @@
 //     total at most.  The 192 decisions of a row are made by the first three wavefronts, whole (lane t decides column C0 + t from the prefixes
 //     at LDS positions t + 32 + r and t + 32 - r - 1), not by the middle 192 lanes of four.
 // 32-bit arithmetic up to S, Q, v n^2 and S n (all < 2^32); 64-bit for D, sd and the comparison.  Stores are plain byte stores.
-#include "common.h"
+#include "pages.h"
 #pragma clang fp contract(off)
 
 #define BIN_THREADS 256
@@ -24,17 +24,14 @@
 #define BIN_STRIP_C CRNN_BINARIZE_STRIP_C
 #define BIN_BAND_R CRNN_BINARIZE_BAND_R
 #define BIN_HALO ((BIN_THREADS - BIN_STRIP_C) / 2)
-#define BIN_MAX_DIM 4096
 #define BIN_MAX_RADIUS 31
 static_assert(BIN_STRIP_C + 2 * BIN_HALO == BIN_THREADS && BIN_HALO > BIN_MAX_RADIUS, "one loaded column per lane, the halo wider than any radius");
-
-__host__ __device__ __forceinline__ int bin_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // The byte of row y of a column of the page (`col`: the column's first byte, the column clamped into the page).  The load is unconditional --
 // the row is clamped into the page, and the kernel has checked once that the page lies inside the arena -- so that the loads of a row are
 // issued together and ahead of their use, with no branch and no wait between them; bin_value then makes v of it, 0 outside the page.
 __device__ __forceinline__ unsigned bin_load(const unsigned char* col, int stride, int rows, int y) {
-  return col[(long)bin_clampi(y, 0, rows - 1) * stride];
+  return col[(long)page_clampi(y, 0, rows - 1) * stride];
 }
 __device__ __forceinline__ unsigned bin_value(unsigned p, bool in, bool light) { return in ? (light ? 255u - p : p) : 0u; }
 
@@ -70,15 +67,12 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_sauvola_kernel(const unsigned
   __shared__ unsigned pS[2][BIN_THREADS], pQ[2][BIN_THREADS];   // wave-local inclusive prefixes of the column sums, by row parity
   __shared__ unsigned tS[2][BIN_WAVES], tQ[2][BIN_WAVES];       // and each wavefront's total
   const crnn_page_item pg = pages[blockIdx.z];
-  const int rows = bin_clampi(pg.rows, 0, BIN_MAX_DIM), cols = bin_clampi(pg.cols, 0, BIN_MAX_DIM);
+  const int rows = page_clampi(pg.rows, 0, PAGE_MAX_DIM), cols = page_clampi(pg.cols, 0, PAGE_MAX_DIM);
   const int C0 = (int)blockIdx.x * BIN_STRIP_C, R0 = (int)blockIdx.y * BIN_BAND_R;
   if (C0 >= cols || R0 >= rows) return;                         // (uniform over the workgroup)
-  // The device entry must fit both arenas, as the host's copy of it did; a page whose entry does not is left alone.  Checked once, here: below,
-  // rows and columns are clamped into the page and no load or store needs a check of its own.
-  const long span = (long)(rows - 1) * pg.stride + cols;
-  if (pg.page_off < 0 || pg.stride < cols || pg.page_off > arena_bytes - span || pg.page_off > out_bytes - span) return;   // (uniform)
-  const int r = bin_clampi(radius, 1, BIN_MAX_RADIUS);
-  const unsigned k = (unsigned)bin_clampi(k256, 0, 255);
+  if (page_outside(pg, rows, cols, arena_bytes, out_bytes)) return;   // (uniform; pages.h: no load or store below needs a check of its own)
+  const int r = page_clampi(radius, 1, BIN_MAX_RADIUS);
+  const unsigned k = (unsigned)page_clampi(k256, 0, 255);
   const bool light = polarity == 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // two roles per lane: it SUMS the loaded column c = C0 - 32 + tid, and (the first 192 lanes, three whole wavefronts) it DECIDES the pixel of
@@ -90,8 +84,8 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_sauvola_kernel(const unsigned
   const bool split = (hi >> 6) != (lo >> 6);
   const int nc = (cw + r < cols - 1 ? cw + r : cols - 1) - (cw - r > 0 ? cw - r : 0) + 1;
   const int rend = R0 + BIN_BAND_R < rows ? R0 + BIN_BAND_R : rows;
-  const unsigned char* col = arena + pg.page_off + bin_clampi(c, 0, cols - 1);
-  const unsigned char* colw = arena + pg.page_off + bin_clampi(cw, 0, cols - 1);
+  const unsigned char* col = arena + pg.page_off + page_clampi(c, 0, cols - 1);
+  const unsigned char* colw = arena + pg.page_off + page_clampi(cw, 0, cols - 1);
 
   unsigned cs = 0, cq = 0;                                      // column c's sums over the rows of the window
   const int y1 = R0 + r < rows ? R0 + r : rows;
@@ -144,17 +138,12 @@ extern "C" int crnn_binarize_pages(const void* arena, long arena_bytes, const cr
     return CRNN_ERR_ARG;
   if (P == 0) return CRNN_OK;
   if (!arena || arena_bytes < 1 || !pages || !pages_dev || !out_arena || out_bytes < 1) return CRNN_ERR_ARG;
-  const uintptr_t a0 = (uintptr_t)arena, o0 = (uintptr_t)out_arena;
-  if (a0 < o0 + (uintptr_t)out_bytes && o0 < a0 + (uintptr_t)arena_bytes) return CRNN_ERR_ARG;   // the ranges overlap
+  if (page_ranges_overlap(arena, arena_bytes, out_arena, out_bytes)) return CRNN_ERR_ARG;
   int max_rows = 0, max_cols = 0;
-  for (int i = 0; i < P; ++i) {
-    const crnn_page_item& g = pages[i];
-    if (g.rows < 1 || g.cols < 1 || g.rows > BIN_MAX_DIM || g.cols > BIN_MAX_DIM || g.stride < g.cols || g.page_off < 0) return CRNN_ERR_ARG;
-    const long span = (long)(g.rows - 1) * g.stride + g.cols;
-    if (g.page_off > arena_bytes || span > arena_bytes - g.page_off || g.page_off > out_bytes || span > out_bytes - g.page_off) return CRNN_ERR_ARG;
+  CRNN_TRY(page_check_table(pages, P, CRNN_ERR_ARG, arena_bytes, out_bytes, [&](const crnn_page_item& g) {   // (pages.h; a page above the limit is CRNN_ERR_ARG here)
     if (g.rows > max_rows) max_rows = g.rows;
     if (g.cols > max_cols) max_cols = g.cols;
-  }
+  }));
   if (P > 65535) return CRNN_ERR_UNSUPPORTED;                   // the page is the grid's z
   hipLaunchKernelGGL(bin_sauvola_kernel, dim3(cdiv(max_cols, BIN_STRIP_C), cdiv(max_rows, BIN_BAND_R), P), dim3(BIN_THREADS), 0, stream,
                      (const unsigned char*)arena, arena_bytes, pages_dev, prm->radius, prm->k256, prm->polarity, (unsigned char*)out_arena, out_bytes);

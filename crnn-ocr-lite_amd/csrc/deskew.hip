@@ -1,9 +1,9 @@
-// Page deskew on the device: the skew of uint8 pages (the arena crnn_detect_words reads) by sheared projection profiles, and the pages resampled
+// Page deskew on the device: the skew of uint8 pages (the arena pages.h defines) by sheared projection profiles, and the pages resampled
 // by that angle into an arena of the same layout.  Integer-only (the rules: include/crnn_mi355x.h; the same rules in NumPy:
 // crnn_mi355x/deskew.py) apart from Otsu's fixed-order float64 score, which is the detector's own code (otsu.h).
 //
 // The estimate: five launches behind one memset of the histograms and profiles, one workspace:
-//   dsk_hist_kernel       the page's 256-bin histogram (otsu.h, as det_hist_kernel).
+//   otsu_hist_kernel      the page's 256-bin histogram (otsu.h, the detector's launch).
 //   dsk_threshold_kernel  one workgroup per page: the threshold and polarity (otsu.h, as det_threshold_kernel) and the page's sanitised geometry
 //                         and the offset of its profiles in the workspace (DskPage) -- the later kernels read only that record.
 //   dsk_profile_kernel    grid (groups of DSK_STRIPS 64-column strips, bands of DSK_BAND_R rows, pages).  The ink of a strip is one 64-bit ballot
@@ -20,7 +20,7 @@
 //
 // The rotation: one gather launch, grid (64-column strips, bands of DSK_ROT_R rows, pages); a wavefront writes 64 consecutive bytes of a row
 // and reads, for slopes up to 0.25, from at most 17 source rows.  No atomics.
-#include "common.h"
+#include "pages.h"
 #pragma clang fp contract(off)
 #include "otsu.h"                           // the histogram and the threshold decision, shared with detect.hip
 #include <math.h>
@@ -32,7 +32,6 @@
 #define DSK_PADW (16 * DSK_STRIPS)          // the most that off can differ between two columns of a workgroup: 64 DSK_STRIPS - 1 columns at 0.25
 #define DSK_WORDS (DSK_BAND_R + 2 * DSK_PADW)
 #define DSK_ROT_R 16
-#define DSK_MAX_DIM 4096
 #define DSK_MAX_STEPS 64
 #define DSK_MAX_SLOPE_STEP 1024
 #define DSK_MAX_SLOPE 16384                 // steps * slope_step: 0.25 in units of 2^-16
@@ -50,16 +49,10 @@ struct DskPage {
 static_assert(sizeof(DskPage) == 64, "DskPage is one 64-byte record");
 struct DskTable { int c[2 * DSK_MAX_STEPS + 1], s[2 * DSK_MAX_STEPS + 1]; };   // 65536 (cos, sin) of candidate a at a + steps
 
-static inline size_t dsk_up16(size_t n) { return (n + 15) & ~(size_t)15; }
 // |off| <= (cols / 2 + 1) * 0.25 + 1: the bins of a page are -pad .. rows - 1 + pad
 __host__ __device__ __forceinline__ int dsk_pad(int cols) { return ((((cols >> 1) + 1) * DSK_MAX_SLOPE) >> 16) + 2; }
 // (c - half) * s: |c - half| < 4096 + 64 DSK_STRIPS, |s| <= 2^14: below 2^27
 __device__ __forceinline__ int dsk_off(int c, int half, int s) { return ((c - half) * s + 32768) >> 16; }
-
-__global__ __launch_bounds__(DSK_THREADS) void dsk_hist_kernel(const unsigned char* __restrict__ arena, long arena_bytes,
-                                                               const crnn_page_item* __restrict__ pages, int* __restrict__ hist) {
-  otsu_hist(arena, arena_bytes, pages, hist, DSK_MAX_DIM);
-}
 
 __global__ __launch_bounds__(DSK_THREADS) void dsk_threshold_kernel(const crnn_page_item* __restrict__ pages, const int* __restrict__ hist,
                                                                     DskPage* __restrict__ meta, int threshold, int polarity, int ncand,
@@ -71,12 +64,12 @@ __global__ __launch_bounds__(DSK_THREADS) void dsk_threshold_kernel(const crnn_p
   // this page's place in the workspace: the sums over the pages before it, from the same table the host validated
   long prof = 0;
   for (int q = 0; q < p; ++q) {                                 // q counts up to p
-    const int r = det_clampi(pages[q].rows, 0, DSK_MAX_DIM), c = det_clampi(pages[q].cols, 0, DSK_MAX_DIM);
+    const int r = page_clampi(pages[q].rows, 0, PAGE_MAX_DIM), c = page_clampi(pages[q].cols, 0, PAGE_MAX_DIM);
     prof += (long)ncand * (r + 2 * dsk_pad(c));
   }
   const crnn_page_item pg = pages[p];
-  int rows = det_clampi(pg.rows, 0, DSK_MAX_DIM);
-  const int cols = det_clampi(pg.cols, 0, DSK_MAX_DIM);
+  int rows = page_clampi(pg.rows, 0, PAGE_MAX_DIM);
+  const int cols = page_clampi(pg.cols, 0, PAGE_MAX_DIM);
   const int nbins = rows + 2 * dsk_pad(cols);
   if (cols == 0 || prof + (long)ncand * nbins > total_words) rows = 0;
   DskPage m;
@@ -95,8 +88,8 @@ __global__ __launch_bounds__(DSK_THREADS) void dsk_profile_kernel(const unsigned
   const int C0 = (int)blockIdx.x * 64 * DSK_STRIPS, R0 = (int)blockIdx.y * DSK_BAND_R;
   if (rows < 1 || m.t < 0 || C0 >= cols || R0 >= rows) return;  // (uniform over the workgroup) no ink: the profiles stay 0
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  steps = det_clampi(steps, 0, DSK_MAX_STEPS);
-  slope_step = det_clampi(slope_step, 1, DSK_MAX_SLOPE / (steps > 0 ? steps : 1));
+  steps = page_clampi(steps, 0, DSK_MAX_STEPS);
+  slope_step = page_clampi(slope_step, 1, DSK_MAX_SLOPE / (steps > 0 ? steps : 1));
   for (int i = tid; i < DSK_STRIPS * DSK_WORDS; i += DSK_THREADS) (&W[0][0])[i] = 0;   // i grows by DSK_THREADS
   __syncthreads();
   // 1. ink words: one (row, strip) per wavefront pass, the four wavefronts on 256 consecutive bytes of a row
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(DSK_THREADS) void dsk_profile_kernel(const unsigned
     const int lr = q / DSK_STRIPS, k = q % DSK_STRIPS;
     const int r = R0 + lr, c = C0 + 64 * k + lane;
     bool ink = false;
-    if (r < rows && c < cols) ink = ((det_pixel(arena, arena_bytes, m.off, m.stride, r, c) <= m.t) ? 1 : 0) == m.dark;
+    if (r < rows && c < cols) ink = ((page_pixel(arena, arena_bytes, m.off, m.stride, r, c) <= m.t) ? 1 : 0) == m.dark;
     const unsigned long long M = __ballot(ink);
     if (lane == 0) W[k][DSK_PADW + lr] = M;
   }
@@ -159,7 +152,7 @@ __global__ __launch_bounds__(DSK_THREADS) void dsk_score_kernel(const DskPage* _
 
 __global__ __launch_bounds__(DSK_THREADS) void dsk_pick_kernel(const long long* __restrict__ scores, int steps, int* __restrict__ index) {
   __shared__ long long sc[2 * DSK_MAX_STEPS + 1];
-  steps = det_clampi(steps, 0, DSK_MAX_STEPS);
+  steps = page_clampi(steps, 0, DSK_MAX_STEPS);
   const int ncand = 2 * steps + 1, tid = threadIdx.x;
   if (tid < ncand) sc[tid] = scores[(long)blockIdx.x * ncand + tid];
   __syncthreads();
@@ -179,14 +172,11 @@ __global__ __launch_bounds__(DSK_THREADS) void dsk_rotate_kernel(const unsigned 
                                                                  DskTable tab, int steps, int fill, unsigned char* __restrict__ out,
                                                                  long out_bytes) {
   const crnn_page_item pg = pages[blockIdx.z];
-  const int rows = det_clampi(pg.rows, 0, DSK_MAX_DIM), cols = det_clampi(pg.cols, 0, DSK_MAX_DIM);
+  const int rows = page_clampi(pg.rows, 0, PAGE_MAX_DIM), cols = page_clampi(pg.cols, 0, PAGE_MAX_DIM);
   const int C0 = (int)blockIdx.x * 64, R0 = (int)blockIdx.y * DSK_ROT_R;
   if (C0 >= cols || R0 >= rows) return;                         // (uniform over the workgroup)
-  // The device entry must fit both arenas, as the host's copy of it did; a page whose entry does not is left alone.  Checked once, here: below,
-  // rows and columns are clamped into the page and no load or store needs a check of its own.
-  const long span = (long)(rows - 1) * pg.stride + cols;
-  if (pg.page_off < 0 || pg.stride < cols || pg.page_off > arena_bytes - span || pg.page_off > out_bytes - span) return;   // (uniform)
-  steps = det_clampi(steps, 0, DSK_MAX_STEPS);
+  if (page_outside(pg, rows, cols, arena_bytes, out_bytes)) return;   // (uniform; pages.h: no load or store below needs a check of its own)
+  steps = page_clampi(steps, 0, DSK_MAX_STEPS);
   int a = __builtin_amdgcn_readfirstlane(index[blockIdx.z]);   // (uniform: one page per workgroup)
   if (a < -steps || a > steps) a = 0;
   const int C = tab.c[a + steps], S = tab.s[a + steps];
@@ -199,8 +189,8 @@ __global__ __launch_bounds__(DSK_THREADS) void dsk_rotate_kernel(const unsigned 
     const int dr = 2 * r - (rows - 1);
     const int X = C * dc - S * dr + ((cols - 1) << 16), Y = S * dc + C * dr + ((rows - 1) << 16);
     const int c0 = X >> 17, r0 = Y >> 17, fx = (X >> 9) & 255, fy = (Y >> 9) & 255;
-    const int ra = det_clampi(r0, 0, rows - 1), rb = det_clampi(r0 + 1, 0, rows - 1);
-    const int ca = det_clampi(c0, 0, cols - 1), cb = det_clampi(c0 + 1, 0, cols - 1);
+    const int ra = page_clampi(r0, 0, rows - 1), rb = page_clampi(r0 + 1, 0, rows - 1);
+    const int ca = page_clampi(c0, 0, cols - 1), cb = page_clampi(c0 + 1, 0, cols - 1);
     int p00 = src[(long)ra * pg.stride + ca], p01 = src[(long)ra * pg.stride + cb];
     int p10 = src[(long)rb * pg.stride + ca], p11 = src[(long)rb * pg.stride + cb];
     if (fill >= 0) {                                            // a sample outside the page is `fill`, not the clamped pixel
@@ -223,31 +213,23 @@ static bool dsk_params_ok(const crnn_deskew_params* p) {
          p->slope_step >= 1 && p->slope_step <= DSK_MAX_SLOPE_STEP && p->steps * p->slope_step <= DSK_MAX_SLOPE && p->fill >= -1 && p->fill <= 255;
 }
 
-// the host table's checks: 0, or CRNN_ERR_ARG / CRNN_ERR_UNSUPPORTED; out_bytes < 0: there is no output arena to fit
-static int dsk_totals(const crnn_page_item* pages, int P, int ncand, long arena_bytes, long out_bytes, bool check_arena, DskTotals& t) {
+// the host table's checks (pages.h; arena_bytes / out_bytes < 0: no such arena to fit) and the launches' totals: 0, or CRNN_ERR_ARG / CRNN_ERR_UNSUPPORTED
+static int dsk_totals(const crnn_page_item* pages, int P, int ncand, long arena_bytes, long out_bytes, DskTotals& t) {
   t = DskTotals{0, 0, 0, 0};
-  for (int i = 0; i < P; ++i) {
-    const crnn_page_item& g = pages[i];
-    if (g.rows < 1 || g.cols < 1 || g.stride < g.cols || g.page_off < 0) return CRNN_ERR_ARG;
-    if (g.rows > DSK_MAX_DIM || g.cols > DSK_MAX_DIM) return CRNN_ERR_UNSUPPORTED;
-    const long span = (long)(g.rows - 1) * g.stride + g.cols;
-    if (check_arena && (g.page_off > arena_bytes || span > arena_bytes - g.page_off)) return CRNN_ERR_ARG;
-    if (check_arena && out_bytes >= 0 && (g.page_off > out_bytes || span > out_bytes - g.page_off)) return CRNN_ERR_ARG;
+  return page_check_table(pages, P, CRNN_ERR_UNSUPPORTED, arena_bytes, out_bytes, [&t, ncand](const crnn_page_item& g) {
     t.words += (long)ncand * (g.rows + 2 * dsk_pad(g.cols));
     if (g.rows > t.max_rows) t.max_rows = g.rows;
     if (g.cols > t.max_cols) t.max_cols = g.cols;
     if (g.rows * g.cols > t.max_pix) t.max_pix = g.rows * g.cols;
-  }
-  return 0;
+  });
 }
 
-static inline size_t dsk_hist_bytes(int P) { return (size_t)P * 256 * sizeof(int); }
 static inline size_t dsk_meta_bytes(int P) { return (size_t)P * sizeof(DskPage); }
 
 extern "C" size_t crnn_deskew_workspace_bytes(const crnn_page_item* pages, int P, const crnn_deskew_params* prm) {
   DskTotals t;
-  if (!pages || !prm || P < 1 || P > 65535 || !dsk_params_ok(prm) || dsk_totals(pages, P, 2 * prm->steps + 1, 0, -1, false, t) != 0) return 0;
-  return dsk_hist_bytes(P) + dsk_up16((size_t)t.words * sizeof(int)) + dsk_meta_bytes(P);
+  if (!pages || !prm || P < 1 || P > 65535 || !dsk_params_ok(prm) || dsk_totals(pages, P, 2 * prm->steps + 1, -1, -1, t) != 0) return 0;
+  return otsu_hist_bytes(P) + page_up16((size_t)t.words * sizeof(int)) + dsk_meta_bytes(P);
 }
 
 extern "C" int crnn_deskew_estimate(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int P,
@@ -258,17 +240,17 @@ extern "C" int crnn_deskew_estimate(const void* arena, long arena_bytes, const c
   if (!arena || arena_bytes < 1 || !pages || !pages_dev || !index || !scores || !ws) return CRNN_ERR_ARG;
   const int ncand = 2 * prm->steps + 1;
   DskTotals t;
-  CRNN_TRY(dsk_totals(pages, P, ncand, arena_bytes, -1, true, t));
+  CRNN_TRY(dsk_totals(pages, P, ncand, arena_bytes, -1, t));
   if (P > 65535) return CRNN_ERR_UNSUPPORTED;                   // the page is the grid's y or z
   if (ws_bytes < crnn_deskew_workspace_bytes(pages, P, prm) || ((uintptr_t)ws & 15)) return CRNN_ERR_ARG;
   unsigned char* w = (unsigned char*)ws;
-  int* hist = (int*)w;                      w += dsk_hist_bytes(P);
-  int* prof = (int*)w;                      w += dsk_up16((size_t)t.words * sizeof(int));
+  int* hist = (int*)w;                      w += otsu_hist_bytes(P);
+  int* prof = (int*)w;                      w += page_up16((size_t)t.words * sizeof(int));
   DskPage* meta = (DskPage*)w;
   const unsigned char* a = (const unsigned char*)arena;
-  const hipError_t e = hipMemsetAsync(hist, 0, dsk_hist_bytes(P) + dsk_up16((size_t)t.words * sizeof(int)), stream);   // histograms and profiles
+  const hipError_t e = hipMemsetAsync(hist, 0, otsu_hist_bytes(P) + page_up16((size_t)t.words * sizeof(int)), stream);   // histograms and profiles
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(dsk_hist_kernel, dim3(cdiv(t.max_pix, OTSU_HIST_CHUNK), P), dim3(DSK_THREADS), 0, stream, a, arena_bytes, pages_dev, hist);
+  hipLaunchKernelGGL(otsu_hist_kernel, dim3(cdiv(t.max_pix, OTSU_HIST_CHUNK), P), dim3(DSK_THREADS), 0, stream, a, arena_bytes, pages_dev, hist);
   CRNN_LAUNCH_CHECK();
   hipLaunchKernelGGL(dsk_threshold_kernel, dim3(P), dim3(DSK_THREADS), 0, stream, pages_dev, (const int*)hist, meta, prm->threshold,
                      prm->polarity, ncand, t.words);
@@ -288,10 +270,9 @@ extern "C" int crnn_rotate_pages(const void* arena, long arena_bytes, const crnn
   if (P < 0 || !prm || !dsk_params_ok(prm)) return CRNN_ERR_ARG;
   if (P == 0) return CRNN_OK;
   if (!arena || arena_bytes < 1 || !pages || !pages_dev || !index_dev || !out_arena || out_bytes < 1) return CRNN_ERR_ARG;
-  const uintptr_t a0 = (uintptr_t)arena, o0 = (uintptr_t)out_arena;
-  if (a0 < o0 + (uintptr_t)out_bytes && o0 < a0 + (uintptr_t)arena_bytes) return CRNN_ERR_ARG;   // the ranges overlap
+  if (page_ranges_overlap(arena, arena_bytes, out_arena, out_bytes)) return CRNN_ERR_ARG;
   DskTotals t;
-  CRNN_TRY(dsk_totals(pages, P, 0, arena_bytes, out_bytes, true, t));
+  CRNN_TRY(dsk_totals(pages, P, 0, arena_bytes, out_bytes, t));
   if (P > 65535) return CRNN_ERR_UNSUPPORTED;                   // the page is the grid's z
   // 65536 (cos, sin) of every candidate's angle, in IEEE double: sqrt and / are correctly rounded, rint rounds to nearest (ties to even)
   DskTable tab;

@@ -1,9 +1,9 @@
-// Word detection: page images (uint8, the arena crnn_ingest_crops reads) -> word boxes, on the device.  Classical, deterministic, integer-only
+// Word detection: page images (uint8, the arena pages.h defines) -> word boxes, on the device.  Classical, deterministic, integer-only
 // except for Otsu's fixed-order float64 score: a global threshold, run-length smearing so that the letters of a word touch, 8-connected
 // component labelling, box extraction with a size filter (the rule: include/crnn_mi355x.h; the same rule in NumPy: crnn_mi355x/detect.py).
 //
 // Seven launches behind one memset of the histograms, one workspace:
-//   det_hist_kernel       grid (chunks of 64 Ki pixels, P): the page's 256-bin histogram, privatised in LDS, non-empty bins added to hist[p].
+//   otsu_hist_kernel      grid (chunks of 64 Ki pixels, P): the page's 256-bin histogram, privatised in LDS, non-empty bins added to hist[p].
 //   det_threshold_kernel  one workgroup per page: Otsu (or the given threshold), the polarity, and the page's sanitised geometry and offsets into
 //                         the workspace (DetPage) -- the later kernels read only that record, never the caller's table.
 //   det_tile_kernel       one workgroup per DET_TILE_R x DET_TILE_C tile.  A wavefront's ballot over 64 pixels is one 64-bit row word (score.hip);
@@ -25,7 +25,7 @@
 //                         workgroup of slot row 0 also writes info and the -1 tail.
 // Roots are minimum row-major indices, so nothing depends on arrival order: two calls agree bit for bit.  No workgroup waits for another inside a
 // launch; everything one workgroup must see from another crosses a kernel boundary.
-#include "common.h"
+#include "pages.h"
 #pragma clang fp contract(off)
 #include "otsu.h"                           // the histogram and the threshold decision, shared with deskew.hip
 
@@ -34,10 +34,8 @@
 #define DET_TILE_R CRNN_DETECT_TILE_R
 #define DET_TILE_C CRNN_DETECT_TILE_C       // 64: one ballot word
 static_assert(DET_TILE_C == 64 && DET_TILE_R % 2 == 0 && DET_TILE_R % (DET_THREADS / 64) == 0, "the tile is 64 columns wide: one ballot word per row");
-#define DET_MAX_DIM 4096
 #define DET_MAX_GAP_X 64                    // <= DET_TILE_C: one halo word either side
 #define DET_MAX_GAP_Y 16
-#define DET_HIST_CHUNK OTSU_HIST_CHUNK
 static_assert(DET_THREADS == OTSU_THREADS, "otsu.h's workgroups are the detector's");
 #define DET_REC 6                           // r0 r1 c0 c1 ink root
 #define DET_TILE_SLOTS ((DET_TILE_R / 2) * (DET_TILE_C / 2))
@@ -51,14 +49,8 @@ struct DetPage {
 };
 static_assert(sizeof(DetPage) == 64, "DetPage is one 64-byte record");
 
-static inline size_t det_up16(size_t n) { return (n + 15) & ~(size_t)15; }
 __device__ __forceinline__ int det_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int det_lds_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-__global__ __launch_bounds__(DET_THREADS) void det_hist_kernel(const unsigned char* __restrict__ arena, long arena_bytes,
-                                                               const crnn_page_item* __restrict__ pages, int* __restrict__ hist) {
-  otsu_hist(arena, arena_bytes, pages, hist, DET_MAX_DIM);
-}
 
 __global__ __launch_bounds__(DET_THREADS) void det_threshold_kernel(const crnn_page_item* __restrict__ pages, const int* __restrict__ hist,
                                                                     DetPage* __restrict__ meta, int threshold, int polarity, long total_pix,
@@ -70,13 +62,13 @@ __global__ __launch_bounds__(DET_THREADS) void det_threshold_kernel(const crnn_p
   // this page's place in the workspace: the sums over the pages before it, from the same table the host validated
   long pix = 0, slot = 0, row = 0;
   for (int q = 0; q < p; ++q) {                                 // q counts up to p
-    const int r = det_clampi(pages[q].rows, 0, DET_MAX_DIM), c = det_clampi(pages[q].cols, 0, DET_MAX_DIM);
+    const int r = page_clampi(pages[q].rows, 0, PAGE_MAX_DIM), c = page_clampi(pages[q].cols, 0, PAGE_MAX_DIM);
     pix += (long)r * c;
     slot += (long)((r + 1) >> 1) * ((c + 1) >> 1);
     row += 2 * ((r + 1) >> 1);
   }
   const crnn_page_item pg = pages[p];
-  int rows = det_clampi(pg.rows, 0, DET_MAX_DIM), cols = det_clampi(pg.cols, 0, DET_MAX_DIM);
+  int rows = page_clampi(pg.rows, 0, PAGE_MAX_DIM), cols = page_clampi(pg.cols, 0, PAGE_MAX_DIM);
   const long srows = (rows + 1) >> 1, scols = (cols + 1) >> 1;
   if (cols == 0 || pix + (long)rows * cols > total_pix || slot + srows * scols > total_slots || row + 2 * srows > total_rows) rows = 0;
   DetPage m;
@@ -120,8 +112,8 @@ __global__ __launch_bounds__(DET_THREADS) void det_tile_kernel(const unsigned ch
   if ((int)blockIdx.x >= tiles) return;
   const int R0 = ((int)blockIdx.x / tiles_c) * DET_TILE_R, C0 = ((int)blockIdx.x % tiles_c) * DET_TILE_C;
   const int tid = threadIdx.x, b = tid & 63, wave = tid >> 6;
-  gap_x = det_clampi(gap_x, 0, DET_MAX_GAP_X);
-  gap_y = det_clampi(gap_y, 0, DET_MAX_GAP_Y);
+  gap_x = page_clampi(gap_x, 0, DET_MAX_GAP_X);
+  gap_y = page_clampi(gap_y, 0, DET_MAX_GAP_Y);
   const unsigned long long below = (1ull << b) - 1;             // the bits of the columns left of this lane's
 
   for (int i = tid; i < DET_TILE_SLOTS; i += DET_THREADS) {     // i grows by DET_THREADS
@@ -135,10 +127,10 @@ __global__ __launch_bounds__(DET_THREADS) void det_tile_kernel(const unsigned ch
     bool ink0 = false, ink1 = false, ink2 = false;
     if (row_in) {
       const int c = C0 + b;
-      if (c < cols) ink1 = ((det_pixel(arena, arena_bytes, m.off, m.stride, r, c) <= m.t) ? 1 : 0) == m.dark;
+      if (c < cols) ink1 = ((page_pixel(arena, arena_bytes, m.off, m.stride, r, c) <= m.t) ? 1 : 0) == m.dark;
       if (gap_x > 0) {                                          // the halo words either side
-        if (c - 64 >= 0) ink0 = ((det_pixel(arena, arena_bytes, m.off, m.stride, r, c - 64) <= m.t) ? 1 : 0) == m.dark;
-        if (c + 64 < cols) ink2 = ((det_pixel(arena, arena_bytes, m.off, m.stride, r, c + 64) <= m.t) ? 1 : 0) == m.dark;
+        if (c - 64 >= 0) ink0 = ((page_pixel(arena, arena_bytes, m.off, m.stride, r, c - 64) <= m.t) ? 1 : 0) == m.dark;
+        if (c + 64 < cols) ink2 = ((page_pixel(arena, arena_bytes, m.off, m.stride, r, c + 64) <= m.t) ? 1 : 0) == m.dark;
       }
     }
     const unsigned long long M0 = __ballot(ink0), M1 = __ballot(ink1), M2 = __ballot(ink2);
@@ -396,14 +388,10 @@ __global__ __launch_bounds__(DET_THREADS) void det_emit_kernel(const DetPage* __
 // ---- entry points --------------------------------------------------------------------------------------------------------------------------
 struct DetTotals { long pix, slots, rows; int max_pix, max_tiles, max_border, max_slots, max_srows; };
 
-// the host table's checks: 0, or CRNN_ERR_ARG / CRNN_ERR_UNSUPPORTED
-static int det_totals(const crnn_page_item* pages, int P, long arena_bytes, bool check_arena, DetTotals& t) {
+// the host table's checks (pages.h; arena_bytes < 0: no arena to fit) and the launch sequence's totals: 0, or CRNN_ERR_ARG / CRNN_ERR_UNSUPPORTED
+static int det_totals(const crnn_page_item* pages, int P, long arena_bytes, DetTotals& t) {
   t = DetTotals{0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < P; ++i) {
-    const crnn_page_item& g = pages[i];
-    if (g.rows < 1 || g.cols < 1 || g.stride < g.cols || g.page_off < 0) return CRNN_ERR_ARG;
-    if (g.rows > DET_MAX_DIM || g.cols > DET_MAX_DIM) return CRNN_ERR_UNSUPPORTED;
-    if (check_arena && (g.page_off > arena_bytes || (long)(g.rows - 1) * g.stride + g.cols > arena_bytes - g.page_off)) return CRNN_ERR_ARG;
+  CRNN_TRY(page_check_table(pages, P, CRNN_ERR_UNSUPPORTED, arena_bytes, -1, [&t](const crnn_page_item& g) {
     const int sr = (g.rows + 1) >> 1, sc = (g.cols + 1) >> 1;
     const int pix = g.rows * g.cols;
     t.pix += pix; t.slots += (long)sr * sc; t.rows += 2 * sr;
@@ -414,7 +402,7 @@ static int det_totals(const crnn_page_item* pages, int P, long arena_bytes, bool
     if (border > t.max_border) t.max_border = border;
     if (sr * sc > t.max_slots) t.max_slots = sr * sc;
     if (sr > t.max_srows) t.max_srows = sr;
-  }
+  }));
   if (t.pix > (1L << 31)) return CRNN_ERR_UNSUPPORTED;
   return 0;
 }
@@ -425,14 +413,13 @@ static bool det_params_ok(const crnn_detect_params* p) {
          p->cap >= 1;
 }
 
-static inline size_t det_hist_bytes(int P) { return (size_t)P * 256 * sizeof(int); }
 static inline size_t det_meta_bytes(int P) { return (size_t)P * sizeof(DetPage); }
 
 extern "C" size_t crnn_detect_workspace_bytes(const crnn_page_item* pages, int P, const crnn_detect_params* prm) {
   DetTotals t;
-  if (!pages || !prm || P < 1 || P > 65535 || !det_params_ok(prm) || det_totals(pages, P, 0, false, t) != 0) return 0;
-  return det_hist_bytes(P) + det_meta_bytes(P) + det_up16((size_t)t.pix * sizeof(int)) + det_up16((size_t)t.slots * DET_REC * sizeof(int)) +
-         det_up16((size_t)t.rows * sizeof(int));
+  if (!pages || !prm || P < 1 || P > 65535 || !det_params_ok(prm) || det_totals(pages, P, -1, t) != 0) return 0;
+  return otsu_hist_bytes(P) + det_meta_bytes(P) + page_up16((size_t)t.pix * sizeof(int)) + page_up16((size_t)t.slots * DET_REC * sizeof(int)) +
+         page_up16((size_t)t.rows * sizeof(int));
 }
 
 extern "C" int crnn_detect_words(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int P,
@@ -441,19 +428,19 @@ extern "C" int crnn_detect_words(const void* arena, long arena_bytes, const crnn
   if (P == 0) return CRNN_OK;
   if (!arena || arena_bytes < 1 || !pages || !pages_dev || !rects || !info || !ws) return CRNN_ERR_ARG;
   DetTotals t;
-  CRNN_TRY(det_totals(pages, P, arena_bytes, true, t));
+  CRNN_TRY(det_totals(pages, P, arena_bytes, t));
   if (P > 65535) return CRNN_ERR_UNSUPPORTED;                   // the page is the grid's y
   if (ws_bytes < crnn_detect_workspace_bytes(pages, P, prm) || ((uintptr_t)ws & 15)) return CRNN_ERR_ARG;
   unsigned char* w = (unsigned char*)ws;
-  int* hist = (int*)w;                      w += det_hist_bytes(P);
+  int* hist = (int*)w;                      w += otsu_hist_bytes(P);
   DetPage* meta = (DetPage*)w;              w += det_meta_bytes(P);
-  int* labels = (int*)w;                    w += det_up16((size_t)t.pix * sizeof(int));
-  int* recs = (int*)w;                      w += det_up16((size_t)t.slots * DET_REC * sizeof(int));
+  int* labels = (int*)w;                    w += page_up16((size_t)t.pix * sizeof(int));
+  int* recs = (int*)w;                      w += page_up16((size_t)t.slots * DET_REC * sizeof(int));
   int* rowcnt = (int*)w;
   const unsigned char* a = (const unsigned char*)arena;
-  const hipError_t e = hipMemsetAsync(hist, 0, det_hist_bytes(P), stream);
+  const hipError_t e = hipMemsetAsync(hist, 0, otsu_hist_bytes(P), stream);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(det_hist_kernel, dim3(cdiv(t.max_pix, DET_HIST_CHUNK), P), dim3(DET_THREADS), 0, stream, a, arena_bytes, pages_dev, hist);
+  hipLaunchKernelGGL(otsu_hist_kernel, dim3(cdiv(t.max_pix, OTSU_HIST_CHUNK), P), dim3(DET_THREADS), 0, stream, a, arena_bytes, pages_dev, hist);
   CRNN_LAUNCH_CHECK();
   hipLaunchKernelGGL(det_threshold_kernel, dim3(P), dim3(DET_THREADS), 0, stream, pages_dev, (const int*)hist, meta, prm->threshold, prm->polarity,
                      t.pix, t.slots, t.rows);

@@ -1,11 +1,11 @@
-// Word-crop ingest: page images (uint8, one arena) + a box table -> the normalised (B, imgh, imgw, 1) fp32 batch the forward reads.
+// Word-crop ingest: page images (uint8, one arena: pages.h) + a box table -> the normalised (B, imgh, imgw, 1) fp32 batch the forward reads.
 // One workgroup builds one output image; one launch per batch.
 //
 // Restates crnn_mi355x/data.py open_img (rotate, modal fill value, optional 1.5x up-scale rounded to uint8, modal-value padding, inversion
 // of bright-background images, bilinear squash to (imgh, imgw)) followed by norm(), bit for bit: resize_linear's float64 arithmetic is kept
 // operation by operation, so nothing here may be contracted into fused multiply-adds (the pragma below; hipcc contracts by default).  The
 // random choices of the padding are NOT made here: the host draws them (ingest.plan_crop) and passes the content offset / padded size.
-#include "common.h"
+#include "pages.h"
 #pragma clang fp contract(off)
 
 #define INGEST_THREADS 256
@@ -38,11 +38,7 @@ struct IngestPage {
   int rows, cols, stride, r0, c0, hc;
   // the rotated crop rot(i, j) = page[r0 + hc - 1 - j, c0 + i]; every read stays inside the page and inside the arena whatever the table holds
   __device__ __forceinline__ int at(int r, int c) const {
-    r = r < 0 ? 0 : (r > rows - 1 ? rows - 1 : r);
-    c = c < 0 ? 0 : (c > cols - 1 ? cols - 1 : c);
-    long a = off + (long)r * stride + c;
-    a = a < 0 ? 0 : (a > arena_bytes - 1 ? arena_bytes - 1 : a);
-    return arena[a];
+    return page_pixel(arena, arena_bytes, off, stride, page_clampi(r, 0, rows - 1), page_clampi(c, 0, cols - 1));
   }
   __device__ __forceinline__ int rot(int i, int j) const { return at(r0 + hc - 1 - j, c0 + i); }
 };
@@ -139,8 +135,7 @@ extern "C" int crnn_ingest_crops(const void* arena, long arena_bytes, const crnn
   if (up_cap > INGEST_LDS_BUDGET) return CRNN_ERR_UNSUPPORTED;
   for (int i = 0; i < n; ++i) {
     const crnn_crop_item& t = items[i];
-    if (t.rows < 1 || t.cols < 1 || t.stride < t.cols || t.page_off < 0 || t.page_off > arena_bytes) return CRNN_ERR_ARG;
-    if ((long)(t.rows - 1) * t.stride + t.cols > arena_bytes - t.page_off) return CRNN_ERR_ARG;           // page extent outside the arena
+    CRNN_TRY(page_check(t.page_off, t.rows, t.cols, t.stride, 0, arena_bytes, -1));                       // (pages.h; no size limit here)
     if (t.r0 < 0 || t.r0 >= t.r1 || t.r1 > t.rows || t.c0 < 0 || t.c0 >= t.c1 || t.c1 > t.cols) return CRNN_ERR_ARG;   // empty box / outside its page
     const int hc = t.r1 - t.r0, wc = t.c1 - t.c0;
     const bool small = wc <= imgh / 2 && hc <= imgw / 2;

@@ -1,30 +1,23 @@
-// What is ink on a page, shared by the word detector (detect.hip) and the skew estimate (deskew.hip): the clamped pixel read, the page's
-// 256-bin histogram and the threshold / polarity decision of the rule in include/crnn_mi355x.h (crnn_detect_words: THRESHOLD, POLARITY).
-// One definition, so that the two translation units cannot come to disagree about a page's ink.
+// What is ink on a page, shared by the word detector (detect.hip) and the skew estimate (deskew.hip): the page's 256-bin histogram and the
+// threshold / polarity decision of the rule in include/crnn_mi355x.h (crnn_detect_words: THRESHOLD, POLARITY).  One definition, so that the
+// two translation units cannot come to disagree about a page's ink.  The arena the pages lie in is pages.h's.
 #pragma once
-#include "common.h"
+#include "pages.h"
 #pragma clang fp contract(off)              // Otsu's score is four float64 operations in a fixed order
 
 #define OTSU_THREADS 256                    // one thread per histogram bin
 #define OTSU_HIST_CHUNK 65536               // pixels per workgroup of the histogram launch
 
-__host__ __device__ __forceinline__ int det_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+static inline size_t otsu_hist_bytes(int P) { return (size_t)P * 256 * sizeof(int); }
 
-// the page's pixel, every read inside the page and inside the arena whatever the table holds
-__device__ __forceinline__ int det_pixel(const unsigned char* arena, long arena_bytes, long off, int stride, int r, int c) {
-  long a = off + (long)r * stride + c;
-  a = a < 0 ? 0 : (a > arena_bytes - 1 ? arena_bytes - 1 : a);
-  return arena[a];
-}
-
-// The body of a histogram kernel, grid (chunks of OTSU_HIST_CHUNK pixels, P), OTSU_THREADS threads: the chunk's histogram, privatised in LDS,
-// non-empty bins added to hist[p] (integer atomics: any order gives the same sums).
-__device__ __forceinline__ void otsu_hist(const unsigned char* __restrict__ arena, long arena_bytes, const crnn_page_item* __restrict__ pages,
-                                          int* __restrict__ hist, int max_dim) {
+// The histogram launch, grid (chunks of OTSU_HIST_CHUNK pixels, P), OTSU_THREADS threads: the chunk's histogram, privatised in LDS, non-empty
+// bins added to hist[p] (integer atomics: any order gives the same sums).  static: each translation unit that includes this launches its own.
+static __global__ __launch_bounds__(OTSU_THREADS) void otsu_hist_kernel(const unsigned char* __restrict__ arena, long arena_bytes,
+                                                                        const crnn_page_item* __restrict__ pages, int* __restrict__ hist) {
   __shared__ int bins[256];
   const int p = blockIdx.y, tid = threadIdx.x;
   const crnn_page_item pg = pages[p];
-  const int rows = det_clampi(pg.rows, 0, max_dim), cols = det_clampi(pg.cols, 0, max_dim);
+  const int rows = page_clampi(pg.rows, 0, PAGE_MAX_DIM), cols = page_clampi(pg.cols, 0, PAGE_MAX_DIM);
   const long n = (long)rows * cols, lo = (long)blockIdx.x * OTSU_HIST_CHUNK;
   if (lo >= n) return;
   const long hi = lo + OTSU_HIST_CHUNK < n ? lo + OTSU_HIST_CHUNK : n;
@@ -32,7 +25,7 @@ __device__ __forceinline__ void otsu_hist(const unsigned char* __restrict__ aren
   __syncthreads();
   for (long i = lo + tid; i < hi; i += OTSU_THREADS) {         // i grows by OTSU_THREADS up to hi
     const int r = (int)(i / cols), c = (int)(i - (long)r * cols);
-    atomicAdd(&bins[det_pixel(arena, arena_bytes, pg.page_off, pg.stride, r, c)], 1);
+    atomicAdd(&bins[page_pixel(arena, arena_bytes, pg.page_off, pg.stride, r, c)], 1);
   }
   __syncthreads();
   if (bins[tid]) atomicAdd(&hist[(long)p * 256 + tid], bins[tid]);
@@ -80,7 +73,7 @@ __device__ __forceinline__ void otsu_decide(const int* __restrict__ h256, int th
   if (tid != 0) return;
   int t = threshold;
   if (threshold < 0) t = sc[0] >= 0.0 ? st[0] : -1;
-  t = det_clampi(t, -1, 254);
+  t = page_clampi(t, -1, 254);
   int dark = polarity != 2;
   if (t >= 0 && polarity == 0) dark = sw[cur][t] <= N - sw[cur][t];
   t_out = t;

@@ -317,7 +317,8 @@ int crnn_ingest_crops(const void* arena, long arena_bytes, const crnn_crop_item*
                       const float* table, float* out, void* out_u8, crnn_stream_t stream);
 
 /* ---- word detection: page images -> the word boxes crnn_ingest_crops takes (csrc/detect.hip; the same rule in NumPy: crnn_mi355x.detect) ---- */
-/* A page: a row-major uint8 image at byte `page_off` of the arena, 1 <= rows, cols <= 4096 -- the page fields of crnn_crop_item. */
+/* A page: a row-major uint8 image at byte `page_off` of the arena, 1 <= rows, cols <= 4096 -- the page fields of crnn_crop_item.  The arena and
+ * the checks of a page table are defined once, in csrc/pages.h for the library and in crnn_mi355x/pages.py for Python. */
 typedef struct { long page_off; int rows, cols, stride; } crnn_page_item;
 /* threshold 0..254, or -1 for Otsu per page; polarity 0 auto / 1 dark ink / 2 bright ink; 0 <= gap_x <= 64, 0 <= gap_y <= 16; the filter's
  * bounds >= 0 (max_w, max_h: 0 = no upper bound); cap >= 1 rows of output per page. */

@@ -23,14 +23,14 @@ ROOFLINE = 8e12
 def main():
     import torch
     import utils as U
-    from crnn_mi355x import binarize as B, data, detect as D, ingest as I, native
+    from crnn_mi355x import binarize as B, data, detect as D, native, pages as PG
     from ingest_bench import make_inputs
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
     pnames, _, _ = make_inputs(tempfile.mkdtemp())
     pages = [data.read_img(n) for n in pnames]
     lib, P = native.lib(), len(pages)
     arena = U.DeviceIngest((100, 32, 1)).upload(pages)
-    table = D.page_table(arena.pages, arena.offsets)
+    table = PG.page_table(arena.pages, arena.offsets)
     table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
     host = table.ctypes.data_as(ctypes.c_void_p)
     out = torch.zeros(arena.nbytes, dtype=torch.uint8, device="cuda")
@@ -79,7 +79,7 @@ def main():
     same, host_s = {}, None
     for r in RADII:
         t = time.time()
-        want, _ = I.pack_arena([B.sauvola_host(pg, r, K256, 1) for pg in (pages if r == 15 else pages[:2])])
+        want, _ = PG.pack_arena([B.sauvola_host(pg, r, K256, 1) for pg in (pages if r == 15 else pages[:2])])
         if r == 15:
             host_s = time.time() - t
         same[r] = np.array_equal(device[r][:want.size], want)

@@ -45,12 +45,12 @@ def make_pages():
 def main():
     import torch
     import utils as U
-    from crnn_mi355x import binarize as B, deskew as K, detect as D, ingest as I, native
+    from crnn_mi355x import binarize as B, deskew as K, detect as D, native, pages as PG
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
     pages = [K.rotate_host(pg, -a) for pg, a in zip(make_pages(), SKEWS)]   # rotating by -a leaves a page whose lines run at slope a / 256
     lib, P = native.lib(), len(pages)
     arena = U.DeviceIngest((100, 32, 1)).upload(pages)
-    table = D.page_table(arena.pages, arena.offsets)
+    table = PG.page_table(arena.pages, arena.offsets)
     table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
     host = table.ctypes.data_as(ctypes.c_void_p)
     out = torch.zeros(arena.nbytes, dtype=torch.uint8, device="cuda")
@@ -110,7 +110,7 @@ def main():
     want = [K.estimate_skew_host(pg) for pg in pages]
     host_est = time.time() - t
     t = time.time()
-    want_flat, _ = I.pack_arena([K.rotate_host(pg, a) for pg, (a, _) in zip(pages, want)])
+    want_flat, _ = PG.pack_arena([K.rotate_host(pg, a) for pg, (a, _) in zip(pages, want)])
     host_rot = time.time() - t
     same = (found.tolist() == [a for a, _ in want], all(np.array_equal(dev_scores[k], s) for k, (_, s) in enumerate(want)),
             np.array_equal(flat[:want_flat.size], want_flat))

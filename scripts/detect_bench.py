@@ -23,7 +23,7 @@ ROOFLINE = 8e12
 def main():
     import torch
     import utils as U
-    from crnn_mi355x import data, detect as D, ingest as I, native
+    from crnn_mi355x import data, detect as D, ingest as I, native, pages as PG
     from ingest_bench import make_inputs
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
     pnames, _, _ = make_inputs(tempfile.mkdtemp())
@@ -36,7 +36,7 @@ def main():
     n_boxes = sum(len(b) for b in boxes)
 
     # (a) the raw entry point, buffers allocated once
-    table = D.page_table(arena.pages, arena.offsets)
+    table = PG.page_table(arena.pages, arena.offsets)
     table_dev = torch.from_numpy(table.view(np.uint8)).cuda()
     prm, P, cap = det._prm, len(pages), det.params["cap"]
     host = table.ctypes.data_as(ctypes.c_void_p)
@@ -71,7 +71,7 @@ def main():
                 call()
             torch.cuda.synchronize()
         rows = [(e.key, getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0), e.count) for e in prof.key_averages()]
-        rows = [(k, t / c) for k, t, c in rows if "det_" in k and c]
+        rows = [(k, t / c) for k, t, c in rows if ("det_" in k or "otsu_" in k) and c]
         if rows:
             total = sum(t for _, t in rows)
             shares = [(k.split("(")[0], t, t / total) for k, t in sorted(rows, key=lambda r: -r[1])]

@@ -68,11 +68,11 @@ def _rate(gen, seconds=4.0, sync=None):
 def step_kernel(pnames, bboxs, fnames):
     import ctypes
     import torch
-    from crnn_mi355x import data as D, ingest as I, native
+    from crnn_mi355x import data as D, ingest as I, native, pages as PG
     out = {}
     for label, pages, rects, index in _decoded(pnames, bboxs, fnames):
         plans = I.plan_crops(rects[:, 1] - rects[:, 0], rects[:, 3] - rects[:, 2], IMG_SIZE)
-        arena, offs = I.pack_arena(pages)
+        arena, offs = PG.pack_arena(pages)
         tab = I.build_table(pages, offs, index, rects, plans, IMG_SIZE)
         d_arena, d_tab = torch.from_numpy(arena).cuda(), torch.from_numpy(tab.view(np.uint8).copy()).cuda()
         table = torch.from_numpy(I.norm_table()).cuda()

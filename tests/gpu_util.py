@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from crnn_mi355x import native
+from crnn_mi355x.pages import PAGE_DTYPE
 
 
 def L():
@@ -64,3 +65,20 @@ def gemm(mode, A, B, M, N, K, lda, ldb, ldc, bias=None, act=0, acc=0, perm=0, C=
     ok(L().crnn_gemm_f32(mode, P(A), P(B), P(Cd), M, N, K, lda, ldb, ldc, P(bias), act, acc, perm, P(scr),
                          (scratch_mb * 1024 * 1024) if scratch_mb else 0, S()))
     return Cd
+
+
+def sentinel_arena(pages, strides=None):
+    """Pages back to back on 16-byte boundaries, page k with row stride strides[k] (the padding bytes hold 0x5a) -> (arena, table, inside):
+    the crnn_page_item table, and `inside` marks the bytes of the pages' rows x cols."""
+    strides = strides or [pg.shape[1] for pg in pages]
+    table, parts, marks, pos = np.zeros(len(pages), PAGE_DTYPE), [], [], 0
+    for k, (pg, st) in enumerate(zip(pages, strides)):
+        buf, mark = np.full((pg.shape[0], st), 0x5a, np.uint8), np.zeros((pg.shape[0], st), bool)
+        buf[:, :pg.shape[1]] = pg
+        mark[:, :pg.shape[1]] = True
+        nbytes = -(-buf.size // 16) * 16
+        parts.append(np.concatenate([buf.ravel(), np.full(nbytes - buf.size, 0x5a, np.uint8)]))
+        marks.append(np.concatenate([mark.ravel(), np.zeros(nbytes - buf.size, bool)]))
+        table[k] = (pos, pg.shape[0], pg.shape[1], st)
+        pos += nbytes
+    return np.concatenate(parts), table, np.concatenate(marks)

@@ -12,8 +12,8 @@ import torch
 
 import utils as U
 from crnn_mi355x import binarize as B, detect as D
-from crnn_mi355x.ingest import pack_arena
-from gpu_util import L, P, S, host
+from crnn_mi355x.pages import pack_arena
+from gpu_util import L, P, S, host, sentinel_arena as _arena
 import binarize_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -21,23 +21,6 @@ pytestmark = pytest.mark.gpu
 S_C, B_R = B.STRIP_C, B.BAND_R
 SENTINELS = (0x33, 0xc4)                                     # neither 0 nor 255
 GUARD = 256
-
-
-def _arena(pages, strides=None):
-    """Pages back to back on 16-byte boundaries, page k with row stride strides[k] (the padding bytes hold 0x5a) -> (arena, table, inside):
-    `inside` marks the bytes of the pages' rows x cols."""
-    strides = strides or [pg.shape[1] for pg in pages]
-    table, parts, marks, pos = np.zeros(len(pages), D.PAGE_DTYPE), [], [], 0
-    for k, (pg, st) in enumerate(zip(pages, strides)):
-        buf, mark = np.full((pg.shape[0], st), 0x5a, np.uint8), np.zeros((pg.shape[0], st), bool)
-        buf[:, :pg.shape[1]] = pg
-        mark[:, :pg.shape[1]] = True
-        nbytes = -(-buf.size // 16) * 16
-        parts.append(np.concatenate([buf.ravel(), np.full(nbytes - buf.size, 0x5a, np.uint8)]))
-        marks.append(np.concatenate([mark.ravel(), np.zeros(nbytes - buf.size, bool)]))
-        table[k] = (pos, pg.shape[0], pg.shape[1], st)
-        pos += nbytes
-    return np.concatenate(parts), table, np.concatenate(marks)
 
 
 def _call(arena_dev, arena_bytes, table, table_dev, n, prm, out, out_bytes, null=None):

@@ -13,8 +13,8 @@ import torch
 
 import utils as U
 from crnn_mi355x import deskew as K, detect as D
-from crnn_mi355x.ingest import pack_arena
-from gpu_util import L, P, S, host
+from crnn_mi355x.pages import pack_arena
+from gpu_util import L, P, S, host, sentinel_arena as _arena
 import deskew_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -22,23 +22,6 @@ pytestmark = pytest.mark.gpu
 GROUP_C, BAND_R = 64 * K.STRIPS, K.BAND_R
 SENTINELS = (0x33, 0xc4)
 GUARD = 256
-
-
-def _arena(pages, strides=None):
-    """Pages back to back on 16-byte boundaries, page k with row stride strides[k] (the padding bytes hold 0x5a) -> (arena, table, inside):
-    `inside` marks the bytes of the pages' rows x cols."""
-    strides = strides or [pg.shape[1] for pg in pages]
-    table, parts, marks, pos = np.zeros(len(pages), D.PAGE_DTYPE), [], [], 0
-    for k, (pg, st) in enumerate(zip(pages, strides)):
-        buf, mark = np.full((pg.shape[0], st), 0x5a, np.uint8), np.zeros((pg.shape[0], st), bool)
-        buf[:, :pg.shape[1]] = pg
-        mark[:, :pg.shape[1]] = True
-        nbytes = -(-buf.size // 16) * 16
-        parts.append(np.concatenate([buf.ravel(), np.full(nbytes - buf.size, 0x5a, np.uint8)]))
-        marks.append(np.concatenate([mark.ravel(), np.zeros(nbytes - buf.size, bool)]))
-        table[k] = (pos, pg.shape[0], pg.shape[1], st)
-        pos += nbytes
-    return np.concatenate(parts), table, np.concatenate(marks)
 
 
 def _prm(**kw):
@@ -351,9 +334,15 @@ def test_detector_and_ingest_read_the_deskewed_arena():
     flat_host = [K.deskew_host(pg, adaptive=adaptive) for pg in (page, other)]
     assert host(flat.index).tolist() == [a for _, a in flat_host] and flat_host[0][1] == -31
     det = U.WordDetector(gap_x=8, adaptive=adaptive)
+    read, run = [], det._binarizer.run
+    det._binarizer.run = lambda pages, arena=None: read.append(run(pages, arena=arena)) or read[-1]   # the binarised arena the detector reads
     for (got, info), (pg, _) in zip(det.detect(None, arena=flat), flat_host):
         want, winfo = D.detect_words_host(pg, gap_x=8, cap=1024, adaptive=adaptive)
         assert np.array_equal(got, want) and info.tolist() == winfo.tolist()
+    # one page table for the upload and everything derived from it: the same host array and the same device tensor, copied once
+    assert len(read) == 1 and read[0] is not flat and read[0].dev.data_ptr() != flat.dev.data_ptr()
+    assert arena.table_dev.is_cuda and flat.table_dev is arena.table_dev and read[0].table_dev is arena.table_dev
+    assert flat.table is arena.table and read[0].table is arena.table
     boxes = det.boxes(None, arena=flat)
     assert len(boxes[0]) == 28 and np.abs(np.array([[b[1], b[3], b[2], b[4]] for b in boxes[0]]) - rects).max() <= 1
     raw = det.boxes(None, arena=arena)[0]                                             # the raw page: 28 boxes, but taller and out of order

@@ -13,7 +13,8 @@ import torch
 
 import utils as U
 from crnn_mi355x import detect as D
-from gpu_util import L, P, S, ok, host
+from crnn_mi355x.pages import PAGE_DTYPE
+from gpu_util import L, P, S, ok, host, sentinel_arena
 import detect_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -22,20 +23,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "crnn-ocr-lite_amd")
 T_R, T_C = D.TILE_R, D.TILE_C
 SENTINELS = (77, -9)
-
-
-def _arena(pages, strides=None):
-    """Pages back to back on 16-byte boundaries, page k with row stride strides[k] (the padding bytes hold 0x5a) -> (arena, table)."""
-    strides = strides or [pg.shape[1] for pg in pages]
-    table, parts, pos = np.zeros(len(pages), D.PAGE_DTYPE), [], 0
-    for k, (pg, st) in enumerate(zip(pages, strides)):
-        buf = np.full((pg.shape[0], st), 0x5a, np.uint8)
-        buf[:, :pg.shape[1]] = pg
-        nbytes = -(-buf.size // 16) * 16
-        parts.append(np.concatenate([buf.ravel(), np.zeros(nbytes - buf.size, np.uint8)]))
-        table[k] = (pos, pg.shape[0], pg.shape[1], st)
-        pos += nbytes
-    return np.concatenate(parts), table
 
 
 def _call(arena_dev, arena_bytes, table, table_dev, n, prm, cap, fill, ws_bytes=None, ws_offset=0, null=None):
@@ -60,7 +47,7 @@ def _detect(pages, strides=None, cap=64, **params):
     """Two calls -> (rects (P, cap, 5), info (P, 4)), equal between the calls and equal to detect_words_host page by page."""
     p = dict(R.PLAIN, **params)
     prm = D.crnn_detect_params(cap=cap, **p)
-    arena, table = _arena(pages, strides)
+    arena, table, _ = sentinel_arena(pages, strides)
     arena_dev, table_dev = torch.from_numpy(arena).cuda(), torch.from_numpy(table.view(np.uint8)).cuda()
     outs = []
     for fill in SENTINELS:
@@ -197,7 +184,7 @@ def test_filter_bounds_at_equality_and_past_it():
 # ---- 5. the refusals ----------------------------------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_outputs_untouched():
     pages = [R.random_page(T_R + 3, T_C + 9, 0.3, seed=1), R.random_page(5, 7, 0.3, seed=2)]
-    arena, table = _arena(pages)
+    arena, table, _ = sentinel_arena(pages)
     arena_dev, table_dev = torch.from_numpy(arena).cuda(), torch.from_numpy(table.view(np.uint8)).cuda()
     good = dict(R.PLAIN, cap=8)
 
@@ -231,12 +218,12 @@ def test_refusals_leave_the_outputs_untouched():
     refused(-2, ws_bytes=need - 1)                                                   # a short workspace
     refused(-2, ws_offset=4)                                                         # a misaligned one
     # -3: a page above 4096 in either direction, more than 2^31 pixels in one call (the pages of a table may share bytes)
-    wide = np.zeros(1, D.PAGE_DTYPE); wide[0] = (0, 1, 4097, 4097)
+    wide = np.zeros(1, PAGE_DTYPE); wide[0] = (0, 1, 4097, 4097)
     refused(-3, table=wide, n=1)
-    tall = np.zeros(1, D.PAGE_DTYPE); tall[0] = (0, 4097, 1, 1)
+    tall = np.zeros(1, PAGE_DTYPE); tall[0] = (0, 4097, 1, 1)
     refused(-3, table=tall, n=1)
     big = torch.zeros(4096 * 4096, dtype=torch.uint8, device="cuda")
-    many = np.zeros(129, D.PAGE_DTYPE); many[:] = (0, 4096, 4096, 4096)
+    many = np.zeros(129, PAGE_DTYPE); many[:] = (0, 4096, 4096, 4096)
     many_dev = torch.from_numpy(many.view(np.uint8)).cuda()
     prm = D.crnn_detect_params(**good)
     assert L().crnn_detect_workspace_bytes(many.ctypes.data_as(ctypes.c_void_p), 129, ctypes.byref(prm)) == 0

@@ -14,6 +14,7 @@ import utils as U
 from crnn_mi355x import data as D
 from crnn_mi355x import ingest as I
 from crnn_mi355x import native
+from crnn_mi355x import pages as PG
 
 pytestmark = pytest.mark.gpu
 
@@ -148,7 +149,7 @@ def _raw(pages, index, rects, img_size, n=None, batch=None, mutate=None, null=()
     T0, T1 = img_size[0], img_size[1]
     rects = np.asarray(rects).reshape(-1, 4)
     rows = [(up, s[0], s[1]) + o for up, s, o in (I.plan_crop(int(r[1] - r[0]), int(r[3] - r[2]), img_size) for r in rects)]
-    arena, offs = I.pack_arena(pages)
+    arena, offs = PG.pack_arena(pages)
     tab = I.build_table(pages, offs, index, rects, tuple(np.array(c) for c in zip(*rows)), img_size)
     if mutate is not None:
         mutate(tab)

@@ -10,6 +10,7 @@ import utils as U
 from crnn_mi355x import data as D
 from crnn_mi355x import ingest as I
 from crnn_mi355x import native
+from crnn_mi355x import pages as PG
 
 # crop shapes (hc rows, wc columns); the rotated crop is (wc, hc).  Axis 0 (time, target T0): 1, T0//2 and T0//2 + 1 (the up-scale rule),
 # T0 - size in {3, 2, 1, 0}, size > T0; axis 1 (target T1) the same.  The product also holds "larger on one axis" and "on both".
@@ -99,7 +100,7 @@ def _table_for(pages, index, rects, img_size, p=0.):
     rects = np.asarray(rects).reshape(-1, 4)
     rows = [(up, s[0], s[1]) + o for up, s, o in (I.plan_crop(int(r[1] - r[0]), int(r[3] - r[2]), img_size, p=p) for r in rects)]
     plans = tuple(np.array(c) for c in zip(*rows))
-    arena, offs = I.pack_arena(pages)
+    arena, offs = PG.pack_arena(pages)
     return arena, offs, I.build_table(pages, offs, index, rects, plans, img_size)
 
 
@@ -124,7 +125,7 @@ def test_arena_and_table_round_trip():
         if up:
             assert it.up_scale0 == (c1 - c0) / float(s0) and it.up_scale1 == (r1 - r0) / float(s1)
     with pytest.raises(ValueError):
-        I.pack_arena([np.zeros((3, 3), np.float32)])
+        PG.pack_arena([np.zeros((3, 3), np.float32)])
     assert np.array_equal(I.norm_table(True, 118.5, 36.25), D.norm(np.arange(256, dtype=np.uint8), 118.5, 36.25))
     assert np.array_equal(I.norm_table(False), np.arange(256, dtype=np.float32)) and I.norm_table().dtype == np.float32
 
