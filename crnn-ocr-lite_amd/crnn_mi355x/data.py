@@ -168,11 +168,16 @@ class Readf:
     a bounded number of chunks in flight, so the generator keeps up with the device (one Python thread manages ~1 k
     images/s, the train step consumes 26 k/s per GPU).  Batches are identical to the serial loop when transform_p == 0;
     with random padding they are reproducible for a given `seed` whatever the worker count.  Scripts that use it
-    need the usual `if __name__ == "__main__":` guard."""
+    need the usual `if __name__ == "__main__":` guard.
+
+    `augment` (an augment.AugmentPolicy; default None = no augmentation): every emitted batch goes through augment.augment_host as uint8,
+    before `norm`, with the items the policy draws for it in the main process when the batch is emitted -- so the result does not
+    depend on `workers`, and the policy's own random stream leaves np.random alone."""
 
     def __init__(self, img_size=(40, 40), max_len=30, normed=False, batch_size=32, classes={},
-                 mean=118.24236953981779, std=36.72835353999682, transform_p=0.7, workers=0, seed=0, chunk=32):
+                 mean=118.24236953981779, std=36.72835353999682, transform_p=0.7, workers=0, seed=0, chunk=32, augment=None):
         self.workers, self.seed, self.chunk = int(workers), int(seed), max(1, int(chunk))
+        self.augment = augment
         self._pool = None
         self.batch_size = batch_size
         self.transform_p = transform_p
@@ -274,7 +279,7 @@ class Readf:
         full_batches, remainder = divmod(total, self.batch_size)
         steps_in = (self.img_size[0] + 4) // downsample_factor - 2
         slot, emitted = 0, 0
-        words = []
+        words, raw = [], []                    # raw: the batch's uint8 images, kept only for the augmentation
         X, Y, in_len, lab_len = self.get_blank_matrices()
         for pixels, word in self._instances(names, bboxs):
             words.append(word)
@@ -282,17 +287,24 @@ class Readf:
             Y[slot, :len(ids)] = ids
             lab_len[slot] = len(ids)
             in_len[slot] = steps_in
-            X[slot] = (norm(pixels, self.mean, self.std) if self.normed else pixels)[:, :, np.newaxis]
+            if self.augment is None:
+                X[slot] = (norm(pixels, self.mean, self.std) if self.normed else pixels)[:, :, np.newaxis]
+            else:
+                raw.append(pixels)
             slot += 1
             tail = emitted == full_batches and slot == remainder
             if not tail and slot != self.batch_size:
                 continue
+            if self.augment is not None:
+                from .augment import augment_host
+                pixels = augment_host(np.stack(raw), self.augment.draw(slot, self.img_size))
+                X[:slot] = (norm(pixels, self.mean, self.std) if self.normed else pixels)[..., np.newaxis]
             batch = ({'the_input': X, 'the_labels': Y, 'input_length': in_len, 'label_length': lab_len,
                       'source_str': np.array(words)}, {'ctc': np.zeros([self.batch_size])})
             if tail:
                 yield batch            # short tail of the first pass: same arrays, stale rows beyond `slot`
             else:
                 emitted += 1
-                slot, words = 0, []
+                slot, words, raw = 0, [], []
                 X, Y, in_len, lab_len = self.get_blank_matrices()
                 yield batch

@@ -2,7 +2,8 @@
 crnn_ingest_crops (csrc/ingest.hip) builds the normalised (B, imgh, imgw, 1) fp32 batch the forward reads -- bit-identical to what
 `data.open_img` + `data.norm` produce on the host (reference utils.py:364-416).  The host keeps the image file decoding, the slicing rules
 of `page[y0:y1, x0:x1]` and every random decision of the padding (`plan_crop` draws from np.random exactly as `open_img` does), so the
-kernel knows nothing about random numbers and serves augmented batches as well.
+kernel knows nothing about random numbers and serves augmented batches as well (the augmentation itself is a second launch on the uint8
+batch: crnn_mi355x/augment.py).
 
     ing = DeviceIngest((100, 32, 1))
     x, words = ing.pages([page], [[(None, x0, y0, x1, y1), ...]])      # x: device tensor (n, 100, 32, 1)
@@ -14,7 +15,7 @@ import numpy as np
 
 from . import native
 from .data import Readf, norm, read_img, _word_of
-from .pages import arena_layout, device_lib, pack_arena, upload_pages
+from .pages import StagingSlots, arena_layout, device_lib, pack_arena, upload_pages
 
 
 class crnn_crop_item(ctypes.Structure):
@@ -140,20 +141,7 @@ class DeviceIngest:
         self.img_size = tuple(img_size)
         self.T0, self.T1 = int(img_size[0]), int(img_size[1])
         self.table = torch.from_numpy(norm_table(normed, mean, std)).to(self.device)
-        self._slots = [{"host": None, "dev": None, "copied": torch.cuda.Event()} for _ in range(self._SLOTS)]
-        self._next = 0
-
-    def _slot(self, nbytes):
-        import torch
-        s = self._slots[self._next]
-        self._next = (self._next + 1) % len(self._slots)
-        s["copied"].synchronize()                       # the previous H->D copy out of this slot's host buffer is done
-        if s["host"] is None or s["host"].numel() < nbytes:
-            cap = max(1 << 20, 1 << (int(nbytes) - 1).bit_length())
-            s["host"] = torch.empty(cap, dtype=torch.uint8).pin_memory()
-            s["dev"] = torch.empty(cap, dtype=torch.uint8, device=self.device)
-            s["np"] = s["host"].numpy()
-        return s
+        self._slot = StagingSlots(self.device, self._SLOTS).take
 
     def upload(self, pages):
         """Pages -> PageArena (pages.py: the arena every page stage shares) on this ingest's device, for crops(..., arena=) and
@@ -235,16 +223,24 @@ class DeviceReadf(Readf):
     (B,) + img_size -- same visiting order, first-pass tail rule, labels, lengths and source_str as the serial Readf (workers=0), and for
     transform_p > 0 the same draws from np.random, so under one seed the images are the serial loop's bit for bit.  Rows past a short tail
     batch's items are zero (Readf leaves them undefined).  `workers=N` decodes the image files in N processes, in order and a bounded
-    number ahead (the one piece of work left on the host); everything after the decoding is the same for any worker count."""
+    number ahead (the one piece of work left on the host); everything after the decoding is the same for any worker count.
+    `augment` (an augment.AugmentPolicy): every emitted batch is augmented on the device, in a second launch on the same stream, with the
+    items the policy draws for it -- the batches of Readf(augment=policy) under the same seeds, bit for bit."""
 
     def __init__(self, *args, device=None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._device, self._ingest = device, None
+        self._device, self._ingest, self._augmenter = device, None, None
 
     def _get_ingest(self):
         if self._ingest is None:
             self._ingest = DeviceIngest(self.img_size, normed=self.normed, mean=self.mean, std=self.std, device=self._device)
         return self._ingest
+
+    def _get_augmenter(self):
+        if self._augmenter is None:
+            from .augment import Augmenter
+            self._augmenter = Augmenter(self.img_size, normed=self.normed, mean=self.mean, std=self.std, device=self._get_ingest().device)
+        return self._augmenter
 
     def _decoded(self, names, bboxs):
         """Endless stream of [(name, decoded image), ...] groups in the visiting order: one page, or a run of up to `chunk` one-word files
@@ -302,7 +298,11 @@ class DeviceReadf(Readf):
                 pages.append(page)
             index.append(k)
         plans = tuple(np.stack([it[2] for it in items], axis=1))
-        return self._get_ingest().crops(pages, index, [it[1] for it in items], plans, batch=self.batch_size)
+        rects = [it[1] for it in items]
+        if self.augment is None:
+            return self._get_ingest().crops(pages, index, rects, plans, batch=self.batch_size)
+        _, u8 = self._get_ingest().crops(pages, index, rects, plans, batch=self.batch_size, return_u8=True)
+        return self._get_augmenter().run(u8, self.augment.draw(len(items), self.img_size))
 
     def run_generator(self, names, downsample_factor=2, bboxs={}):
         if bboxs:

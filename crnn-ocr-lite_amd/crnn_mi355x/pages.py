@@ -104,6 +104,31 @@ def upload_pages(pages, device):
     return PageArena(pages, offs, nbytes, host, dev)
 
 
+class StagingSlots:
+    """Page-locked host buffers with their device twins, for the small tables a launch takes along (the ingest's arena and box table, the
+    augmentation's items): take(nbytes) -> {"host", "dev", "np", "copied"} of the next slot, grown to a power of two of at least `floor`
+    bytes.  A slot's host buffer is handed out again only after its previous copy has finished (the Engine.stage pattern): the caller records
+    "copied" on the stream after its H->D copy.  Copy and kernel are ordered by the stream, so successive calls belong on one stream."""
+
+    def __init__(self, device, slots=2, floor=1 << 20):
+        import torch
+        self.device, self.floor = device, int(floor)
+        self._slots = [{"host": None, "dev": None, "copied": torch.cuda.Event()} for _ in range(slots)]
+        self._next = 0
+
+    def take(self, nbytes):
+        import torch
+        s = self._slots[self._next]
+        self._next = (self._next + 1) % len(self._slots)
+        s["copied"].synchronize()                       # the previous H->D copy out of this slot's host buffer is done
+        if s["host"] is None or s["host"].numel() < nbytes:
+            cap = max(self.floor, 1 << (int(nbytes) - 1).bit_length())
+            s["host"] = torch.empty(cap, dtype=torch.uint8).pin_memory()
+            s["dev"] = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            s["np"] = s["host"].numpy()
+        return s
+
+
 def device_lib(who, host_path, device=None):
     """The preamble of a class that runs on the GPU -> (libcrnn_mi355x, the resolved torch device); RuntimeError without a GPU."""
     import torch

@@ -46,6 +46,13 @@ def build_parser():
     parser.add_argument('--imgW', type=int, default=32)
     parser.add_argument('--workers', type=int, default=0,
                         help='image decoding processes feeding the generator (0 = the reference\'s single-threaded loader)')
+    parser.add_argument('--device_ingest', action='store_true',
+                        help='build the training and validation batches on the GPU (crnn_mi355x.ingest.DeviceReadf)')
+    parser.add_argument('--augment', action='store_true',
+                        help='augment the training batches (crnn_mi355x.augment: warp, stroke width, blur, tone, noise; the default ranges are '
+                             'placeholders); on the GPU with --device_ingest.  The validation batches are never augmented')
+    parser.add_argument('--augment_p', type=float, default=None, metavar='P',
+                        help='with --augment: the probability that switches each augmentation stage on per image (default: the policy\'s own)')
     return parser
 
 
@@ -69,6 +76,7 @@ def main(argv=None):
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.G)
 
     import utils as U
+    from crnn_mi355x.data import _chunk_seed
     from crnn_mi355x.parallel import shard
 
     out_dir = args.save_path + "/" + args.model_name
@@ -94,8 +102,18 @@ def main(argv=None):
     lo, hi = shard(len(train), rank, world)    # equal shards: every rank runs the same number of steps (= collectives) per epoch
     train = train[lo:hi]
 
-    reader = U.Readf(img_size=(args.imgh, args.imgW, 1), normed=args.norm, batch_size=args.batch_size, classes=classes,
-                     max_len=max_len, transform_p=0.7, workers=args.workers, seed=args.random_state)
+    if args.augment_p is not None and not args.augment:
+        raise SystemExit("--augment_p goes with --augment")
+    policy = None
+    if args.augment:      # seeded per rank, so the ranks' shards are augmented differently
+        policy = U.AugmentPolicy(seed=_chunk_seed(args.random_state, rank), **({} if args.augment_p is None else {"p": args.augment_p}))
+
+    def make_reader(augment):
+        return (U.DeviceReadf if args.device_ingest else U.Readf)(
+            img_size=(args.imgh, args.imgW, 1), normed=args.norm, batch_size=args.batch_size, classes=classes, max_len=max_len, transform_p=0.7,
+            workers=args.workers, seed=args.random_state, **({} if augment is None else {"augment": augment}))
+    reader = make_reader(policy)
+    val_reader = reader if policy is None else make_reader(None)      # validation: a reader of its own, without augmentation
     print(" [INFO] Number of classes: {}; Max. string length: {} ".format(len(classes) + 1, max_len))
     init_model = U.CRNN(num_classes=len(classes) + 1, shape=(args.imgh, args.imgW, 1), GRU=args.GRU,
                         time_dense_size=args.time_dense_size, n_units=args.n_units, max_string_len=max_len)
@@ -124,7 +142,7 @@ def main(argv=None):
                                                   restore_best_weights=True, mode="auto"))
     down = 2 ** init_model.pooling_counter_h
     H = model.fit_generator(generator=reader.run_generator(train, downsample_factor=down), steps_per_epoch=train_steps,
-                            epochs=args.nbepochs, validation_data=reader.run_generator(val, downsample_factor=down) if val else None,
+                            epochs=args.nbepochs, validation_data=val_reader.run_generator(val, downsample_factor=down) if val else None,
                             validation_steps=test_steps, shuffle=False, verbose=1 if rank == 0 else 0, callbacks=callbacks_list)
     if rank == 0:
         pickle.dump(H.history, open(out_dir + '/loss_history.pickle.dat', 'wb'))

@@ -316,6 +316,41 @@ typedef struct {
 int crnn_ingest_crops(const void* arena, long arena_bytes, const crnn_crop_item* items, const crnn_crop_item* items_dev, int n, int batch, int imgh, int imgw,
                       const float* table, float* out, void* out_u8, crnn_stream_t stream);
 
+/* ---- training augmentation of the ingest's batch (csrc/augment.hip; the same rule in NumPy: crnn_mi355x.augment.augment_host) ----
+ * The input is the uint8 batch [batch][T0][T1] that crnn_ingest_crops writes as out_u8: axis 0 (i) is time and runs along the text, axis 1 (j)
+ * runs across it, ink is bright.  Image b < n has one crnn_augment_item; the host draws every random decision (crnn_mi355x.augment.AugmentPolicy)
+ * and the kernel has no random numbers of its own, no floating point before the table lookup and no atomics.  The stages run in this order on
+ * integer values v; every shift is arithmetic (the floor).
+ * 1 WARP: an inverse affine map in 16.16 fixed point about the image centre, in 64-bit integers (the arithmetic of crnn_rotate_pages):
+ *     di = 2 i - (T0 - 1), dj = 2 j - (T1 - 1);
+ *     Y = a00 di + a01 dj + t0 + ((T0 - 1) << 16), X = a10 di + a11 dj + t1 + ((T1 - 1) << 16);
+ *     i0 = Y >> 17, j0 = X >> 17, fy = (Y >> 9) & 255, fx = (X >> 9) & 255;
+ *     v = ((256 - fy)(256 - fx) tap(i0, j0) + (256 - fy) fx tap(i0, j0 + 1) + fy (256 - fx) tap(i0 + 1, j0) + fy fx tap(i0 + 1, j0 + 1) + 32768) >> 16.
+ *   tap outside the image is `fill` for fill 0..255 and the nearest image pixel for fill = -1.  a00 = a11 = 65536 with the rest 0 is the identity and
+ *   returns the input bytes; a01 is the slant, a shift along the text proportional to the position across it; t0, t1 are in 1 / 131072 pixel.
+ * 2 STROKE WIDTH: morph > 0 is the grey dilation (max), morph < 0 the grey erosion (min) over the (2 |morph| + 1)^2 window clipped to the image.
+ * 3 BLUR: `blur` passes of the binomial filter with edge replication: h = p[j - 1] + 2 p[j] + p[j + 1] along axis 1, then
+ *     v = (h[i - 1] + 2 h[i] + h[i + 1] + 8) >> 4 along axis 0.
+ * 4 TONE: v = clamp(((v - 128) gain + ((128 + bias) << 8) + 128) >> 8, 0, 255); gain is 8.8 fixed point, 256 is neutral.
+ * 5 NOISE: o = i T1 + j, h = mix32(seed ^ (o * 0x9E3779B9 mod 2^32)) with mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b;
+ *     x ^= x >> 16 (modulo 2^32); s = the sum of the four bytes of h, minus 510; v = clamp(v + ((s noise) >> 8), 0, 255).
+ * 6 OUTPUT: out[b] = table[v] (the 256 fp32 of crnn_ingest_crops), out_u8[b] = v when out_u8 is given; rows n <= b < batch are 0.f and 0.
+ * A stage whose parameter is neutral leaves v unchanged and is skipped.  Ranges: |a00|, |a01|, |a10|, |a11| <= 262144, |t0| <= T0 << 17,
+ * |t1| <= T1 << 17, fill -1..255, morph -2..2, blur 0..2, gain 0..1024, bias -255..255, noise 0..64. */
+typedef struct {
+  int a00, a01, a10, a11, t0, t1;
+  int fill, morph, blur, gain, bias, noise;
+  unsigned seed;
+} crnn_augment_item;
+/* out [batch][imgh][imgw] fp32 (and out_u8, or NULL) = the rule above on in_u8 [batch][imgh][imgw] uint8 (device); one launch, one workgroup per image,
+ * which stages the image in LDS once and runs the stages between two LDS buffers; bit-equal between calls and to augment_host.  items is the table in
+ * HOST memory, judged before anything is launched, items_dev the copy of the same n entries in device memory that the kernel reads (as crnn_ingest_crops
+ * takes its table).  CRNN_ERR_ARG (-2), with nothing launched: n < 0 or n > batch, batch < 1, a non-positive size, a null in_u8, table or out, null item
+ * pointers when n > 0, an item out of range, an out_u8 whose batch * imgh * imgw bytes overlap in_u8's in any way.  CRNN_ERR_UNSUPPORTED (-3):
+ * imgh * imgw > 16384 (two 16 KiB LDS buffers: 100 x 32, 200 x 32 and 512 x 32 fit). */
+int crnn_augment_batch(const void* in_u8, const crnn_augment_item* items, const crnn_augment_item* items_dev, int n, int batch, int imgh, int imgw,
+                       const float* table, float* out, void* out_u8, crnn_stream_t stream);
+
 /* ---- word detection: page images -> the word boxes crnn_ingest_crops takes (csrc/detect.hip; the same rule in NumPy: crnn_mi355x.detect) ---- */
 /* A page: a row-major uint8 image at byte `page_off` of the arena, 1 <= rows, cols <= 4096 -- the page fields of crnn_crop_item.  The arena and
  * the checks of a page table are defined once, in csrc/pages.h for the library and in crnn_mi355x/pages.py for Python. */
