@@ -15,6 +15,57 @@ pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
+# ------------------------------------------------------------------------------------------------ the hot regime
+# ReLU6 clamps at 0 and at 6.  The cold draws of the tests below (gamma about 1, beta about 1 .. 1.5) leave the ceiling 4.5 - 5 sigma away, so a kernel that
+# implemented ReLU would pass them.  Each test_*_hot case re-runs its test -- same assertions, same tolerances -- with BatchNorm parameters that put the
+# pre-activation at about N(3, 2^2): 6-7 % of the decided elements at each end, and asserts on the host that it got there.
+# Which hot case holds which spelling of the gate 0 < t < 6 to a host reference (each fails with the `< 6` term taken out of the kernels):
+#   conv.hip  BatchNorm backward, statistics and apply passes   bn_relu6_pool_dropout, batchnorm_backward_..._as_planes, pooled_..._saved_window_maxima (sum gy)
+#   conv.hip  saved-window-maxima passes (`best`)               pooled_..._saved_window_maxima (bit identity with the pass above)
+#   conv.hip  block 1: one backward pass over dq, c1 backward   block1_kernels_with_batchnorm1_folded_in (sum gy, BatchNorm-1 input gradient)
+#   conv_bwd_fused.hip                                          fused_depthwise_stage_backward (dx, dk against the oracle)
+#   dwconv_bwd_stream.hip  BatchNorm-1 gate of every form       fused_depthwise_stage_backward[(1, 3, 18, 256)], fp32_row_stream_depthwise_stage_backward
+#   dwconv_bwd_stream.hip  producer's BatchNorm-2 statistics    row_stream_..._batchnorm2_prologue (bf16: the statistics wave), its fp32 twin (the DX waves)
+#                          (the fp32 branch inside the statistics wave is compiled out -- that wave exists for bf16 tensors only -- and no case can reach it)
+#   gemm_tile.h / gemm_wres.hip / gemm_wres3.hip / gemm_pres.hip   three_plane_ / weights_resident_ / resident_weight_plane_ / data_gradient_from_planes (sums vs fp64)
+# and the clamp itself (relu6f and the three fmed3 staging forms of gemm_bf16.hip, gemm_wgrad.hip, gemm_wres.hip: each hot forward case fails with ReLU in
+# their place): bn_relu6_pool_dropout, the two prologue tests, pwconv_with_producer_bn_relu6, three_plane_gemms_..._while_staging, two_plane_weight_gradient,
+# inference_epilogues, weights_resident_inference_conv, block1; the fmed3 forms by pwconv_with_producer_bn_relu6 and the bf16s model cases of test_gpu_model.py.
+def _bn_affine(rs, C, hot, cold=None):
+    """-> gamma, beta.  hot: gamma = 2 (1 + 0.3 U(-1, 1)), beta = 3 + 0.6 U(-1, 1); otherwise cold(), the calling test's own draws in their own order."""
+    if not hot:
+        return cold()
+    return 2 * (1 + 0.3 * rs.uniform(-1, 1, C)), 3 + 0.6 * rs.uniform(-1, 1, C)
+
+
+def _hot_scale_shift(rs, C, mean, std):
+    """-> scale, shift with t = d * scale + shift about N(beta, gamma^2) of _bn_affine's hot draws, for d about N(mean, std^2): tests that hand the kernel a
+    BatchNorm state directly or use inference statistics."""
+    gamma, beta = _bn_affine(rs, C, True)
+    scale = gamma / std
+    return scale, beta - mean * scale
+
+
+def _hot_infer_affine(rs, z, mmean, mvar):
+    """-> gamma, beta of an inference BatchNorm (moving statistics mmean, mvar) that put its output at about N(3, 2^2) for the columns of z as they are."""
+    g, b = _bn_affine(rs, z.shape[-1], True)
+    gamma = g * np.sqrt(mvar + ops.BN_EPS) / z.std(0)
+    return gamma, b - (z.mean(0) - mmean) * g / z.std(0)
+
+
+def _assert_hot(t, pool=None):
+    """The coverage a hot case is for: at least 3 % of the pre-activations t at or above 6 and at least 3 % at or below 0; with pool = (ph, pw) on
+    t[B, H, W, C], at least one pooling window holding two elements at the ceiling (a tie at exactly 6.0 after the clamp)."""
+    t = np.asarray(t)
+    hi, lo = float((t >= 6).mean()), float((t <= 0).mean())
+    assert hi >= 0.03 and lo >= 0.03, "not a hot case: %.4f of the pre-activations at the ceiling, %.4f at the floor" % (hi, lo)
+    if pool is not None and pool[0] * pool[1] > 1:
+        B, H, W, C = t.shape
+        ph, pw = pool
+        tw = t[:, :H // ph * ph, :W // pw * pw, :].reshape(B, H // ph, ph, W // pw, pw, C)
+        assert bool(((tw >= 6).sum(axis=(2, 4)) >= 2).any()), "no pooling window with two elements at the ceiling"
+
+
 # ------------------------------------------------------------------------------------------------ GEMM
 @pytest.mark.parametrize("mode", [0, 1, 2])
 @pytest.mark.parametrize("shape", [(300, 130, 70), (128, 64, 32), (1000, 38, 512), (77, 20, 25), (513, 257, 129),
@@ -194,16 +245,16 @@ def test_dwconv_fwd_flip_wgrad_stats(shape):
                                    (3, 104, 36, 64), (2, 204, 36, 128), (40, 52, 18, 256), (128, 52, 9, 512), (2, 7, 36, 64), (1, 3, 18, 256),
                                    # round 5: image widths 48 (ranges of 208 columns: three and a quarter of the five waves busy) and 64 (272 columns) on the row-stream kernel
                                    (3, 64, 52, 64), (2, 64, 52, 128), (4, 32, 26, 256), (40, 32, 13, 512), (2, 104, 68, 64), (2, 104, 68, 128), (3, 52, 34, 256), (2, 52, 17, 512)])
-def test_fused_depthwise_stage_backward_equals_the_three_kernel_sequence(shape):
+def test_fused_depthwise_stage_backward_equals_the_three_kernel_sequence(shape, hot=False, seed=None):
     """crnn_dwconv3x3_bwd_fused (BatchNorm-backward pass 2 formed in the halo-tile fill, depthwise weight and data gradients from one
     pass over the tiles) against crnn_bn_bwd_ex + crnn_dwconv3x3_wgrad_ex + crnn_dwconv3x3_fwd_ex(flip=1) on bf16 tensors: the data
     gradient bit for bit, the weight gradient to fp32 summation-order round-off; both against the fp64 oracle.  Several bands per
     workgroup, ragged widths and heights, band counts that do not divide."""
     B, H, W, C = shape
-    rs = np.random.RandomState(sum(shape))
+    rs = np.random.RandomState(sum(shape) if seed is None else seed)
     x = _bf16_round(rs.normal(size=shape)); k = rs.normal(size=(3, 3, C))
     d = _bf16_round(ops.dwconv_fwd(x, k))
-    gamma, beta = rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 1.0
+    gamma, beta = _bn_affine(rs, C, hot, lambda: (rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 1.0))
     da = _bf16_round(rs.normal(size=shape))
     xd, dd, dad, kd = _to_bf16_dev(x), _to_bf16_dev(d), _to_bf16_dev(da), dev(k)
     M = B * H * W
@@ -231,7 +282,12 @@ def test_fused_depthwise_stage_backward_equals_the_three_kernel_sequence(shape):
     assert_close(host(dk2), host(dk1), rtol=2e-5, atol=2e-4 * np.abs(host(dk1)).max(), what="dk fused vs sequence")
     # fp64 oracle of the same stage (gradient w.r.t. d through BN + ReLU6, then the conv gradients); dd is stored as bf16 on both paths
     xhat = (d - mean) / np.sqrt(var + 1e-3); y = xhat * gamma + beta
+    if hot:
+        _assert_hot(y)
     gy = da * ((y > 0) & (y < 6))
+    if hot:     # (with two pixels per channel BatchNorm's input gradient, hence dx and dk, is zero whatever the gate: there the statistics pass's sum gy decides)
+        sgy = gy.reshape(M, C).sum(0)
+        assert_close(host(db1), sgy, rtol=1e-4, atol=1e-4 * np.abs(gy).reshape(M, C).sum(0).max(), what="sum gy vs fp64")
     ddn = scale * (gy - gy.reshape(M, C).mean(0) - xhat * (gy * xhat).reshape(M, C).mean(0))
     dx_ref, dk_ref = ops.dwconv_bwd(x, k, _bf16_round(ddn))
     assert_close(_f(dx2), dx_ref, rtol=2.0 ** -7, atol=2e-2 * np.abs(dx_ref).max(), what="dx vs oracle")
@@ -255,17 +311,25 @@ def test_fused_depthwise_stage_backward_equals_the_three_kernel_sequence(shape):
         assert L().crnn_dwconv_bwd_stream_rows(B, H, W, C) == 0
 
 
+@pytest.mark.parametrize("shape,seed", [((2, 13, 7, 64), 86), ((2, 1, 1, 64), 96371), ((1, 3, 18, 256), 278)])
+def test_fused_depthwise_stage_backward_equals_the_three_kernel_sequence_hot(shape, seed):
+    """The hot regime on the halo-tile kernel's two smallest shapes and on the smallest one the row-stream kernel takes as well.  Two pixels per channel
+    put the pre-activations at beta +- gamma, past a threshold for one channel in seventy: seed 96371 is the first with 3 % of them at each end."""
+    assert (L().crnn_dwconv_bwd_stream_supported(*shape) == 0) == (shape == (1, 3, 18, 256))
+    test_fused_depthwise_stage_backward_equals_the_three_kernel_sequence(shape, hot=True, seed=seed)
+
+
 @pytest.mark.parametrize("shape", [(2, 104, 36, 128), (3, 52, 18, 256), (2, 52, 9, 512), (3, 104, 36, 64), (2, 204, 36, 128), (40, 52, 18, 256), (70, 52, 9, 512),
                                    (1, 40, 36, 64), (2, 13, 7, 64), (1, 3, 18, 256), (3, 64, 52, 64), (4, 32, 26, 256), (2, 104, 68, 128), (2, 52, 17, 512)])
-def test_fp32_row_stream_depthwise_stage_backward_equals_the_three_kernel_sequence(shape):
+def test_fp32_row_stream_depthwise_stage_backward_equals_the_three_kernel_sequence(shape, hot=False, seed=None):
     """crnn_dwconv3x3_bwd_stream_ex(dtype = fp32) -- the parity mode's depthwise-stage backward in one pass (round 4) -- against
     crnn_bn_bwd_ex + crnn_dwconv3x3_wgrad_ex + crnn_dwconv3x3_fwd_ex(flip = 1) on fp32 tensors: the data gradient bit for bit, the weight
     gradient to fp32 summation-order round-off; both against the fp64 oracle at the fp32 kernels' tolerance.  Shapes the rule refuses report so."""
     B, H, W, C = shape
-    rs = np.random.RandomState(sum(shape) + 1)
+    rs = np.random.RandomState(sum(shape) + 1 if seed is None else seed)
     x = rs.normal(size=shape).astype(np.float32).astype(np.float64); k = rs.normal(size=(3, 3, C))
     d = ops.dwconv_fwd(x, k).astype(np.float32).astype(np.float64)
-    gamma, beta = rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 1.0
+    gamma, beta = _bn_affine(rs, C, hot, lambda: (rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 1.0))
     da = rs.normal(size=shape).astype(np.float32).astype(np.float64)
     xd, dd, dad, kd = dev(x), dev(d), dev(da), dev(k)
     M = B * H * W
@@ -275,7 +339,7 @@ def test_fp32_row_stream_depthwise_stage_backward_equals_the_three_kernel_sequen
     sup = L().crnn_dwconv_bwd_stream_supported_ex(B, H, W, C, 0)
     rows = L().crnn_dwconv_bwd_stream_rows_ex(B, H, W, C, 0)
     if sup != 0:
-        assert sup == -3 and rows == 0
+        assert sup == -3 and rows == 0 and not hot
         assert L().crnn_dwconv3x3_bwd_stream_ex(P(dd), P(dad), P(st), P(st), P(xd), P(kd), P(dd), P(kd), P(kd), B, H, W, C, 0, S()) == -3
         return
     assert rows >= B
@@ -301,6 +365,9 @@ def test_fp32_row_stream_depthwise_stage_backward_equals_the_three_kernel_sequen
     ddn = scale * (gy - gy.reshape(M, C).mean(0) - xhat * (gy * xhat).reshape(M, C).mean(0))
     dx_ref, dk_ref = ops.dwconv_bwd(x, k, ddn)
     near = np.minimum(np.abs(y), np.abs(y - 6)) < 1e-4          # (activations within round-off of a ReLU6 threshold may gate differently)
+    if hot:                                                      # (the hot cases' seeds leave none, so the oracle comparison below always runs)
+        _assert_hot(y)
+        assert not near.any()
     if not near.any():
         assert_close(host(dx2[:-64]).reshape(shape), dx_ref, rtol=1e-4, atol=1e-4 * np.abs(dx_ref).max(), what="dx vs oracle")
         assert_close(host(dk2).reshape(3, 3, C), dk_ref, rtol=1e-4, atol=1e-4 * np.abs(dk_ref).max(), what="dk vs oracle")
@@ -308,6 +375,12 @@ def test_fp32_row_stream_depthwise_stage_backward_equals_the_three_kernel_sequen
     assert L().crnn_dwconv_bwd_stream_supported_ex(B, H, W, C, 1) == L().crnn_dwconv_bwd_stream_supported(B, H, W, C)
     assert L().crnn_dwconv_bwd_stream_rows_ex(B, H, W, C, 1) == L().crnn_dwconv_bwd_stream_rows(B, H, W, C)
     assert L().crnn_dwconv_bwd_stream_supported_ex(B, H, W, C, 7) == -2
+
+
+@pytest.mark.parametrize("shape,seed", [((1, 3, 18, 256), 280), ((1, 40, 36, 64), 154)])
+def test_fp32_row_stream_depthwise_stage_backward_equals_the_three_kernel_sequence_hot(shape, seed):
+    """The hot regime on the two smallest shapes of the list that the kernel takes ((2, 13, 7, 64) is refused and would return before any launch)."""
+    test_fp32_row_stream_depthwise_stage_backward_equals_the_three_kernel_sequence(shape, hot=True, seed=seed)
 
 
 # ------------------------------------------------------------------------------------------------ BatchNorm chain
@@ -325,15 +398,20 @@ def _bn_state(x, gamma, beta):
 
 @pytest.mark.parametrize("shape,pool,rate", [((3, 8, 6, 64), (1, 1), 0.0), ((2, 8, 6, 32), (2, 2), 0.0), ((2, 6, 8, 128), (1, 2), 0.1),
                                             ((2, 7, 5, 1), (1, 1), 0.0), ((2, 9, 7, 36), (2, 2), 0.1)])
-def test_bn_relu6_pool_dropout_fwd_bwd(shape, pool, rate):
+def test_bn_relu6_pool_dropout_fwd_bwd(shape, pool, rate, hot=False, seed=None):
     B, H, W, C = shape
     ph, pw = pool
-    rs = np.random.RandomState(sum(shape) + ph)
+    rs = np.random.RandomState(sum(shape) + ph if seed is None else seed)
     x = rs.normal(size=shape) * 3 + 1.0
-    x = np.round(x * 4) / 4  # coarse grid => ties / saturated ReLU6 values inside pool windows
-    gamma = 1 + 0.3 * rs.normal(size=C); beta = 0.5 * rs.normal(size=C) + 1.5
+    # coarse grid => tied maxima inside pool windows.  ReLU6 saturates in the hot cases only (windows tied at exactly 6.0): the cold draws below leave the
+    # ceiling 4.5 - 5 sigma away, 0 to 2 pre-activations per case at or above 6
+    x = np.round(x * 4) / 4
+    gamma, beta = _bn_affine(rs, C, hot, lambda: (1 + 0.3 * rs.normal(size=C), 0.5 * rs.normal(size=C) + 1.5))
     xd, st = _bn_state(x, gamma, beta)
     y_bn, mean, var = ops.bn_train_fwd(x, gamma, beta)
+    if hot:     # both ends decided, a window tied at the ceiling, and (the decision below is the fp64 oracle's) nothing within fp32 reach of a threshold
+        _assert_hot(y_bn, pool)
+        assert float(np.minimum(np.abs(y_bn), np.abs(y_bn - 6)).min()) >= 1e-4
     sth = host(st)
     assert_close(sth[:C], mean, what="mean"); assert_close(sth[C:2 * C], var, what="var")
     Ho, Wo = H // ph, W // pw
@@ -361,6 +439,14 @@ def test_bn_relu6_pool_dropout_fwd_bwd(shape, pool, rate):
     assert_close(host(dgm), dg_ref, rtol=2e-4, atol=1e-4, what="dgamma")
     assert_close(host(dbt), db_ref, rtol=2e-4, atol=1e-4, what="dbeta")
     assert_close(host(dx), dx_ref, rtol=2e-4, atol=1e-5, what="dx")
+
+
+@pytest.mark.parametrize("shape,pool,rate,seed", [((3, 8, 6, 64), (1, 1), 0.0, 1), ((2, 8, 6, 32), (2, 2), 0.0, 1), ((2, 6, 8, 128), (1, 2), 0.1, 1),
+                                                 ((2, 7, 5, 1), (1, 1), 0.0, 3), ((2, 9, 7, 36), (2, 2), 0.1, 1)])
+def test_bn_relu6_pool_dropout_fwd_bwd_hot(shape, pool, rate, seed):
+    """The five shapes with 6-7 % of the pre-activations at each end of ReLU6 and pooling windows tied at 6.0, against the fp64 oracle as above.  The seeds
+    are the first that keep every fp64 pre-activation 1e-4 away from both thresholds (and, for the one-channel shape, reach 3 % at both ends)."""
+    test_bn_relu6_pool_dropout_fwd_bwd(shape, pool, rate, hot=True, seed=seed)
 
 
 @pytest.mark.parametrize("pattern", [0, 1])
@@ -1045,7 +1131,7 @@ def test_row_stream_depthwise_equals_the_halo_tile_kernel(B, H, W, C):
 
 @pytest.mark.parametrize("B,H,W,C", [(3, 104, 36, 64), (2, 104, 36, 128), (5, 52, 18, 256), (2, 52, 9, 512), (256, 52, 9, 512), (70, 104, 36, 64)])
 @pytest.mark.parametrize("rate", [0.1, 0.0])
-def test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_path(B, H, W, C, rate):
+def test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_path(B, H, W, C, rate, hot=False):
     """crnn_dwconv3x3_fwd_stream_pro / crnn_dwconv3x3_bwd_stream_pro: the previous block's BatchNorm-2 + ReLU6 + Dropout(.1) (utils.py:48-56)
     applied to its pointwise output q inside the depthwise row-stream kernels (LDS, one row ahead) instead of by crnn_bn_act_pool_drop_ex
     writing x: depthwise outputs, BatchNorm-1 statistic partials, data gradient and depthwise weight gradient are bit-identical to the
@@ -1056,7 +1142,8 @@ def test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_p
     n = B * H * W * C
     qd = (torch.randn(n, device="cuda", generator=torch.Generator("cuda").manual_seed(n % 1000)) * 1.5).to(torch.bfloat16)
     k = rs.normal(size=(3, 3, C)); kd = dev(k)
-    st2 = dev(np.concatenate([rs.normal(size=C), 1 + rs.uniform(size=C), 1 + 0.5 * rs.normal(size=C), 1.5 * rs.normal(size=C) + 1.5]))
+    ss2 = _hot_scale_shift(rs, C, 0.0, 1.5) if hot else None
+    st2 = dev(np.concatenate([rs.normal(size=C), 1 + rs.uniform(size=C)] + (list(ss2) if hot else [1 + 0.5 * rs.normal(size=C), 1.5 * rs.normal(size=C) + 1.5])))
     seed, layer = 77, 4
     ng = n // 8
     keep = torch.full((ng + 3 + 64,), 0x55, dtype=torch.uint8, device="cuda")
@@ -1073,6 +1160,11 @@ def test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_p
     ok(L().crnn_bn_act_pool_drop_ex(P(qd), P(st2), P(xd), B, H, W, C, 1, 1, rate, seed, layer, 1, 1, S()))
     xf = xd.float()
     assert float((xf == 0).float().mean()) > (0.08 if rate > 0 else 0.0) and float((xf > 6.0).float().mean()) > (1e-3 if rate > 0 else -1)
+    if hot:     # both paths below read the same ReLU6: the hot case also holds the materialised x against the host's clamp at both ends
+        st2h = host(st2).reshape(4, C); mh = host(m).reshape(-1, C)
+        t2 = host(qd.float()).reshape(-1, C) * st2h[2] + st2h[3]                # fp32 replay of the device's fma
+        _assert_hot(t2)
+        assert_close(_f(xd).reshape(-1, C), _bf16_round(np.clip(t2, 0.0, 6.0) * mh), rtol=2.0 ** -8, atol=1e-6, what="x vs the host's ReLU6")
     # ---- forward
     rows = L().crnn_dwconv_fwd_stream_rows(B, H, W, C)
     o1 = torch.zeros(n, dtype=torch.bfloat16, device="cuda"); p1 = zeros(rows, 2, C)
@@ -1097,9 +1189,12 @@ def test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_p
     M = B * H * W
     dh = dd.float().view(M, C).double()
     mean, var = dh.mean(0).cpu().numpy(), dh.var(0, unbiased=False).cpu().numpy()
-    gamma, beta = rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 1.0
+    gamma, beta = _bn_affine(rs, C, hot, lambda: (rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 1.0))
     scale = gamma / np.sqrt(var + 1e-3)
     st1 = dev(np.concatenate([mean, var, scale, beta - mean * scale]))
+    if hot:     # the consuming stage's BatchNorm-1 gate, decided inside the backward kernels
+        st1h = host(st1).reshape(4, C)
+        _assert_hot(host(dd.float()).reshape(M, C) * st1h[2] + st1h[3])
     coef = dev(np.concatenate([rs.normal(size=C) * 1e-3, rs.normal(size=C) * 1e-3]))
     brow = L().crnn_dwconv_bwd_stream_rows(B, H, W, C)
     dx1 = torch.zeros(n, dtype=torch.bfloat16, device="cuda"); dk1 = zeros(9, C); sc = zeros(brow * 9 * C)
@@ -1123,14 +1218,21 @@ def test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_p
     ok(L().crnn_bn_bwd_ex(P(qd), P(dx1), P(st2), P(gam), P(gq), P(dg1), P(db1), P(pp), P(coef1), B, H, W, C, 1, 1, rate, seed, layer, 1, S()))
     for a, b, what in ((db2, db1, "sum gy"), (dg2, dg1, "sum gy xhat"), (coef2, coef1, "coefficients")):
         assert_close(host(a), host(b), rtol=2e-4, atol=2e-5 * max(1.0, float(b.abs().max())), what="BatchNorm-2 backward " + what)
+    if hot:     # ... and the stand-alone pass's sum gy against the fp64 sum under ReLU6's two-sided gate
+        gy = np.where((t2 > 0) & (t2 < 6), _f(dx1).reshape(M, C) * mh, 0.0)
+        assert_close(host(db1), gy.sum(0), rtol=1e-4, atol=1e-4 * np.abs(gy).sum(0).max(), what="sum gy vs fp64")
     gq2 = torch.zeros_like(gq)
     ok(L().crnn_bn_bwd_apply_ex(P(qd), P(dx1), P(st2), P(coef1), P(gq2), B, H, W, C, 1, 1, rate, seed, layer, 1, S()))
     assert torch.equal(gq2, gq)
 
 
+def test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_path_hot():
+    test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_path(3, 104, 36, 64, 0.1, hot=True)
+
+
 @pytest.mark.parametrize("B,H,W,C", [(3, 104, 36, 64), (2, 104, 36, 128), (5, 52, 18, 256), (2, 52, 9, 512), (256, 52, 9, 512), (70, 104, 36, 64)])
 @pytest.mark.parametrize("rate", [0.1, 0.0])
-def test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms(B, H, W, C, rate):
+def test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms(B, H, W, C, rate, hot=False):
     """The fp32 forms of the row-stream kernels (round 4, the parity mode): crnn_dwconv3x3_fwd_stream_dt against the halo-tile kernel (outputs
     bit for bit, statistics to summation order); crnn_dwconv3x3_fwd_stream_pro_ex / crnn_dwconv3x3_bwd_stream_pro_ex (BatchNorm-2 + ReLU6 +
     Dropout(.1) of the previous block applied to q in LDS; keep bytes read as nibbles) against crnn_bn_act_pool_drop_ex + the plain fp32 forms on
@@ -1143,7 +1245,8 @@ def test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms(B
     n = B * H * W * C
     qd = torch.randn(n, device="cuda", generator=torch.Generator("cuda").manual_seed(n % 1000 + 1)) * 1.5
     k = rs.normal(size=(3, 3, C)); kd = dev(k)
-    st2 = dev(np.concatenate([rs.normal(size=C), 1 + rs.uniform(size=C), 1 + 0.5 * rs.normal(size=C), 1.5 * rs.normal(size=C) + 1.5]))
+    ss2 = _hot_scale_shift(rs, C, 0.0, 1.5) if hot else None
+    st2 = dev(np.concatenate([rs.normal(size=C), 1 + rs.uniform(size=C)] + (list(ss2) if hot else [1 + 0.5 * rs.normal(size=C), 1.5 * rs.normal(size=C) + 1.5])))
     seed, layer = 78, 2
     ng = n // 8
     keep = torch.full((ng + 3 + 64,), 0x55, dtype=torch.uint8, device="cuda")
@@ -1151,6 +1254,13 @@ def test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms(B
     xd = zeros(n)
     ok(L().crnn_bn_act_pool_drop_ex(P(qd), P(st2), P(xd), B, H, W, C, 1, 1, rate, seed, layer, F32, F32, S()))
     assert float((xd == 0).float().mean()) > (0.08 if rate > 0 else 0.0) and float((xd > 6.0).float().mean()) > (1e-3 if rate > 0 else -1)
+    if hot:     # both paths below read the same ReLU6: the hot case also holds the materialised x against the host's clamp at both ends
+        m = zeros(n)
+        ok(L().crnn_dropout_mask(P(m), n, rate, seed, layer, S()))
+        st2h = host(st2).reshape(4, C); mh = host(m).reshape(-1, C)
+        t2 = host(qd).reshape(-1, C) * st2h[2] + st2h[3]                        # fp32 replay of the device's fma
+        _assert_hot(t2)
+        assert_close(host(xd).reshape(-1, C), np.clip(t2, 0.0, 6.0) * mh, what="x vs the host's ReLU6")
     # ---- forward: tile kernel, plain stream form, prologue form
     ntiles = L().crnn_dwconv_num_tiles(B, H, W)
     o0 = zeros(n); p0 = zeros(ntiles, 2, C)
@@ -1178,9 +1288,12 @@ def test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms(B
     M = B * H * W
     dh = dd.view(M, C).double()
     mean, var = dh.mean(0).cpu().numpy(), dh.var(0, unbiased=False).cpu().numpy()
-    gamma, beta = rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 1.0
+    gamma, beta = _bn_affine(rs, C, hot, lambda: (rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 1.0))
     scale = gamma / np.sqrt(var + 1e-3)
     st1 = dev(np.concatenate([mean, var, scale, beta - mean * scale]))
+    if hot:     # the consuming stage's BatchNorm-1 gate, decided inside the backward kernels
+        st1h = host(st1).reshape(4, C)
+        _assert_hot(host(dd.float()).reshape(M, C) * st1h[2] + st1h[3])
     coef = dev(np.concatenate([rs.normal(size=C) * 1e-3, rs.normal(size=C) * 1e-3]))
     brow = L().crnn_dwconv_bwd_stream_rows_ex(B, H, W, C, F32)
     dx1 = zeros(n); dk1 = zeros(9, C); sc = zeros(brow * 9 * C)
@@ -1201,6 +1314,13 @@ def test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms(B
     ok(L().crnn_bn_bwd_ex(P(qd), P(dx1), P(st2), P(gam), P(gq), P(dg1), P(db1), P(pp), P(coef1), B, H, W, C, 1, 1, rate, seed, layer, F32, S()))
     for a, b, what in ((db2, db1, "sum gy"), (dg2, dg1, "sum gy xhat"), (coef2, coef1, "coefficients")):
         assert_close(host(a), host(b), rtol=2e-4, atol=2e-5 * max(1.0, float(b.abs().max())), what="BatchNorm-2 backward " + what)
+    if hot:     # ... and the stand-alone pass's sum gy against the fp64 sum under ReLU6's two-sided gate
+        gy = np.where((t2 > 0) & (t2 < 6), host(dx1).reshape(M, C).astype(np.float64) * mh, 0.0)
+        assert_close(host(db1), gy.sum(0), rtol=1e-4, atol=1e-4 * np.abs(gy).sum(0).max(), what="sum gy vs fp64")
+
+
+def test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms_hot():
+    test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms(3, 104, 36, 64, 0.1, hot=True)
 
 
 def test_dropout_rng_statistics():
@@ -1340,14 +1460,16 @@ def test_bf16_dwconv_ragged_width_after_nan_filled_lds(shape):
 
 
 @pytest.mark.parametrize("shape", [(3000, 128, 64, 1), (1111, 64, 256, 1), (2049, 256, 128, 0), (520, 512, 512, 1)])
-def test_pwconv_with_producer_bn_relu6_matches_the_two_pass_path(shape):
+def test_pwconv_with_producer_bn_relu6_matches_the_two_pass_path(shape, hot=False):
     """crnn_pwconv_bnrelu6_fwd / _wgrad apply ReLU6(BN(d)) while the GEMM stages its operand; the result must be
     bit-identical to materialising a = ReLU6(BN(d)) with crnn_bn_act_pool_drop_ex (bf16) and running the plain GEMMs --
     output tensor, BatchNorm statistics partials and weight gradient -- and within bf16 round-off of the fp64 oracle."""
     M, N, K, wt = shape
     rs = np.random.RandomState(M + N)
     d = _bf16_round(rs.normal(size=(M, K)) * 2.0)
-    scale = rs.normal(size=K); shift = rs.normal(size=K) + 1.0
+    scale, shift = _hot_scale_shift(rs, K, 0.0, 2.0) if hot else (rs.normal(size=K), rs.normal(size=K) + 1.0)
+    if hot:
+        _assert_hot(d * scale + shift)
     w = _bf16_round(rs.normal(size=(K, N)) / np.sqrt(K)); g = _bf16_round(rs.normal(size=(M, N)))
     st = dev(np.concatenate([np.zeros(K), np.ones(K), scale, shift]))
     dd, gd = _to_bf16_dev(d), _to_bf16_dev(g)
@@ -1378,6 +1500,10 @@ def test_pwconv_with_producer_bn_relu6_matches_the_two_pass_path(shape):
     assert_close(host(dw1), _f(a).astype(np.float64).T @ g, rtol=1e-3, atol=2e-2 * np.sqrt(M / 1000.0), what="dw")
     # contract: a missing BatchNorm state is refused
     assert L().crnn_pwconv_bnrelu6_fwd(P(dd), None, P(wd), P(q1), M, N, K, None, 1, wt, S()) != 0
+
+
+def test_pwconv_with_producer_bn_relu6_matches_the_two_pass_path_hot():
+    test_pwconv_with_producer_bn_relu6_matches_the_two_pass_path((1111, 64, 256, 1), hot=True)
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2])
@@ -1503,7 +1629,7 @@ def test_weights_resident_gemm_equals_the_tile_kernel(M, N, K):
 
 @pytest.mark.parametrize("M,N,K", [(128 * 3, 128, 256), (128 * 41, 256, 256), (128 * 300, 256, 512), (128 * 531, 512, 512), (128 * 936, 512, 512), (128 * 7488, 128, 256),
                                    (128, 1024, 256), (128 * 9, 384, 512)])
-def test_weights_resident_data_gradient_with_batchnorm_backward_statistics(M, N, K):
+def test_weights_resident_data_gradient_with_batchnorm_backward_statistics(M, N, K, hot=False):
     """crnn_gemm_wres_bf16_bnstats: the data-gradient GEMM da = dq . W^T whose storer waves also take the statistics pass of the depthwise
     BatchNorm's backward.  da must be the very bits of crnn_gemm_wres_bf16; dgamma / dbeta / coef after
     crnn_bn_bwd_finalize must equal crnn_bn_bwd_ex's statistics pass on the same da and d up to the order of the fp32 partial sums, and an
@@ -1512,7 +1638,7 @@ def test_weights_resident_data_gradient_with_batchnorm_backward_statistics(M, N,
     rs = np.random.RandomState(M % 1000 + N + K)
     dq = _bf16_round(rs.normal(size=(M, K))); W = _bf16_round(rs.normal(size=(N, K)) * 0.1)
     d = _bf16_round(rs.normal(size=(M, N)) * 1.5 + 0.3)
-    gamma = rs.uniform(0.5, 1.5, N); beta = rs.normal(size=N) * 0.5 + 1.0
+    gamma, beta = _bn_affine(rs, N, hot, lambda: (rs.uniform(0.5, 1.5, N), rs.normal(size=N) * 0.5 + 1.0))
     mean = d.mean(0); var = d.var(0)
     inv = 1.0 / np.sqrt(var.astype(np.float32) + np.float32(1e-3))
     scale = (gamma * inv).astype(np.float32); shift = (beta - mean * gamma * inv).astype(np.float32)
@@ -1541,6 +1667,8 @@ def test_weights_resident_data_gradient_with_batchnorm_backward_statistics(M, N,
     # fp64 statistics of the device's own da
     g = da0.float().cpu().numpy().astype(np.float64)
     t = d.astype(np.float32) * scale + shift                                  # fp32 fma on the device; threshold ties are measure-zero here
+    if hot:
+        _assert_hot(t)
     live = (t > 0) & (t < 6)
     gy = np.where(live, g, 0.0)
     xhat = (d - mean.astype(np.float32).astype(np.float64)) * inv.astype(np.float64)
@@ -1549,6 +1677,10 @@ def test_weights_resident_data_gradient_with_batchnorm_backward_statistics(M, N,
     # shapes outside the rules are refused
     assert L().crnn_gemm_wres_bnstats_supported(M + 5, N, K) == -3 and L().crnn_gemm_wres_bnstats_supported(M, N, 128) == -3
     assert L().crnn_gemm_wres_bf16_bnstats(P(dqd), P(Wd), P(da), M, N, K, None, P(bnstate), P(parts), S()) == -2
+
+
+def test_weights_resident_data_gradient_with_batchnorm_backward_statistics_hot():
+    test_weights_resident_data_gradient_with_batchnorm_backward_statistics(128 * 3, 128, 256, hot=True)
 
 
 @pytest.mark.parametrize("M,N,K", [(128 * 3, 128, 64), (128 * 40, 256, 128), (128 * 700 + 0, 128, 64), (128 * 300, 512, 256), (128 * 530, 512, 512), (128, 1024, 64),
@@ -1756,13 +1888,18 @@ def test_streaming_tn_gemm_on_bf16_operands_equals_the_tile_kernel(M, N, K, lda,
 
 
 @pytest.mark.parametrize("M,N,K", [(128 * 5, 128, 64), (128 * 300 + 17, 256, 256), (128 * 700, 512, 512), (100, 128, 128)])
-def test_weights_resident_inference_conv_with_folded_batchnorm_equals_the_tile_kernel(M, N, K):
+def test_weights_resident_inference_conv_with_folded_batchnorm_equals_the_tile_kernel(M, N, K, hot=False):
     """crnn_pwconv_fwd_wres_folded (predict path: pointwise conv with the following BatchNorm + ReLU6 applied to the fp32 accumulators
     in the MFMA waves before the one rounding to bf16) against crnn_pwconv_fwd(out_bnstate) on the tile GEMM: bit for bit; and
     against the fp64 evaluation.  Ragged M, 1..4 channel slices, repeated launches."""
     rs = np.random.RandomState(M % 9973 + N + K)
     a = _bf16_round(np.abs(rs.normal(size=(M, K))) * 1.5); W = _bf16_round(rs.normal(size=(N, K)) * 0.2)
-    scale, shift = rs.normal(size=N) * 0.3 + 1.0, rs.normal(size=N) * 0.5 + 1.0
+    if hot:     # the folded BatchNorm applies to the accumulators a . W^T: their own mean and spread per channel put t at about N(3, 2^2)
+        acc = a @ W.T
+        scale, shift = _hot_scale_shift(rs, N, acc.mean(0), acc.std(0))
+        _assert_hot(acc * scale + shift)
+    else:
+        scale, shift = rs.normal(size=N) * 0.3 + 1.0, rs.normal(size=N) * 0.5 + 1.0
     st = dev(np.concatenate([rs.normal(size=N), rs.uniform(0.5, 2.0, size=N), scale, shift]))
     ad, Wd = _to_bf16_dev(a), _to_bf16_dev(W)
     y1 = torch.full((M + 2, N), 7.0, dtype=torch.bfloat16, device="cuda")
@@ -1778,8 +1915,13 @@ def test_weights_resident_inference_conv_with_folded_batchnorm_equals_the_tile_k
     assert_close(y1[:M].float().cpu().numpy(), ref, rtol=1e-2, atol=2e-2, what="folded conv vs fp64")
 
 
+@pytest.mark.parametrize("M,N,K", [(128 * 5, 128, 64), (100, 128, 128)])
+def test_weights_resident_inference_conv_with_folded_batchnorm_equals_the_tile_kernel_hot(M, N, K):
+    test_weights_resident_inference_conv_with_folded_batchnorm_equals_the_tile_kernel(M, N, K, hot=True)
+
+
 @pytest.mark.parametrize("M,N,K", [(128, 64, 128), (128 * 9, 128, 256), (128 * 40, 256, 256), (128 * 21, 512, 512), (128 * 1500, 128, 256), (128 * 7, 64, 128)])
-def test_three_plane_data_gradient_with_batchnorm_backward_statistics(M, N, K):
+def test_three_plane_data_gradient_with_batchnorm_backward_statistics(M, N, K, hot=False):
     """crnn_gemm_f32x3_bnstats (parity mode): the pointwise conv's data gradient da = dq . W^T as three-plane products whose epilogue also takes
     the statistics pass of the depthwise BatchNorm's backward.  da must be the very bits of crnn_gemm_f32x3; dgamma / dbeta / coef after
     crnn_bn_bwd_finalize_folded must equal crnn_bn_bwd_ex's statistics pass on the same da and d up to the order of the fp32 partial sums and an
@@ -1788,7 +1930,7 @@ def test_three_plane_data_gradient_with_batchnorm_backward_statistics(M, N, K):
     rs = np.random.RandomState(M % 1000 + N + K + 7)
     dq = rs.normal(size=(M, K)).astype(np.float32); W = (rs.normal(size=(N, K)) * 0.1).astype(np.float32)
     d = (rs.normal(size=(M, N)) * 1.5 + 0.3).astype(np.float32)
-    gamma = rs.uniform(0.5, 1.5, N); beta = rs.normal(size=N) * 0.5 + 1.0
+    gamma, beta = _bn_affine(rs, N, hot, lambda: (rs.uniform(0.5, 1.5, N), rs.normal(size=N) * 0.5 + 1.0))
     mean = d.astype(np.float64).mean(0); var = d.astype(np.float64).var(0)
     inv = 1.0 / np.sqrt(var.astype(np.float32) + np.float32(1e-3))
     scale = (gamma * inv).astype(np.float32); shift = (beta - mean * gamma * inv).astype(np.float32)
@@ -1817,6 +1959,8 @@ def test_three_plane_data_gradient_with_batchnorm_backward_statistics(M, N, K):
     assert torch.equal(dx1, dx2), "pass 2 alone differs from crnn_bn_bwd_ex"
     g = host(da0).astype(np.float64)
     t = d * scale + shift
+    if hot:
+        _assert_hot(t)
     live = (t > 0) & (t < 6)
     gy = np.where(live, g, 0.0)
     xhat = (d.astype(np.float64) - mean.astype(np.float32).astype(np.float64)) * inv.astype(np.float64)
@@ -1826,8 +1970,12 @@ def test_three_plane_data_gradient_with_batchnorm_backward_statistics(M, N, K):
     assert L().crnn_gemm_f32x3_bnstats(P(dqd), P(Wd), P(da), M, N, K, None, P(bnstate), P(parts), S()) == -2
 
 
+def test_three_plane_data_gradient_with_batchnorm_backward_statistics_hot():
+    test_three_plane_data_gradient_with_batchnorm_backward_statistics(128, 64, 128, hot=True)
+
+
 @pytest.mark.parametrize("M,K,N", [(128 * 40, 128, 256), (1000, 64, 128), (128 * 6, 512, 512), (128 * 3 + 5, 256, 64), (128 * 200, 64, 128)])
-def test_three_plane_gemms_apply_batchnorm_relu6_while_staging(M, K, N):
+def test_three_plane_gemms_apply_batchnorm_relu6_while_staging(M, K, N, hot=False):
     """crnn_pwconv_bnrelu6_fwd_f32x3 / crnn_pwconv_bnrelu6_wgrad_f32x3 (parity mode): the staging waves of the three-plane kernel apply
     ReLU6(d * scale + shift) to the raw fp32 items before the plane split.  Both must equal the unfused sequence -- crnn_bn_act_pool_drop_ex,
     then crnn_pwconv_fwd(bf16_products = 2) with its statistics / crnn_gemm_f32x3 mode 2 -- bit for bit: whole and ragged tiles, both tile
@@ -1835,9 +1983,11 @@ def test_three_plane_gemms_apply_batchnorm_relu6_while_staging(M, K, N):
     rs = np.random.RandomState(M % 1000 + N + K + 3)
     d = dev((rs.normal(size=(M, K)) * 1.5 + 0.4).astype(np.float32)); w = dev((rs.normal(size=(K, N)) * 0.1).astype(np.float32))
     g = dev(rs.normal(size=(M, N)).astype(np.float32))
-    st = dev(np.concatenate([rs.normal(size=K), rs.uniform(0.5, 2.0, size=K), rs.normal(size=K) * 0.3 + 1.0, rs.normal(size=K) * 0.5 + 0.5]).astype(np.float32))
+    st = _bnstate(rs, K, hot, 0.4, 1.5)
     a = zeros(M, K)
     ok(L().crnn_bn_act_pool_drop_ex(P(d), P(st), P(a), 1, 1, M, K, 1, 1, 0.0, 0, 0, 0, 0, S()))
+    if hot:     # the fused and the unfused sequence read the same ReLU6: the hot case also holds a against the host's clamp at both ends
+        assert_close(host(a), np.clip(_hot_replay(d, st, K), 0.0, 6.0), what="a vs the host's ReLU6")
     rows = L().crnn_pwconv_stat_rows(M)
     q0, q1 = zeros(M, N), torch.full((M + 2, N), 7.0, device="cuda"); p0, p1 = zeros(rows, 2, N), zeros(rows, 2, N)
     ok(L().crnn_pwconv_fwd(P(a), P(w), P(q0), M, N, K, P(p0), None, 2, 0, 0, 0, 0, S()))
@@ -1855,8 +2005,38 @@ def test_three_plane_gemms_apply_batchnorm_relu6_while_staging(M, K, N):
     assert_close(host(dw1), ref, rtol=1e-4, atol=1e-5 * np.abs(ref).max() + 1e-6, what="weight gradient vs fp64")
 
 
-def _bnstate(rs, C):
-    return dev(np.concatenate([rs.normal(size=C), rs.uniform(0.5, 2.0, size=C), rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 0.5]).astype(np.float32))
+def test_three_plane_gemms_apply_batchnorm_relu6_while_staging_hot():
+    test_three_plane_gemms_apply_batchnorm_relu6_while_staging(128 * 3 + 5, 256, 64, hot=True)
+
+
+def _bnstate(rs, C, hot=False, mean=0.0, std=1.0):
+    """mean, variance, scale, shift.  hot: scale and shift put t = d * scale + shift at about N(3, 2^2) for d about N(mean, std^2)."""
+    mv = [rs.normal(size=C), rs.uniform(0.5, 2.0, size=C)]
+    ss = _hot_scale_shift(rs, C, mean, std) if hot else (rs.normal(size=C) * 0.3 + 1.0, rs.normal(size=C) * 0.5 + 0.5)
+    return dev(np.concatenate(mv + list(ss)).astype(np.float32))
+
+
+def _hot_replay(d, st, C):
+    """t = d * scale + shift as the fp32 replay of the device's fma gives it, with the hot case's coverage asserted."""
+    sth = host(st).reshape(4, C)
+    t = host(d.float()).reshape(-1, C) * sth[2] + sth[3]
+    _assert_hot(t)
+    return t
+
+
+def _hot_bn_bwd_sum_gy(xh, st, g, ph, pw, rate, seed, layer):
+    """For the hot cases of tests that compare two device paths only: the pre-activations t = x * scale + shift as the fp32 replay gives them, and the fp64
+    sum over each channel of gy = g through dropout (the device's mask), max-pool (first maximum) and ReLU6's two-sided gate -- what dbeta must be.
+    -> t, sum gy, largest sum |gy|"""
+    B, H, W, C = xh.shape
+    sth = host(st).reshape(4, C)
+    t = xh.astype(np.float32) * sth[2] + sth[3]
+    _assert_hot(t, (ph, pw))
+    mk = zeros(B * (H // ph) * (W // pw) * C)
+    ok(L().crnn_dropout_mask(P(mk), mk.numel(), rate, seed, layer, S()))
+    r = np.clip(t.astype(np.float64), 0.0, 6.0)
+    gy = ops.relu6_bwd_from_out(r, ops.maxpool_bwd(r, g.astype(np.float64) * host(mk).reshape(g.shape), ph, pw))
+    return t, gy.sum((0, 1, 2)), np.abs(gy).sum((0, 1, 2)).max()
 
 
 @pytest.mark.parametrize("planes", [3, 2])
@@ -1902,14 +2082,14 @@ def test_resident_weight_plane_forward_equals_the_tile_kernel(M, K, N, planes):
 
 @pytest.mark.parametrize("planes", [2, 3])
 @pytest.mark.parametrize("M,N,K", [(32 * 9, 128, 256), (32 * 500, 128, 256), (32 * 41, 256, 256), (32 * 300, 256, 512), (32 * 40, 512, 512), (32 * 260, 512, 512), (32 * 8, 64, 512)])
-def test_resident_weight_plane_data_gradient_with_batchnorm_backward_statistics(M, N, K, planes):
+def test_resident_weight_plane_data_gradient_with_batchnorm_backward_statistics(M, N, K, planes, hot=False):
     """crnn_gemm_wres3_bnstats: da = dq . W^T with W's planes resident in registers, dq streamed once, and BatchNorm-1's backward statistics taken while the
     result is drained.  da: crnn_gemm_f32x3_bnstats / _f32x2_bnstats up to the order of the fp32 accumulation; dgamma / dbeta / coef
     after crnn_bn_bwd_finalize_folded equal the tile kernel's up to the order of the partial sums."""
     rs = np.random.RandomState(M % 1000 + N + K + 11 * planes)
     dq = dev(rs.normal(size=(M, K)).astype(np.float32)); W = dev((rs.normal(size=(N, K)) * 0.1).astype(np.float32))
     dh = (rs.normal(size=(M, N)) * 1.5 + 0.3).astype(np.float32); d = dev(dh)
-    gamma = rs.uniform(0.5, 1.5, N); beta = rs.normal(size=N) * 0.5 + 1.0
+    gamma, beta = _bn_affine(rs, N, hot, lambda: (rs.uniform(0.5, 1.5, N), rs.normal(size=N) * 0.5 + 1.0))
     mean = dh.astype(np.float64).mean(0); var = dh.astype(np.float64).var(0)
     inv = 1.0 / np.sqrt(var.astype(np.float32) + np.float32(1e-3))
     scale = (gamma * inv).astype(np.float32); shift = (beta - mean * gamma * inv).astype(np.float32)
@@ -1932,6 +2112,8 @@ def test_resident_weight_plane_data_gradient_with_batchnorm_backward_statistics(
     assert np.abs(host(da1[:M]) - ref).max() <= (3e-6 if planes == 3 else 3e-5) * sc
     g = host(da1[:M]).astype(np.float64)
     t = dh * scale + shift
+    if hot:
+        _assert_hot(t)
     gy = np.where((t > 0) & (t < 6), g, 0.0)
     xhat = (dh.astype(np.float64) - mean.astype(np.float32).astype(np.float64)) * inv.astype(np.float64)
     s1 = host(p1).astype(np.float64).sum(0)
@@ -1944,16 +2126,22 @@ def test_resident_weight_plane_data_gradient_with_batchnorm_backward_statistics(
     assert L().crnn_gemm_wres3_bnstats(P(dq), P(W), P(da1), M, N, K, planes, None, P(bnstate), P(p1), S()) == -2
 
 
+@pytest.mark.parametrize("planes", [2, 3])
+@pytest.mark.parametrize("M,N,K", [(32 * 9, 128, 256), (32 * 8, 64, 512)])
+def test_resident_weight_plane_data_gradient_with_batchnorm_backward_statistics_hot(M, N, K, planes):
+    test_resident_weight_plane_data_gradient_with_batchnorm_backward_statistics(M, N, K, planes, hot=True)
+
+
 @pytest.mark.parametrize("M,K,N,bn", [(32 * 7, 128, 128, True), (32 * 900, 128, 256, True), (32 * 64 * 3, 256, 256, True), (32 * 500, 256, 512, True), (32 * 1200, 512, 512, True),
                                         (32 * 333, 512, 128, False), (32 * 2, 128, 128, False)])
-def test_two_plane_weight_gradient_on_the_pixel_stream_equals_the_tile_kernel(M, K, N, bn):
+def test_two_plane_weight_gradient_on_the_pixel_stream_equals_the_tile_kernel(M, K, N, bn, hot=False):
     """crnn_pwconv_bnrelu6_wgrad_planes_stream (round 6, gemm_wgrad3.hip): the parity mode's pointwise weight gradient with two bf16 planes per operand on a pixel
     stream -- against crnn_pwconv_bnrelu6_wgrad_f32x2 (same planes and products, other reduction ranges: fp32 summation round-off) and the fp64 product of the
     activated operand (16 significant bits per factor: 3e-5 of the scale); ranges of one chunk to hundreds; without the BatchNorm transform too; repeated launches
     give the same bits."""
     rs = np.random.RandomState(M % 1000 + N + K)
     d = dev((rs.normal(size=(M, K)) * 1.5 + 0.4).astype(np.float32)); g = dev(rs.normal(size=(M, N)).astype(np.float32))
-    st = _bnstate(rs, K)
+    st = _bnstate(rs, K, hot, 0.4, 1.5)
     assert L().crnn_pwconv_wgrad_planes_stream_supported(M, N, K) == 0
     nb = L().crnn_pwconv_wgrad_planes_stream_scratch_bytes(M, N, K)
     assert 0 < nb <= 64 << 20
@@ -1966,6 +2154,8 @@ def test_two_plane_weight_gradient_on_the_pixel_stream_equals_the_tile_kernel(M,
         a = zeros(M, K)
         ok(L().crnn_bn_act_pool_drop_ex(P(d), P(st), P(a), 1, 1, M, K, 1, 1, 0.0, 0, 0, 0, 0, S()))
         ok(L().crnn_pwconv_bnrelu6_wgrad_f32x2(P(d), P(st), P(g), P(dw0), M, N, K, P(scr2), sb2, S()))
+        if hot:     # a is the operand of the fp64 product below: held against the host's clamp at both ends
+            assert_close(host(a), np.clip(_hot_replay(d, st, K), 0.0, 6.0), what="a vs the host's ReLU6")
     else:
         a = d
         ok(L().crnn_gemm_f32x2(2, P(d), P(g), P(dw0), K, N, M, K, N, N, None, 0, 0, 0, P(scr2), sb2, S()))
@@ -1976,6 +2166,10 @@ def test_two_plane_weight_gradient_on_the_pixel_stream_equals_the_tile_kernel(M,
     assert L().crnn_pwconv_wgrad_planes_stream_supported(M + 8, N, K) == -3 and L().crnn_pwconv_wgrad_planes_stream_supported(M, N, 64) == -3
     assert L().crnn_pwconv_wgrad_planes_stream_supported(M, 1024, 1152) == -3      # 72 tiles
     assert L().crnn_pwconv_bnrelu6_wgrad_planes_stream(P(d), P(st), P(g), P(dw1), M, N, K, P(scr), ctypes.c_size_t(1024), S()) == -3
+
+
+def test_two_plane_weight_gradient_on_the_pixel_stream_equals_the_tile_kernel_hot():
+    test_two_plane_weight_gradient_on_the_pixel_stream_equals_the_tile_kernel(32 * 7, 128, 128, True, hot=True)
 
 
 @pytest.mark.parametrize("rows,M,N,lda,ldb,ldc", [(52 * 256, 128, 1024, 128, 1024, 1024), (51 * 256, 256, 1024, 512, 1024, 1024), (51 * 64, 256, 1024, 256, 1024, 1028),
@@ -2369,7 +2563,7 @@ def test_ctc_and_decoders_at_the_size_limits_and_with_empty_labels():
 
 
 @pytest.mark.parametrize("storage", ["fp32", "bf16"])
-def test_inference_epilogues_fold_batchnorm_and_relu6(storage):
+def test_inference_epilogues_fold_batchnorm_and_relu6(storage, hot=False):
     """Inference forms (BN scale/shift known up front): crnn_dwconv3x3_bn_relu6_fwd and crnn_pwconv_fwd(out_bnstate)
     must equal conv -> BatchNorm(inference) -> ReLU6 done as separate oracle steps (utils.py:44-51)."""
     rs = np.random.RandomState(5)
@@ -2381,8 +2575,11 @@ def test_inference_epilogues_fold_batchnorm_and_relu6(storage):
     gam, bet = rs.uniform(0.5, 1.5, C), rs.normal(size=C) * 0.3
     mm, mv = rs.normal(size=C) * 0.2, rs.uniform(0.5, 2.0, C)
     st = zeros(4 * C)
-    ok(L().crnn_bn_infer_state(P(dev(mm)), P(dev(mv)), P(dev(gam)), P(dev(bet)), C, P(st), S()))
     ref_d = ops.dwconv_fwd(x, k)
+    if hot:
+        gam, bet = _hot_infer_affine(rs, ref_d.reshape(-1, C), mm, mv)
+        _assert_hot(ops.bn_infer_fwd(ref_d, gam, bet, mm, mv))
+    ok(L().crnn_bn_infer_state(P(dev(mm)), P(dev(mv)), P(dev(gam)), P(dev(bet)), C, P(st), S()))
     ref_a = ops.relu6_fwd(ops.bn_infer_fwd(ref_d, gam, bet, mm, mv))
     xd = _to_bf16_dev(x) if bf else dev(x)
     out = torch.zeros(B, H, W, C, dtype=torch.bfloat16 if bf else torch.float32, device="cuda")
@@ -2397,6 +2594,9 @@ def test_inference_epilogues_fold_batchnorm_and_relu6(storage):
     g2, b2 = rs.uniform(0.5, 1.5, N), rs.normal(size=N) * 0.3
     m2, v2 = rs.normal(size=N) * 0.2, rs.uniform(0.5, 2.0, N)
     st2 = zeros(4 * N)
+    if hot:
+        g2, b2 = _hot_infer_affine(rs, a @ Wp, m2, v2)
+        _assert_hot(ops.bn_infer_fwd((a @ Wp).reshape(B, H, W, N), g2, b2, m2, v2))
     ok(L().crnn_bn_infer_state(P(dev(m2)), P(dev(v2)), P(dev(g2)), P(dev(b2)), N, P(st2), S()))
     ref_x = ops.relu6_fwd(ops.bn_infer_fwd((a @ Wp).reshape(B, H, W, N), g2, b2, m2, v2)).reshape(-1, N)
     M_ = a.shape[0]
@@ -2410,6 +2610,11 @@ def test_inference_epilogues_fold_batchnorm_and_relu6(storage):
         assert_close(host(q), ref_x, rtol=1e-4, atol=1e-4, what="pw + folded BN + ReLU6 (fp32)")
     # statistics and the folded BatchNorm are mutually exclusive
     assert L().crnn_pwconv_fwd(P(out), P(dev(Wp)), P(q), M_, N, C, P(zeros(8, 2, N)), P(st2), 0, 0, 0, 0, 0, S()) != 0
+
+
+@pytest.mark.parametrize("storage", ["fp32", "bf16"])
+def test_inference_epilogues_fold_batchnorm_and_relu6_hot(storage):
+    test_inference_epilogues_fold_batchnorm_and_relu6(storage, hot=True)
 
 
 @pytest.mark.parametrize("storage", ["fp32", "bf16"])
@@ -2480,11 +2685,11 @@ def test_localisation_net_direct_conv_kernels(cin, H, W):
 
 
 @pytest.mark.parametrize("B,H,W,N,bf", [(3, 104, 36, 64, True), (256, 104, 36, 64, True), (5, 44, 36, 64, False), (2, 204, 36, 64, False), (1, 7, 5, 64, True)])
-def test_block1_kernels_with_batchnorm1_folded_in(B, H, W, N, bf):
+def test_block1_kernels_with_batchnorm1_folded_in(B, H, W, N, bf, hot=False, seed=None):
     """crnn_dwconv3x3_c1_fwd, crnn_pw1_bn_fwd, crnn_pw1_bn_bwd (round 4): block 1's single-channel depthwise conv with its own statistics, the outer
     product applying BatchNorm-1 + ReLU6 to d on the way in, and ONE backward pass over dq for weight gradient, data gradient and BatchNorm-1's backward
     statistics -- against the stand-alone kernels (outputs bit for bit; the statistics the same sums in another order) and the fp64 oracle."""
-    rs = np.random.RandomState(B + H + W)
+    rs = np.random.RandomState(B + H + W if seed is None else seed)
     x = rs.normal(size=(B, H, W, 1)); k = rs.normal(size=(3, 3, 1)); w = rs.normal(size=N) * 0.3
     xd, kd, wd = dev(x), dev(k), dev(w)
     M = B * H * W
@@ -2499,10 +2704,15 @@ def test_block1_kernels_with_batchnorm1_folded_in(B, H, W, N, bf):
     assert_close(host(parts[:rows]).sum(0), np.array([dn.sum(), (dn ** 2).sum()]), rtol=1e-4, atol=1e-3, what="statistics")
     assert_close(dn.reshape(B, H, W, 1), ops.dwconv_fwd(x, k), what="d vs oracle")
     # outer product of relu6(BN(d))
-    mean, var = dn.mean(), dn.var(); gamma, beta = 1.3, 1.1
+    mean, var = dn.mean(), dn.var(); gamma, beta = (float(v[0]) for v in _bn_affine(rs, 1, hot, lambda: ([1.3], [1.1])))
     scale = gamma / np.sqrt(var + 1e-3); st = dev(np.array([mean, var, scale, beta - mean * scale]))
     a = zeros(M)
     ok(L().crnn_bn_act_pool_drop_ex(P(d_ref), P(st), P(a), 1, 1, M, 1, 1, 1, 0.0, 0, 0, 0, 0, S()))
+    if hot:     # the kernels below are compared with each other: the hot cases also hold a, sum gy and the BatchNorm input gradient against the host's ReLU6
+        sth = host(st)
+        t = dn * sth[2] + sth[3]                                  # fp32 replay of the device's fma
+        _assert_hot(t)
+        assert_close(host(a), np.clip(t.astype(np.float64), 0.0, 6.0), what="a vs the host's ReLU6")
     dtq = 1 if bf else 0
     mk = (lambda *sh: torch.zeros(*sh, dtype=torch.bfloat16, device="cuda")) if bf else zeros
     srows = L().crnn_pwconv_stat_rows(M)
@@ -2532,6 +2742,12 @@ def test_block1_kernels_with_batchnorm1_folded_in(B, H, W, N, bf):
     ok(L().crnn_bn_bwd_finalize(P(bp), brow, 1, M, P(dg2), P(db2), P(coef2), S()))
     for u, v, nm in ((db2, db1, "sum gy"), (dg2, dg1, "sum gy xhat"), (coef2, coef1, "coefficients")):
         assert_close(host(u), host(v), rtol=2e-4, atol=2e-5 * max(1.0, float(v.abs().max())), what=nm)
+    if hot:
+        gy = np.where((t > 0) & (t < 6), host(da1).astype(np.float64), 0.0)
+        assert_close(host(db1), gy.sum(), rtol=1e-4, atol=1e-4 * np.abs(gy).sum(), what="sum gy vs fp64")
+        xhat = (dn.astype(np.float64) - mean) / np.sqrt(var + 1e-3)
+        gin_ref = scale * (gy - gy.mean() - xhat * (gy * xhat).mean())
+        assert_close(host(gin), gin_ref, rtol=1e-4, atol=1e-4 * np.abs(gin_ref).max(), what="BatchNorm-1 input gradient vs fp64")
     # the depthwise stage backwards in one kernel: BatchNorm-1 backward pass 2 (gin above) + weight gradient + data gradient
     dk1 = zeros(9); scw = zeros(max(L().crnn_dwconv_num_tiles(B, H, W) * 9, 1024 * 9) + 64)
     ok(L().crnn_dwconv3x3_wgrad_ex(P(xd), P(gin), P(dk1), P(scw), B, H, W, 1, 0, S()))
@@ -2546,6 +2762,12 @@ def test_block1_kernels_with_batchnorm1_folded_in(B, H, W, N, bf):
     dk3 = zeros(9)
     ok(L().crnn_dwconv3x3_c1_bwd(P(d_ref), P(da1), P(st), P(coef1), P(xd), P(kd), None, P(dk3), P(sc3), B, H, W, S()))
     assert torch.equal(dk3, dk2)
+
+
+@pytest.mark.parametrize("B,H,W,N,bf,seed", [(1, 7, 5, 64, True, 3), (5, 44, 36, 64, False, 2)])
+def test_block1_kernels_with_batchnorm1_folded_in_hot(B, H, W, N, bf, seed):
+    """One channel, so one gamma and one beta decide the whole case: the seeds are the first whose draw leaves 3 % of d's pre-activations at each end."""
+    test_block1_kernels_with_batchnorm1_folded_in(B, H, W, N, bf, hot=True, seed=seed)
 
 
 @pytest.mark.parametrize("B,H0,W0", [(7, 100, 32), (256, 100, 32), (3, 200, 32), (5, 40, 32), (2, 60, 48)])
@@ -2637,7 +2859,7 @@ def _split_planes(x, n_planes=3):
 @pytest.mark.parametrize("planes", [2, 3])
 @pytest.mark.parametrize("M,N,K", [(64 * 9, 128, 256), (64 * 250, 128, 256), (64 * 41, 256, 256), (64 * 150, 256, 512), (64 * 20, 512, 512), (64 * 700, 512, 512),
                                    (64 * 1, 128, 512), (64 * 66, 128, 512), (256 * 52 * 9, 512, 512), (256 * 52 * 18, 256, 256)])   # (the last two: blocks 6 / 7 and 4 at batch 256)
-def test_data_gradient_from_planes_equals_the_tile_kernel_bit_for_bit(M, N, K, planes):
+def test_data_gradient_from_planes_equals_the_tile_kernel_bit_for_bit(M, N, K, planes, hot=False):
     """crnn_gemm_pres_bnstats (round 6, gemm_pres.hip): da = dq . W^T with dq given as pre-split bf16 planes (LDS-DMA, no split in the GEMM), the planes of W
     resident in up to 512 registers per wave, one wave per SIMD.  The same planes, products and single fp32 accumulation chain per result as the tile kernel:
     da EQUALS crnn_gemm_f32x2 / _f32x3 (mode 1) bit for bit; the BatchNorm-1 backward statistics are the tile kernel's sums in another order (vs fp64);
@@ -2650,7 +2872,7 @@ def test_data_gradient_from_planes_equals_the_tile_kernel_bit_for_bit(M, N, K, p
     rs = np.random.RandomState(M % 1000 + N + K + 13 * planes)
     dq = dev((rs.normal(size=(M, K)) * 1e-2).astype(np.float32)); W = dev((rs.normal(size=(N, K)) * 0.1).astype(np.float32))
     dh = (rs.normal(size=(M, N)) * 1.5 + 0.3).astype(np.float32); d = dev(dh)
-    gamma = rs.uniform(0.5, 1.5, N); beta = rs.normal(size=N) * 0.5 + 1.0
+    gamma, beta = _bn_affine(rs, N, hot, lambda: (rs.uniform(0.5, 1.5, N), rs.normal(size=N) * 0.5 + 1.0))
     mean = dh.astype(np.float64).mean(0); var = dh.astype(np.float64).var(0)
     inv = 1.0 / np.sqrt(var.astype(np.float32) + np.float32(1e-3))
     scale = (gamma * inv).astype(np.float32); shift = (beta - mean * gamma * inv).astype(np.float32)
@@ -2672,6 +2894,8 @@ def test_data_gradient_from_planes_equals_the_tile_kernel_bit_for_bit(M, N, K, p
         assert torch.equal(da1[:M], da0), "da differs from the tile kernel: %g" % float((da1[:M] - da0).abs().max())
         g = host(da1[:M]).astype(np.float64)
         t = dh * scale + shift
+        if hot:
+            _assert_hot(t)
         gy = np.where((t > 0) & (t < 6), g, 0.0)
         xhat = (dh.astype(np.float64) - mean.astype(np.float32).astype(np.float64)) * inv.astype(np.float64)
         s1 = host(p1[:rows]).astype(np.float64).sum(0)
@@ -2690,16 +2914,22 @@ def test_data_gradient_from_planes_equals_the_tile_kernel_bit_for_bit(M, N, K, p
     assert L().crnn_gemm_pres_bnstats(P(pl), M * K, P(W), P(da1), M, N, K, 4, P(d), P(bnstate), P(p1), None, 0, 0, S()) == -2
 
 
+@pytest.mark.parametrize("planes", [2, 3])
+def test_data_gradient_from_planes_equals_the_tile_kernel_bit_for_bit_hot(planes):
+    """(The drain of gemm_pres.hip forms the gate as two selects some operations apart, t > 0 and then t < 6: both ends decided here.)"""
+    test_data_gradient_from_planes_equals_the_tile_kernel_bit_for_bit(64 * 9, 128, 256, planes, hot=True)
+
+
 @pytest.mark.parametrize("B,H,W,C,ph,pw,rate", [(2, 8, 12, 64, 1, 1, 0.0), (3, 8, 12, 128, 2, 2, 0.2), (2, 6, 20, 256, 1, 2, 0.2), (1, 9, 7, 32, 1, 1, 0.2), (2, 18, 52, 512, 1, 1, 0.0)])
 @pytest.mark.parametrize("planes", [2, 3])
-def test_batchnorm_backward_writes_its_input_gradient_as_planes(B, H, W, C, ph, pw, rate, planes):
+def test_batchnorm_backward_writes_its_input_gradient_as_planes(B, H, W, C, ph, pw, rate, planes, hot=False):
     """crnn_bn_bwd_planes_ex / crnn_bn_bwd_apply_planes_ex (round 6): the fp32 BatchNorm backward (through dropout, max-pool and ReLU6) with dx written as bf16
     planes -- the words crnn_split3_planes forms from the dx crnn_bn_bwd_ex writes, bit for bit; dgamma, dbeta and coef unchanged; nothing written behind the
     planes; bad arguments rejected."""
     rs = np.random.RandomState(B * 131 + H * 17 + C + ph + 3 * pw)
     Ho, Wo = H // ph, W // pw
     x = dev((rs.normal(size=(B, H, W, C)) * 1.2 + 0.5).astype(np.float32)); g = dev(rs.normal(size=(B, Ho, Wo, C)).astype(np.float32))
-    st = _bnstate(rs, C); gamma = dev(rs.uniform(0.5, 1.5, C).astype(np.float32))
+    st = _bnstate(rs, C, hot, 0.5, 1.2); gamma = dev(rs.uniform(0.5, 1.5, C).astype(np.float32))
     n = B * H * W * C
     chunks = L().crnn_bn_bwd_chunks(B * H * W)
     def run(planes_out):
@@ -2716,12 +2946,21 @@ def test_batchnorm_backward_writes_its_input_gradient_as_planes(B, H, W, C, ph, 
     _, dg1, db1, coef1 = run(out)
     assert torch.equal(out[:planes * n], ref[:planes * n]) and bool((out[planes * n:] == 0x4321).all())
     assert torch.equal(dg0, dg1) and torch.equal(db0, db1) and torch.equal(coef0, coef1)
+    if hot:     # two paths that gate alike agree whatever the gate is: the hot cases also hold dbeta = sum gy against the fp64 sum under ReLU6's gate
+        _, sgy, top = _hot_bn_bwd_sum_gy(host(x), st, host(g), ph, pw, rate, 77, 3)
+        assert_close(host(db1), sgy, rtol=1e-4, atol=1e-4 * top, what="dbeta vs fp64")
     out2 = torch.full((planes * n + 16,), 0x4321, dtype=torch.int16, device="cuda")
     ok(L().crnn_bn_bwd_apply_planes_ex(P(x), P(g), P(st), P(coef0), P(out2), n, planes, B, H, W, C, ph, pw, rate, 77, 3, S()))
     assert torch.equal(out2, out)
     assert L().crnn_bn_bwd_apply_planes_ex(P(x), P(g), P(st), P(coef0), P(out2), n, 4, B, H, W, C, ph, pw, rate, 77, 3, S()) == -2
     assert L().crnn_bn_bwd_apply_planes_ex(P(x), P(g), P(st), P(coef0), P(out2), n - 4, planes, B, H, W, C, ph, pw, rate, 77, 3, S()) == -2
     assert L().crnn_bn_bwd_apply_planes_ex(P(x), P(g), P(st), P(coef0), None, n, planes, B, H, W, C, ph, pw, rate, 77, 3, S()) == -2
+
+
+@pytest.mark.parametrize("B,H,W,C,ph,pw,rate", [(3, 8, 12, 128, 2, 2, 0.2), (1, 9, 7, 32, 1, 1, 0.2)])
+@pytest.mark.parametrize("planes", [2, 3])
+def test_batchnorm_backward_writes_its_input_gradient_as_planes_hot(B, H, W, C, ph, pw, rate, planes):
+    test_batchnorm_backward_writes_its_input_gradient_as_planes(B, H, W, C, ph, pw, rate, planes, hot=True)
 
 
 @pytest.mark.parametrize("M,K,N,bn", [(32 * 7, 128, 128, True), (32 * 900, 128, 256, True), (32 * 500, 256, 512, True), (32 * 1200, 512, 512, True), (32 * 333, 512, 128, False)])
@@ -2743,7 +2982,7 @@ def test_weight_gradient_stream_reads_the_planes_of_g(M, K, N, bn):
 
 @pytest.mark.parametrize("B,H,W,C,ph,pw,rate", [(3, 8, 12, 128, 2, 2, 0.2), (2, 6, 20, 256, 1, 2, 0.2), (2, 36, 52, 64, 2, 2, 0.0), (5, 18, 26, 24, 1, 2, 0.3)])
 @pytest.mark.parametrize("dtype", [0, 1])
-def test_pooled_batchnorm_backward_statistics_from_the_saved_window_maxima(B, H, W, C, ph, pw, rate, dtype):
+def test_pooled_batchnorm_backward_statistics_from_the_saved_window_maxima(B, H, W, C, ph, pw, rate, dtype, hot=False):
     """Pooled blocks, round 6: crnn_bn_act_pool_drop_qmax_ex writes the same y as crnn_bn_act_pool_drop_ex plus qmax = x at the first maximum of x * scale + shift
     over each pool window (checked against a numpy scan of the window in the kernel's order); crnn_bn_bwd_qmax_ex's statistics pass then reads one value per
     window instead of the window -- dgamma, dbeta, coef and dx equal crnn_bn_bwd_ex's BIT FOR BIT (fp32 and bf16 tensors, with the planes output too); other
@@ -2752,7 +2991,7 @@ def test_pooled_batchnorm_backward_statistics_from_the_saved_window_maxima(B, H,
     Ho, Wo = H // ph, W // pw
     xh = (rs.normal(size=(B, H, W, C)) * 1.2 + 0.5).astype(np.float32)
     if dtype == 1: xh = host(dev(xh).to(torch.bfloat16).float())           # bf16-representable values
-    st = _bnstate(rs, C); gamma = dev(rs.uniform(0.5, 1.5, C).astype(np.float32))
+    st = _bnstate(rs, C, hot, 0.5, 1.2); gamma = dev(rs.uniform(0.5, 1.5, C).astype(np.float32))
     tdt = torch.bfloat16 if dtype == 1 else torch.float32
     x = dev(xh).to(tdt); g = dev(rs.normal(size=(B, Ho, Wo, C)).astype(np.float32)).to(tdt)
     y0 = torch.zeros(B, Ho, Wo, C, device="cuda", dtype=tdt); y1 = torch.zeros_like(y0); qm = torch.full((B * Ho * Wo * C + 16,), 9.0, device="cuda", dtype=tdt)
@@ -2783,5 +3022,14 @@ def test_pooled_batchnorm_backward_statistics_from_the_saved_window_maxima(B, H,
     dgm, dbt, coef, pp = zeros(C), zeros(C), zeros(2 * C), zeros(chunks * 2 * C + 64); dx0 = torch.zeros(B, H, W, C, device="cuda", dtype=tdt)
     ok(L().crnn_bn_bwd_ex(P(x), P(g), P(st), P(gamma), P(dx0), P(dgm), P(dbt), P(pp), P(coef), B, H, W, C, ph, pw, rate, 77, 3, dtype, S()))
     assert torch.equal(dx0, a[0] if dtype == 1 else run(qm, 0)[0]) and torch.equal(dgm, b[1]) and torch.equal(dbt, b[2])
+    if hot:     # windows tied at exactly 6.0 after the clamp: the saved-maximum path gave the stand-alone path's sums above, and those are the fp64 sums
+        _, sgy, top = _hot_bn_bwd_sum_gy(xh, st, host(g.float()), ph, pw, rate, 77, 3)
+        assert_close(host(dbt), sgy, rtol=1e-4, atol=1e-4 * top, what="dbeta vs fp64")
     assert L().crnn_bn_act_pool_drop_qmax_ex(P(x), P(st), P(y1), P(qm), B, H, W, C, 1, 1, rate, 77, 3, dtype, dtype, S()) == -3
     assert L().crnn_bn_act_pool_drop_qmax_ex(P(x), P(st), P(y1), None, B, H, W, C, ph, pw, rate, 77, 3, dtype, dtype, S()) == -2
+
+
+@pytest.mark.parametrize("B,H,W,C,ph,pw,rate", [(3, 8, 12, 128, 2, 2, 0.2), (5, 18, 26, 24, 1, 2, 0.3)])
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_pooled_batchnorm_backward_statistics_from_the_saved_window_maxima_hot(B, H, W, C, ph, pw, rate, dtype):
+    test_pooled_batchnorm_backward_statistics_from_the_saved_window_maxima(B, H, W, C, ph, pw, rate, dtype, hot=True)
