@@ -26,6 +26,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Compute units of the current device; the MI355X's 256 when there is no device to ask (the host plans then still answer: tests, workspace sizing)
+// or when it reports fewer than at_least (8 where the plan divides by the 8 XCDs, 1 elsewhere).
+static inline int crnn_cu_count(int at_least) {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < at_least) cus = 256;
+  return cus;
+}
+
+#define BN_EPS 1e-3f   // BatchNormalization's epsilon (the Keras default); every kernel forms 1.0f / sqrtf(var + BN_EPS), the spelling of bn_bwd_kernel
+
 // Kernels with more than 64 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once PER DEVICE.  The latch is a
 // per-call-site bit mask over device ordinals (atomic: launchers may be called from several host threads, one per GPU); it caches a
 // device property, it is not state of the computation.

@@ -9,7 +9,6 @@
 #include "common.h"
 #include "stream_ops.h"
 
-#define BN_EPS 1e-3f
 constexpr int DW_NT = 256;   // threads per depthwise workgroup
 
 // VEC consecutive channels of one pixel, widened to fp32 (VEC = 1, 4 or 8; 8 = one 16-byte access of bf16 storage)

@@ -18,7 +18,6 @@
 namespace {
 
 constexpr int kNT = 256, kPXB = 3, kVN = 4, kCL = 16, kPT = kNT / kCL;   // 16 lanes x 4 bf16 channels = one 128-byte slab per pixel
-#define BN_EPS_F 1e-3f
 constexpr int kFusedWpe = 2;   // workgroups per CU the registers are budgeted for (profiles/r02_dw_bwd_fused_bench.txt)
 
 // (chunks travel as u32x4, a native vector: a uint4 struct copy becomes a memcpy through scratch)
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(kNT, kFusedWpe) void dw_bwd_fused_kernel(const bf16
     else if (a == 10) v = bnstate[3 * C + ch];
     else {
       float P, Q;
-      bn_bwd_pq(bnstate[2 * C + ch], coef[ch], coef[C + ch], bnstate[ch], 1.0f / sqrtf(bnstate[C + ch] + BN_EPS_F), P, Q);
+      bn_bwd_pq(bnstate[2 * C + ch], coef[ch], coef[C + ch], bnstate[ch], 1.0f / sqrtf(bnstate[C + ch] + BN_EPS), P, Q);
       v = a == 11 ? P : Q;
     }
     cst[i] = v;

@@ -26,7 +26,6 @@
 
 namespace {
 
-#define BN_EPS_F 1e-3f
 
 struct DbsParams {
   const unsigned char *d, *da, *xin; unsigned char* dx; const float *bnstate, *coef, *k; float* partials;
@@ -186,7 +185,7 @@ __global__ __launch_bounds__((STATS && !F32) ? 768 : 704, 1) void dw_bwd_stream_
     for (int e = 0; e < HP; ++e) {
       sc[e] = (f32x2_t){p.pro_bn[2 * p.C + chS + 2 * e], p.pro_bn[2 * p.C + chS + 2 * e + 1]};
       sh[e] = (f32x2_t){p.pro_bn[3 * p.C + chS + 2 * e], p.pro_bn[3 * p.C + chS + 2 * e + 1]};
-      iv[e] = (f32x2_t){1.0f / sqrtf(p.pro_bn[p.C + chS + 2 * e] + BN_EPS_F), 1.0f / sqrtf(p.pro_bn[p.C + chS + 2 * e + 1] + BN_EPS_F)};
+      iv[e] = (f32x2_t){1.0f / sqrtf(p.pro_bn[p.C + chS + 2 * e] + BN_EPS), 1.0f / sqrtf(p.pro_bn[p.C + chS + 2 * e + 1] + BN_EPS)};
       nm[e] = (f32x2_t){-p.pro_bn[chS + 2 * e] * iv[e].x, -p.pro_bn[chS + 2 * e + 1] * iv[e].y};
       st_s[e] = (f32x2_t){0.f, 0.f}; st_q[e] = (f32x2_t){0.f, 0.f};
     }
@@ -354,7 +353,7 @@ __global__ __launch_bounds__((STATS && !F32) ? 768 : 704, 1) void dw_bwd_stream_
       for (int e = 0; e < EPC / 2; ++e) {
         dsc[e] = (f32x2_t){p.pro_bn[2 * p.C + ch0 + 2 * e], p.pro_bn[2 * p.C + ch0 + 2 * e + 1]};
         dsh[e] = (f32x2_t){p.pro_bn[3 * p.C + ch0 + 2 * e], p.pro_bn[3 * p.C + ch0 + 2 * e + 1]};
-        div_[e] = (f32x2_t){1.0f / sqrtf(p.pro_bn[p.C + ch0 + 2 * e] + BN_EPS_F), 1.0f / sqrtf(p.pro_bn[p.C + ch0 + 2 * e + 1] + BN_EPS_F)};
+        div_[e] = (f32x2_t){1.0f / sqrtf(p.pro_bn[p.C + ch0 + 2 * e] + BN_EPS), 1.0f / sqrtf(p.pro_bn[p.C + ch0 + 2 * e + 1] + BN_EPS)};
         dnm[e] = (f32x2_t){-p.pro_bn[ch0 + 2 * e] * div_[e].x, -p.pro_bn[ch0 + 2 * e + 1] * div_[e].y};
         ds_s[e] = (f32x2_t){0.f, 0.f}; ds_q[e] = (f32x2_t){0.f, 0.f};
       }
@@ -465,7 +464,7 @@ __global__ __launch_bounds__((STATS && !F32) ? 768 : 704, 1) void dw_bwd_stream_
     const int ch = c0 + i;
     const float scv = p.bnstate[2 * p.C + ch];
     float P, Q;
-    bn_bwd_pq(scv, p.coef[ch], p.coef[p.C + ch], p.bnstate[ch], 1.0f / sqrtf(p.bnstate[p.C + ch] + BN_EPS_F), P, Q);
+    bn_bwd_pq(scv, p.coef[ch], p.coef[p.C + ch], p.bnstate[ch], 1.0f / sqrtf(p.bnstate[p.C + ch] + BN_EPS), P, Q);
     cst[i] = scv; cst[cw + i] = p.bnstate[3 * p.C + ch]; cst[2 * cw + i] = P; cst[3 * cw + i] = Q;
   }
   const float* cl = cst + oct * EPC;

@@ -165,8 +165,7 @@ extern "C" int crnn_gemm_nt_bf16(const void* X, const void* W, void* Y, int M, i
   NtParams p;
   p.X = (const bf16_t*)X; p.W = (const bf16_t*)W; p.Y = (bf16_t*)Y; p.M = M; p.N = N; p.K = K;
   p.stripes = cdiv(M, 128); p.kch = K / 64;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  const int cus = crnn_cu_count(1);
   const int grid = p.stripes < cus ? p.stripes : cus;
   // (256 channels per pass wherever N allows it; 128 + 3 slots lost: profiles/r02_gemm_nt_bench.txt)
   if (N % 256 == 0) {

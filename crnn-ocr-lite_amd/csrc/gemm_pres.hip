@@ -7,7 +7,8 @@
 // (profiles/r06_wres3_ablate.txt).  Here nothing is split in the GEMM and nothing passes through registers on the way in:
 //   * a workgroup is FOUR waves, one per SIMD, each with the whole register file of its SIMD (up to 512 registers): wave w keeps the planes of the 32 x K block
 //     W[slice * 128 + 32 w ..][0 .. K) as MFMA A-operand fragments for its whole life (planes * K / 4 registers: 256 for two planes at K = 512), split once
-//     in the prologue.  A slice is 128 result channels for every K <= 512: half the slices (and L2 -> LDS traffic) of gemm_wres3's K = 512 form;
+//     in the prologue.  A slice is 128 result channels for every K <= 512: half the slices (and L2 -> LDS traffic) of gemm_wres3's K = 512 form; the
+//     workgroups form the stripe grid of stream_grid.h ("The streamed GEMMs' two grids");
 //   * the pixel planes stream through an LDS ring by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave instruction, no VGPRs, no VALU): every wave issues its
 //     quarter of a stage (64 k x 32 PB pixels x planes) right after the stage barrier, R - 1 stages ahead; rows of 64 k = 128 B, 16-byte chunk c of row r at
 //     position c ^ ((r >> 1) & 7) (on the per-lane SOURCE address: the LDS image stays lane-linear): conflict-free ds_read_b128 fragment reads;
@@ -25,6 +26,7 @@
 // statistics are the same sums in another order (per-lane fp32 chains, crnn_bn_bwd_finalize_folded in double).
 #include "common.h"
 #include "stream_ops.h"
+#include "stream_grid.h"
 #include <type_traits>
 #include <utility>
 
@@ -38,7 +40,7 @@ struct PresParams {
   float* stats;                    // [rows][2][N]
   bf16_t* AP; long aps;            // NPA > 0: planes of a = ReLU6(d * scale + shift) [NPA][M][N]
   int M, N, K;
-  int stripes, S, Q, nxcd;
+  StripeGrid g;                    // stripes of 32 PB pixels x slices of 128 channels
 };
 
 constexpr int kMaxLaneTermsP = 4096;   // longest fp32 chain of a statistics lane
@@ -77,13 +79,9 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // ring [R][planes][PB][32][128 B] | transposition tiles [4 waves][PB][4 KiB] | d [4 waves][DB][PB][4 KiB]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wg = blockIdx.x;
-  const int x = wg % p.nxcd, jq = wg / p.nxcd;
-  const int slice = jq % p.S, q = jq / p.S;
-  const int step = p.Q * p.nxcd;
-  const int first = q * p.nxcd + x;
-  const int mine = first < p.stripes ? (p.stripes - first + step - 1) / step : 0;
-  const int srow = q * p.nxcd + x;
+  const StripeLane sl = stripe_lane(p.g);
+  const int slice = sl.slice, first = sl.first, step = sl.step, mine = sl.mine;
+  const int srow = first;                                       // one statistics row per stripe lane
   const int c8 = lane & 3, r16 = lane >> 2;                     // drain lane: channels 8 c8 .. + 7 of the wave's 32, rows r16 + 16 t
   const int chan = slice * 128 + 32 * wave + 8 * c8;
   if (mine <= 0) {                                             // no stripe: the statistics row must still read as zero
@@ -148,7 +146,7 @@ __global__ __launch_bounds__(256, OCC) void pres_dgrad_kernel(PresParams p) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     bmu[e] = p.bnstate[chan + e];
-    binv[e] = 1.0f / sqrtf(p.bnstate[p.N + chan + e] + 1e-3f);   // BN_EPS, the spelling of bn_bwd_kernel
+    binv[e] = 1.0f / sqrtf(p.bnstate[p.N + chan + e] + BN_EPS);
     bsc[e] = p.bnstate[2 * p.N + chan + e]; bsh[e] = p.bnstate[3 * p.N + chan + e];
   }
   float ss[8], qq[8];
@@ -370,23 +368,14 @@ bool pres_shape(int N, int K, int planes, PresShape& s) {
   return N >= 128 && N % 128 == 0 && N <= 1024;
 }
 void pres_geom(long M, int N, const PresShape& s, PresParams& p, int& grid) {
-  p.stripes = (int)(M / (32 * s.pb)); p.S = N / 128;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  p.nxcd = 8;
-  int per_xcd = cus / 8 * s.occ;
-  if (per_xcd < p.S) per_xcd = p.S;
-  p.Q = per_xcd / p.S;
-  const int need = cdiv(p.stripes, p.nxcd);
-  if (p.Q > need) p.Q = need;
-  grid = p.nxcd * p.Q * p.S;
+  grid = stripe_grid_plan(p.g, (int)(M / (32 * s.pb)), N / 128, crnn_cu_count(8), s.occ, false);
 }
 int pres_supported(long M, int N, int K, int planes) {
   PresShape s;
   if (M <= 0 || (planes != 2 && planes != 3) || !pres_shape(N, K, planes, s) || M % (32 * s.pb) != 0 || M * (long)(K > N ? K : N) >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
   PresParams p; int grid;
   pres_geom(M, N, s, p, grid);
-  const long per_wg = cdiv(p.stripes, p.Q * p.nxcd);
+  const long per_wg = cdiv(p.g.stripes, stripe_grid_lanes(p.g));
   if (per_wg * 2 * s.pb > kMaxLaneTermsP) return CRNN_ERR_UNSUPPORTED;
   return CRNN_OK;
 }
@@ -421,7 +410,7 @@ extern "C" int crnn_gemm_pres_stat_rows(long M, int N, int K, int planes) {
   PresShape s; pres_shape(N, K, planes, s);
   PresParams p; int grid;
   pres_geom(M, N, s, p, grid);
-  return p.Q * p.nxcd;
+  return stripe_grid_lanes(p.g);
 }
 // da[M][N] = dq[M][K] . w[N][K]^T from the planes of dq (dq_planes: plane pl of dq[m][k] at dq_planes[pl * plane_stride + m * K + k], bf16 words, the
 // words of crnn_split3_planes; planes = 2 | 3), w fp32 [N][K]; stat_partials [crnn_gemm_pres_stat_rows][2][N] = partial sums of gy and gy * xhat,

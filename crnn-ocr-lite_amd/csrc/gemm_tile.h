@@ -284,7 +284,7 @@ __device__ __forceinline__ void gemm_tile_epilogue(const GemmParams& p, f32x16 (
     const float4 mu = *reinterpret_cast<const float4*>(p.bnstate + gnb), va = *reinterpret_cast<const float4*>(p.bnstate + p.N + gnb);
     const float4 sc = *reinterpret_cast<const float4*>(p.bnstate + 2 * p.N + gnb), sh = *reinterpret_cast<const float4*>(p.bnstate + 3 * p.N + gnb);
     const float bmu[4] = {mu.x, mu.y, mu.z, mu.w}, bsc[4] = {sc.x, sc.y, sc.z, sc.w}, bsh[4] = {sh.x, sh.y, sh.z, sh.w};
-    const float binv[4] = {1.0f / sqrtf(va.x + 1e-3f), 1.0f / sqrtf(va.y + 1e-3f), 1.0f / sqrtf(va.z + 1e-3f), 1.0f / sqrtf(va.w + 1e-3f)};   // BN_EPS, the spelling of bn_bwd_kernel
+    const float binv[4] = {1.0f / sqrtf(va.x + BN_EPS), 1.0f / sqrtf(va.y + BN_EPS), 1.0f / sqrtf(va.z + BN_EPS), 1.0f / sqrtf(va.w + BN_EPS)};
     float bs[4] = {0.f, 0.f, 0.f, 0.f}, bq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int it = 0; it < 128 / RPI; ++it) {

@@ -13,12 +13,13 @@
 //     128 + 32 bf16 so that the transposing fragment reads (two ds_read_b64_tr_b16 per fragment) are conflict-free;
 //   * one raw s_barrier per chunk; the steady-state IO loop is branch-free so the wait-count insertion counts the outstanding
 //     loads exactly instead of draining them;
-//   * all tiles of one reduction range sit on one XCD (they read the same pixel rows: HBM sees them once); ranges are
-//     contiguous, the fp32 partial tiles go to scratch [range][K][N] and a fixed-order second stage sums them (deterministic).
+//   * the workgroups form the reduction-split grid of stream_grid.h ("The streamed GEMMs' two grids"): all tiles of one reduction range
+//     sit on one XCD, the fp32 partial tiles go to scratch [range][K][N] and a fixed-order second stage sums them (deterministic).
 // Same products as the tile kernel (bf16 operands, fp32 accumulation); the reduction is grouped differently (other range
 // boundaries), so the result agrees to fp32 summation round-off, not bit for bit.
 #include "common.h"
 #include "stream_ops.h"
+#include "stream_grid.h"
 
 namespace {
 
@@ -26,13 +27,9 @@ struct WgParams {
   const bf16_t* D; const bf16_t* G; float* part;     // d [M][K], g [M][N], partial tiles [nsplit][K][N]
   const float* scale; const float* shift;             // [K]
   int M, N, K;
-  int chunks;        // M / 64
-  int TI, TJ;        // output tiles along K (rows) and N (columns)
-  int nsplit;        // reduction ranges; grid = 8 * ceil(TI * TJ * nsplit / 8) workgroups, id -> (xcd, tile, range) below
-  int per;           // chunks per range (the last range may be shorter)
+  SplitGrid g;       // chunks of 64 pixels; tiles along K (rows) and N (columns)
   int lda, ldg;      // row strides of D and G in elements (bf16 convs: K and N)
-  int flat;          // more tiles than an XCD has CUs (round 5, dense1: 36): grid = tiles * nsplit, id -> (tile = id % tiles, range = id / tiles) -- a range's
-                     // tiles spread over the XCDs (one XCD would run 32 of them and then the other 4: twice the time, measured)
+  int flat;          // the grid's id -> (tile, range) mapping (stream_grid.h)
 };
 
 constexpr int kLd = 128 + 32;                 // bf16 row stride of a k-major operand stage (320 B)
@@ -66,15 +63,15 @@ __global__ __launch_bounds__(256 + 64 * NIO + (GDMA ? 64 * kLoaders : 0)) void p
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // kRing x (A stage | B stage)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // workgroup -> (xcd, local) -> (range, tile): the tiles of a range are neighbours on one XCD
+  // workgroup -> (tile, range): the id mapping of stream_grid.h, spelled here (a shared helper changed this kernel's vector code: profiles/stream_grid_refactor.txt)
   const int wg = blockIdx.x, x = wg & 7, loc = wg >> 3;
-  const int tiles = p.TI * p.TJ;
+  const int tiles = p.g.TI * p.g.TJ;
   const int lin = p.flat ? wg % tiles : loc % tiles, rloc = loc / tiles;   // tile, range index within this XCD
   const int split = p.flat ? wg / tiles : rloc * 8 + x;
-  if (split >= p.nsplit) return;
-  const int ti = lin / p.TJ, tj = lin % p.TJ;
-  const int c0 = split * p.per;
-  const int total = min(p.per, p.chunks - c0);                  // chunks of this range (> 0 by the host's choice of nsplit)
+  if (split >= p.g.nsplit) return;
+  const int ti = lin / p.g.TJ, tj = lin % p.g.TJ;
+  const int c0 = split * p.g.per;
+  const int total = min(p.g.per, p.g.chunks - c0);              // chunks of this range (> 0 by the host's choice of nsplit)
 
   if constexpr (GDMA) {
     if (wave >= 4 + NIO) {
@@ -267,22 +264,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_sum_kernel(const float* __restri
   pw_wgrad_sum_block(part, nsplit, total, out, N, ldc, blockIdx.x);
 }
 
-void wg_geom(long M, int N, int K, WgParams& p, int& grid) {
-  p.chunks = (int)(M / 64); p.TI = K / 128; p.TJ = N / 128;
-  const int tiles = p.TI * p.TJ;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  int ns = (cus / tiles) & ~7;                                  // one workgroup per CU, a multiple of 8 ranges (8 XCDs)
-  p.flat = tiles > cus / 8;
-  if (p.flat) ns = cus / tiles < 1 ? 1 : cus / tiles;           // more tiles than an XCD has CUs (dense1: 36): cus / tiles ranges, one workgroup per CU
-  else if (ns < 8) ns = 8;
-  while (ns > 8 && p.chunks / ns < 2 * kD) ns -= 8;             // a range is at least two pipeline depths long
-  if (ns > p.chunks) ns = p.chunks;                             // (tiny inputs: ranges of one chunk; some of the 8 XCD lanes stay empty)
-  p.nsplit = ns;
-  p.per = cdiv(p.chunks, ns);
-  p.nsplit = cdiv(p.chunks, p.per);                             // drop empty tail ranges
-  grid = p.flat ? p.nsplit * tiles : 8 * cdiv(p.nsplit, 8) * tiles;
-}
+void wg_geom(long M, int N, int K, WgParams& p, int& grid) { grid = split_grid_plan(p.g, p.flat, (int)(M / 64), K / 128, N / 128, crnn_cu_count(8), kD); }
 
 }  // namespace
 
@@ -295,14 +277,14 @@ extern "C" int crnn_pwconv_wgrad_stream_supported(long M, int N, int K) {
 extern "C" size_t crnn_pwconv_wgrad_stream_scratch_bytes(long M, int N, int K) {
   if (crnn_pwconv_wgrad_stream_supported(M, N, K) != CRNN_OK) return 0;
   WgParams p; int grid; wg_geom(M, N, K, p, grid);
-  return (size_t)p.nsplit * K * N * sizeof(float);
+  return (size_t)p.g.nsplit * K * N * sizeof(float);
 }
 namespace {
 template <bool F32, bool XF = true>
 int wg_launch(WgParams& p, long M, float* out, int ldc, float* scratch, size_t scratch_bytes, hipStream_t stream) {
   int grid;
   wg_geom(M, p.N, p.K, p, grid);
-  if ((size_t)p.nsplit * p.K * p.N * sizeof(float) > scratch_bytes) return CRNN_ERR_UNSUPPORTED;
+  if ((size_t)p.g.nsplit * p.K * p.N * sizeof(float) > scratch_bytes) return CRNN_ERR_UNSUPPORTED;
   if constexpr (!F32 && XF) {   // the pointwise convolutions' form (bf16 d with the BatchNorm transform, bf16 g): g by LDS-DMA from loader waves
     // (its one caller has checked what the DMA needs: g 16-byte aligned, N = ldg a multiple of 128)
     const int ldsd = kRing * kOp + kRingB * kOpB;
@@ -315,7 +297,7 @@ int wg_launch(WgParams& p, long M, float* out, int ldc, float* scratch, size_t s
   }
   CRNN_LAUNCH_CHECK();
   const long total = (long)p.K * p.N;
-  hipLaunchKernelGGL(pw_wgrad_sum_kernel, dim3(cdiv(total, 128)), dim3(256), 0, stream, scratch, p.nsplit, total, out, p.N, ldc);
+  hipLaunchKernelGGL(pw_wgrad_sum_kernel, dim3(cdiv(total, 128)), dim3(256), 0, stream, scratch, p.g.nsplit, total, out, p.N, ldc);
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;
 }
@@ -361,7 +343,7 @@ extern "C" int crnn_gemm_tn_bf16_stream_supported(int M, int N, long K) {
 extern "C" size_t crnn_gemm_tn_bf16_stream_scratch_bytes(int M, int N, long K) {
   if (crnn_gemm_tn_bf16_stream_supported(M, N, K) != CRNN_OK) return 0;
   WgParams p; int grid; wg_geom(K, N, M, p, grid);
-  return (size_t)p.nsplit * M * N * sizeof(float);
+  return (size_t)p.g.nsplit * M * N * sizeof(float);
 }
 extern "C" int crnn_gemm_tn_bf16_stream(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, long K, float* scratch,
                                         size_t scratch_bytes, hipStream_t stream) {
@@ -680,9 +662,7 @@ extern "C" int crnn_rnn_input_proj(const float* X, const void* Wf, const void* W
   p.X = X; p.W[0] = (const bf16_t*)Wf; p.W[1] = (const bf16_t*)Wb; p.Y[0] = Yf; p.Y[1] = Yb; p.bias[0] = bias_f; p.bias[1] = bias_b;
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldy = ldy;
   const int slabs2 = 2 * (N / 256);
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-  int groups = cus / slabs2; if (groups < 1) groups = 1;       // one workgroup per CU: (row groups) x (slabs of both directions)
+  int groups = crnn_cu_count(1) / slabs2; if (groups < 1) groups = 1;       // one workgroup per CU: (row groups) x (slabs of both directions)
   if (groups > M / 64) groups = M / 64;
   const int lds = (K / 64) * 256 * 128 + kNtsRing * 64 * 128;
   CRNN_LDS_ATTR(gemm_nt_f32_proj_kernel, 4 * 256 * 128 + kNtsRing * 64 * 128);

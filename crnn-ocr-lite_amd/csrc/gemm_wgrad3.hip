@@ -13,11 +13,12 @@
 //   * g given as planes (crnn_pwconv_bnrelu6_wgrad_planes_stream_gp: what the step runs): the IO waves handle d only, and FOUR loader waves bring the planes of g
 //     by LDS-DMA into a ring of their own (6 stages of 2 planes x 32 pixel rows x 256 B, unpadded, 16-byte chunks swizzled on the source address) -- the IO side
 //     is this kernel's bound (profiles/r06_wgrad3_ablate.txt);
-//   * one raw s_barrier per chunk, branch-free steady state; all tiles of one reduction range sit on one XCD; the fp32 partial tiles go to scratch
-//     [range][K][N] and a fixed-order second stage sums them (deterministic).
+//   * one raw s_barrier per chunk, branch-free steady state; the workgroups form the reduction-split grid of stream_grid.h ("The streamed GEMMs' two grids"); the
+//     fp32 partial tiles go to scratch [range][K][N] and a fixed-order second stage sums them (deterministic).
 // Same planes and products as the tile kernel; the reduction is grouped differently (other range boundaries): equal to fp32 summation round-off.
 #include "common.h"
 #include "stream_ops.h"
+#include "stream_grid.h"
 
 namespace {
 
@@ -26,9 +27,9 @@ struct Wg3Params {
   const unsigned short* GP; long gps;                 // GPL: g as bf16 planes [2][M][ldg] (hi, mid: the words of crnn_split3_pair), element stride between them
   const float* scale; const float* shift;             // [K] or null (plain operand)
   int M, N, K;
-  int chunks;        // M / 32
-  int TI, TJ, nsplit, per, lda, ldg;
-  int flat;          // more tiles than an XCD has CUs (dense1's weight gradient: 36): grid = tiles * nsplit, id -> (tile = id % tiles, range = id / tiles), as gemm_wgrad.hip
+  SplitGrid g;       // chunks of 32 pixels; tiles along K (rows) and N (columns)
+  int lda, ldg;
+  int flat;          // the grid's id -> (tile, range) mapping (stream_grid.h)
 };
 
 constexpr int kLd3 = 128 + 32;                // bf16 row stride of a k-major operand plane (320 B)
@@ -54,15 +55,15 @@ __global__ __launch_bounds__(GPL ? 512 + 64 * kLoaders3 : 512, GPL ? 1 : 2) void
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // kRing3 stages
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // workgroup -> (xcd, local) -> (range, tile): the tiles of a range are neighbours on one XCD
+  // workgroup -> (tile, range): the id mapping of stream_grid.h, spelled here (a shared helper changed this kernel's vector code: profiles/stream_grid_refactor.txt)
   const int wg = blockIdx.x, x = wg & 7, loc = wg >> 3;
-  const int tiles = p.TI * p.TJ;
-  const int lin = p.flat ? wg % tiles : loc % tiles, rloc = loc / tiles;
+  const int tiles = p.g.TI * p.g.TJ;
+  const int lin = p.flat ? wg % tiles : loc % tiles, rloc = loc / tiles;   // tile, range index within this XCD
   const int split = p.flat ? wg / tiles : rloc * 8 + x;
-  if (split >= p.nsplit) return;
-  const int ti = lin / p.TJ, tj = lin % p.TJ;
-  const int c0 = split * p.per;
-  const int total = min(p.per, p.chunks - c0);                  // chunks of this range (> 0 by the host's choice of nsplit)
+  if (split >= p.g.nsplit) return;
+  const int ti = lin / p.g.TJ, tj = lin % p.g.TJ;
+  const int c0 = split * p.g.per;
+  const int total = min(p.g.per, p.g.chunks - c0);              // chunks of this range (> 0 by the host's choice of nsplit)
 
   if constexpr (GPL) {
     if (wave >= 8) {
@@ -248,21 +249,7 @@ __global__ __launch_bounds__(256) void pw_wgrad3_sum_kernel(const float* __restr
   *reinterpret_cast<float4*>(out + (i / N) * ldc + i % N) = a;
 }
 
-void wg3_geom(long M, int N, int K, Wg3Params& p, int& grid) {
-  p.chunks = (int)(M / 32); p.TI = K / 128; p.TJ = N / 128;
-  const int tiles = p.TI * p.TJ;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  int ns = (cus / tiles) & ~7;                                  // one workgroup per CU, a multiple of 8 ranges (8 XCDs)
-  p.flat = tiles > cus / 8;
-  if (p.flat) ns = cus / tiles < 1 ? 1 : cus / tiles;           // (round 6: dense1's 36 feature tiles -- cus / tiles ranges, one workgroup per CU)
-  else if (ns < 8) ns = 8;
-  while (ns > 8 && p.chunks / ns < 2 * kD3) ns -= 8;            // a range is at least two pipeline depths long
-  if (ns > p.chunks) ns = p.chunks;
-  p.per = cdiv(p.chunks, ns);
-  p.nsplit = cdiv(p.chunks, p.per);                             // drop empty tail ranges
-  grid = p.flat ? p.nsplit * tiles : 8 * cdiv(p.nsplit, 8) * tiles;
-}
+void wg3_geom(long M, int N, int K, Wg3Params& p, int& grid) { grid = split_grid_plan(p.g, p.flat, (int)(M / 32), K / 128, N / 128, crnn_cu_count(8), kD3); }
 
 }  // namespace
 
@@ -274,7 +261,7 @@ extern "C" int crnn_pwconv_wgrad_planes_stream_supported(long M, int N, int K) {
 extern "C" size_t crnn_pwconv_wgrad_planes_stream_scratch_bytes(long M, int N, int K) {
   if (crnn_pwconv_wgrad_planes_stream_supported(M, N, K) != CRNN_OK) return 0;
   Wg3Params p; int grid; wg3_geom(M, N, K, p, grid);
-  return (size_t)p.nsplit * K * N * sizeof(float);
+  return (size_t)p.g.nsplit * K * N * sizeof(float);
 }
 namespace {
 template <bool XF, bool GPL>
@@ -296,12 +283,12 @@ int wg3_run(const float* d, const float* in_bnstate, const float* g, const void*
   p.scale = in_bnstate ? in_bnstate + 2L * K : nullptr; p.shift = in_bnstate ? in_bnstate + 3L * K : nullptr;
   p.M = (int)M; p.N = N; p.K = K; p.lda = lda; p.ldg = ldg;
   int grid; wg3_geom(M, N, K, p, grid);
-  if ((size_t)p.nsplit * K * N * sizeof(float) > scratch_bytes) return CRNN_ERR_UNSUPPORTED;
+  if ((size_t)p.g.nsplit * K * N * sizeof(float) > scratch_bytes) return CRNN_ERR_UNSUPPORTED;
   const int lds = g_planes ? kRing3 * kStageA3 + kRingB3 * kStageB3 : kRing3 * kStage3;
   if (in_bnstate) CRNN_TRY(g_planes ? (wg3_launch_kernel<true, true>(p, grid, lds, stream)) : (wg3_launch_kernel<true, false>(p, grid, lds, stream)));
   else CRNN_TRY(g_planes ? (wg3_launch_kernel<false, true>(p, grid, lds, stream)) : (wg3_launch_kernel<false, false>(p, grid, lds, stream)));
   const long total = (long)K * N;
-  hipLaunchKernelGGL(pw_wgrad3_sum_kernel, dim3(cdiv(total / 4, 256)), dim3(256), 0, stream, scratch, p.nsplit, total, dw, N, ldc);
+  hipLaunchKernelGGL(pw_wgrad3_sum_kernel, dim3(cdiv(total / 4, 256)), dim3(256), 0, stream, scratch, p.g.nsplit, total, dw, N, ldc);
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;
 }

@@ -10,8 +10,8 @@
 //     an LDS ring of R = 6 stages (128 pixels x 64 k = 16 KiB each) with global_load_lds (16 B per lane, no VGPR staging) under
 //     counted s_waitcnt vmcnt(N); up to 4 stages = 64 KiB per CU are in flight (16 MB over the chip against the ~8 MB that
 //     8 TB/s x 1 us of latency need);
-//   * the N/128 slices of one stripe run at the same time on CUs of the SAME XCD (workgroup id -> xcd = id % 8), so the
-//     stripe is read from HBM once and from that XCD's L2 by the other slices;
+//   * the workgroups form the stripe grid of stream_grid.h ("The streamed GEMMs' two grids"): the N/128 slices of one stripe run at the
+//     same time on CUs of the SAME XCD, so the stripe is read from HBM once and from that XCD's L2 by the other slices;
 //   * pixels are the MFMA B operand (D = W X^T): a lane holds 4 consecutive output channels of one pixel per register
 //     group, v_permlane32_swap pairs groups into 8 channels;
 //   * the MFMA waves do not store to global memory: issuing the 8 result stores of a stripe costs a wave ~0.8 us (the
@@ -27,16 +27,14 @@
 // results are bit-identical.
 #include "common.h"
 #include "stream_ops.h"
+#include "stream_grid.h"
 
 namespace {
 
 struct WresParams {
   const bf16_t* X; const bf16_t* W; bf16_t* Y;
   int M, N, K;
-  int stripes;   // ceil(M / 128)
-  int S;         // channel slices of 128 (N / 128)
-  int Q;         // stripes processed concurrently per XCD (workgroups per XCD / S)
-  int nxcd;      // XCDs the grid spans (grid = nxcd * Q * S)
+  StripeGrid g;  // stripes of 128 pixels x slices of 128 channels
   const float* cscale; const float* cshift;   // EPI instantiation: per-output-channel epilogue Y = ReLU6(acc * cscale[n] + cshift[n])
   // BNS instantiation (Y = the gradient w.r.t. a = ReLU6(BN(d)) of a depthwise-separable block): the storer waves also take the statistics
   // of that BatchNorm's backward pass, sum(gy) and sum(gy * xhat) per channel with gy = Y where 0 < d * scale + shift < 6, from the
@@ -166,7 +164,7 @@ __device__ __forceinline__ void wres_store_bnstats(const WresParams& p, const un
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     mu[e] = p.bnstate[ch0 + e];
-    inv[e] = 1.0f / sqrtf(p.bnstate[p.N + ch0 + e] + 1e-3f);   // BN_EPS, the spelling of bn_bwd_kernel
+    inv[e] = 1.0f / sqrtf(p.bnstate[p.N + ch0 + e] + BN_EPS);
     sc[e] = p.bnstate[2 * p.N + ch0 + e]; sh[e] = p.bnstate[3 * p.N + ch0 + e];
     ss[e] = 0.f; qq[e] = 0.f;
   }
@@ -259,17 +257,12 @@ __global__ __launch_bounds__(384 + 64 * NLW) void gemm_wres_kernel(WresParams p)
   unsigned char* const outs = smem + RR * kStage;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // workgroup -> (xcd, slice, stripe lane): consecutive ids go to consecutive XCDs
-  const int wg = blockIdx.x;
-  const int x = wg % p.nxcd, j = wg / p.nxcd;
-  const int slice = j % p.S, q = j / p.S;
-  const int step = p.Q * p.nxcd;                              // stripe stride between this workgroup's iterations
-  const int first = q * p.nxcd + x;
-  const int mine = first < p.stripes ? (p.stripes - first + step - 1) / step : 0;
+  const StripeLane sl = stripe_lane(p.g);
+  const int slice = sl.slice, first = sl.first, step = sl.step, mine = sl.mine;
   if (mine <= 0) {
     if constexpr (BNS) {                                      // no stripe: this workgroup's statistics rows must still read as zero
       if (wave >= 4 + NLW && lane < 16) {
-        const long row = (long)(q * p.nxcd + x) * 2 + (wave - 4 - NLW);
+        const long row = (long)first * 2 + (wave - 4 - NLW);
         float4* r0 = reinterpret_cast<float4*>(p.stats + (row * 2 + 0) * p.N + slice * 128 + lane * 8);
         float4* r1 = reinterpret_cast<float4*>(p.stats + (row * 2 + 1) * p.N + slice * 128 + lane * 8);
         r0[0] = r0[1] = r1[0] = r1[1] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -287,7 +280,7 @@ __global__ __launch_bounds__(384 + 64 * NLW) void gemm_wres_kernel(WresParams p)
   }
 
   if constexpr (BNS) {
-    if (wave >= 4 + NLW) { wres_store_bnstats<KCH>(p, outs, wave - 4 - NLW, lane, slice, first, step, mine, (q * p.nxcd + x) * 2 + (wave - 4 - NLW)); return; }
+    if (wave >= 4 + NLW) { wres_store_bnstats<KCH>(p, outs, wave - 4 - NLW, lane, slice, first, step, mine, first * 2 + (wave - 4 - NLW)); return; }
   }
   if (wave >= 4 + NLW) {
     // ------------------------------------------------------------------ storer waves: drain the staged stripes, a piece per stage
@@ -391,7 +384,7 @@ struct WresFwdParams {
   const float* scale; const float* shift;   // [K] each
   float* stats;                             // [rows][2][N] or null
   int M, N, K;
-  int stripes, S, Q, nxcd;
+  StripeGrid g;                             // stripes of 32 PB pixels x slices of 128 CB channels
 };
 constexpr int kRf = 3;                      // ring slots (the data in flight lives in the IO waves' registers)
 
@@ -417,14 +410,10 @@ __global__ __launch_bounds__(512) void gemm_wres_fwd_kernel(WresFwdParams p) {
   float* const tab = reinterpret_cast<float*>(outs + 2 * otile);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wg = blockIdx.x;
-  const int x = wg % p.nxcd, j = wg / p.nxcd;
-  const int slice = j % p.S, q = j / p.S;
-  const int step = p.Q * p.nxcd;
-  const int first = q * p.nxcd + x;
-  const int mine = first < p.stripes ? (p.stripes - first + step - 1) / step : 0;
+  const StripeLane sl = stripe_lane(p.g);
+  const int slice = sl.slice, first = sl.first, step = sl.step, mine = sl.mine;
   const int total = mine * KCH;
-  const int srow = (q * p.nxcd + x) * 4 + (wave - 4);          // this IO wave's partial-statistics row
+  const int srow = first * 4 + (wave - 4);                     // this IO wave's partial-statistics row
   if (mine <= 0) {                                             // no stripe: the statistics rows must still read as zero
     if (p.stats && wave >= 4 && lane < 16 * CB)
       for (int e = 0; e < 8; ++e) {
@@ -567,22 +556,8 @@ extern "C" int crnn_gemm_wres_supported(int N, int K) {
 
 // Y[M][N] (bf16) = X[M][K] (bf16, row stride K) . W[N][K]^T (bf16, row stride K), weights resident in registers.
 // One persistent workgroup per CU (512 threads: 4 MFMA waves + 2 LDS-DMA loader waves + 2 storer waves, 160 KiB of LDS).
-static int wres_geom(int M, int N, WresParams& p) {             // -> grid
-  p.stripes = cdiv(M, 128); p.S = N / 128;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-  p.nxcd = 8;
-  int per_xcd = cus / 8;                                       // workgroups per XCD: one per CU
-  if (p.S > per_xcd) {                                         // more slices than an XCD has CUs (round 5: dense1's data gradient, 36 slices of a 3.4 MB operand):
-    p.nxcd = cus / p.S < 1 ? 1 : cus / p.S;                    // one workgroup per (slice, stripe lane), at most one per CU -- the stripe lanes no longer
-    p.Q = 1;                                                   // coincide with XCDs, which only matters for operands that do not fit the L2s
-    if (p.nxcd > p.stripes) p.nxcd = p.stripes;
-    return p.nxcd * p.S;
-  }
-  p.Q = per_xcd / p.S;
-  const int need = cdiv(p.stripes, p.nxcd);                    // stripe lanes that have any work
-  if (p.Q > need) p.Q = need;
-  return p.nxcd * p.Q * p.S;
+static int wres_geom(int M, int N, WresParams& p) {             // -> grid (flat lanes when N / 128 exceeds an XCD's CUs: dense1's data gradient)
+  return stripe_grid_plan(p.g, cdiv(M, 128), N / 128, crnn_cu_count(1), 1, true);
 }
 static int gemm_wres_impl(const void* X, const void* W, void* Y, int M, int N, int K, const float* cscale, const float* cshift, hipStream_t stream,
                           const void* D = nullptr, const float* bnstate = nullptr, float* stats = nullptr, int pool = 1) {
@@ -636,7 +611,7 @@ extern "C" int crnn_gemm_wres_bnstats_rows(long M, int N, int K) {
   if (crnn_gemm_wres_bnstats_supported(M, N, K) != CRNN_OK) return 0;
   WresParams p;
   wres_geom((int)M, N, p);
-  return 2 * p.Q * p.nxcd;
+  return 2 * stripe_grid_lanes(p.g);
 }
 extern "C" int crnn_gemm_wres_bf16_bnstats(const void* X, const void* W, void* Y, long M, int N, int K, const void* d, const float* bnstate,
                                            float* stat_partials, hipStream_t stream) {
@@ -678,16 +653,7 @@ namespace {
 bool wres_fwd_wide(int N, int K) { return N % 256 == 0 && K >= 128 && K <= 256; }
 void wres_fwd_geom(long M, int N, int K, WresFwdParams& p, int& grid) {
   const bool wide = wres_fwd_wide(N, K);
-  p.stripes = cdiv(M, wide ? 64 : 128); p.S = N / (wide ? 256 : 128);
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-  p.nxcd = 8;
-  int per_xcd = cus / 8;
-  if (per_xcd < p.S) per_xcd = p.S;
-  p.Q = per_xcd / p.S;
-  const int need = cdiv(p.stripes, p.nxcd);
-  if (p.Q > need) p.Q = need;
-  grid = p.nxcd * p.Q * p.S;
+  grid = stripe_grid_plan(p.g, cdiv(M, wide ? 64 : 128), N / (wide ? 256 : 128), crnn_cu_count(1), 1, false);
 }
 template <int KCH, int CB, int PB>
 int launch_wres_fwd(const WresFwdParams& p, int grid, hipStream_t stream) {
@@ -709,7 +675,7 @@ extern "C" int crnn_pwconv_fwd_wres_rows(long M, int N, int K) {
   if (crnn_pwconv_fwd_wres_supported(M, N, K) != CRNN_OK) return 0;
   WresFwdParams p; int grid;
   wres_fwd_geom(M, N, K, p, grid);
-  return p.Q * p.nxcd * 4;
+  return stripe_grid_lanes(p.g) * 4;
 }
 // q[M][N] (bf16) = ReLU6(d * scale + shift)[M][K] . wT[N][K]^T with in_bnstate = [mean|var|scale|shift] of the BatchNorm on d
 // (as crnn_pwconv_bnrelu6_fwd with w_transposed = 1 and bf16 q: the same bf16 result bit for bit); stat_partials (may be NULL):

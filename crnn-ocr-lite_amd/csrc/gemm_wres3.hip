@@ -12,7 +12,7 @@
 //   * the pixels stream ONCE: four IO waves load the fp32 rows of a 32 PB-pixel stripe (64 k per stage; registers, D stages ahead), apply
 //     ReLU6(x * scale[k] + shift[k]) (forward: the arithmetic of bn_act_pool_drop_kernel, bit for bit), split into planes and write them to a
 //     three-slot LDS ring (rows of 64 k = 128 B per plane, 16-byte chunk c of row r at position c ^ ((r >> 1) & 7): conflict-free ds_read_b128
-//     fragment reads); the slices of a stripe run at the same time on CUs of one XCD, so HBM is read once and the other slices hit that XCD's L2;
+//     fragment reads); the workgroups form the stripe grid of stream_grid.h ("The streamed GEMMs' two grids"): HBM is read once, the other slices of a stripe hit their XCD's L2;
 //   * the MFMA waves leave a finished stripe as fp32 in one of two LDS staging tiles; the IO waves drain it to global memory in 16-byte pieces spread
 //     over the stages of the next stripe (fully coalesced rows) and take the statistics from the same registers: a lane owns four channels over the
 //     whole launch, one partial row per IO wave and stripe lane;
@@ -23,6 +23,7 @@
 // The statistics are the same sums in another order (per-lane fp32 chains of at most kMaxLaneTerms terms, then crnn_bn_finalize / crnn_bn_bwd_finalize in double).
 #include "common.h"
 #include "stream_ops.h"
+#include "stream_grid.h"
 #include <type_traits>
 
 namespace {
@@ -35,7 +36,7 @@ struct W3Params {
   float* stats;                    // [rows][2][N] partial statistics (may be null in MODE 0)
   const float* D; const float* bnstate;     // MODE 1: d [M][N]; [mean | var | scale | shift] x N
   int M, N, K;
-  int stripes, S, Q, nxcd;
+  StripeGrid g;                    // stripes of 32 PB pixels x slices of 128 / KHN channels
 };
 
 constexpr int kMaxLaneTerms = 4096;   // longest fp32 chain of a statistics lane (rows per lane and launch); longer launches take the tile kernel
@@ -202,15 +203,11 @@ __global__ __launch_bounds__(512) void gemm_wres3_kernel(W3Params p) {
   float* const tab = reinterpret_cast<float*>(wlo + (WL ? 4 * KST * (4 / KHN) * 1024 : 0));
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wg = blockIdx.x;
-  const int x = wg % p.nxcd, jq = wg / p.nxcd;
-  const int slice = jq % p.S, q = jq / p.S;
-  const int step = p.Q * p.nxcd;
-  const int first = q * p.nxcd + x;
-  const int mine = first < p.stripes ? (p.stripes - first + step - 1) / step : 0;
+  const StripeLane sl = stripe_lane(p.g);
+  const int slice = sl.slice, first = sl.first, step = sl.step, mine = sl.mine;
   const int total = mine * KST;
   const int tio = tid - 256;
-  const int srow = (q * p.nxcd + x) * 4 + (wave - 4);          // this IO wave's partial-statistics row
+  const int srow = first * 4 + (wave - 4);                     // this IO wave's partial-statistics row
   const int pc = tio % NCH, prow = tio / NCH;                   // IO lane: staging-tile piece pc (4 channels) of rows prow + RSTEP t
   if (mine <= 0) {                                             // no stripe: the statistics rows must still read as zero
     if (p.stats && wave >= 4 && lane < NCH) {
@@ -290,7 +287,7 @@ __global__ __launch_bounds__(512) void gemm_wres3_kernel(W3Params p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       bmu[e] = p.bnstate[ch + e];
-      binv[e] = 1.0f / sqrtf(p.bnstate[p.N + ch + e] + 1e-3f);   // BN_EPS, the spelling of bn_bwd_kernel
+      binv[e] = 1.0f / sqrtf(p.bnstate[p.N + ch + e] + BN_EPS);
       bsc[e] = p.bnstate[2 * p.N + ch + e]; bsh[e] = p.bnstate[3 * p.N + ch + e];
     }
   }
@@ -389,23 +386,14 @@ bool w3_shape(int N, int K, W3Shape& s) {
   return N >= ns && N % ns == 0 && N <= 1024;
 }
 void w3_geom(long M, int N, const W3Shape& s, W3Params& p, int& grid) {
-  p.stripes = (int)(M / (32 * s.pb)); p.S = N / (128 / s.khn);
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  p.nxcd = 8;
-  int per_xcd = cus / 8;
-  if (per_xcd < p.S) per_xcd = p.S;
-  p.Q = per_xcd / p.S;
-  const int need = cdiv(p.stripes, p.nxcd);
-  if (p.Q > need) p.Q = need;
-  grid = p.nxcd * p.Q * p.S;
+  grid = stripe_grid_plan(p.g, (int)(M / (32 * s.pb)), N / (128 / s.khn), crnn_cu_count(8), 1, false);
 }
 int w3_supported(long M, int N, int K) {
   W3Shape s;
   if (M <= 0 || !w3_shape(N, K, s) || M % (32 * s.pb) != 0 || M * (long)(K > N ? K : N) >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
   W3Params p; int grid;
   w3_geom(M, N, s, p, grid);
-  const long per_wg = cdiv(p.stripes, p.Q * p.nxcd);          // stripes of the busiest workgroup
+  const long per_wg = cdiv(p.g.stripes, stripe_grid_lanes(p.g));   // stripes of the busiest workgroup
   const int nch = (128 / s.khn) / 4;
   if (per_wg * (32 * s.pb * nch / 256) > kMaxLaneTerms) return CRNN_ERR_UNSUPPORTED;
   return CRNN_OK;
@@ -444,7 +432,7 @@ extern "C" int crnn_gemm_wres3_stat_rows(long M, int N, int K) {
   W3Shape s; w3_shape(N, K, s);
   W3Params p; int grid;
   w3_geom(M, N, s, p, grid);
-  return p.Q * p.nxcd * 4;
+  return stripe_grid_lanes(p.g) * 4;
 }
 // q[M][N] = ReLU6(d * scale + shift)[M][K] . w[K][N]   (in_bnstate = [mean|var|scale|shift] x K of the BatchNorm on d), planes = 3 | 2 bf16 planes per
 // operand; stat_partials (may be NULL): [crnn_gemm_wres3_stat_rows(M, N, K)][2][N] column sums / sums of squares of q.

@@ -1238,7 +1238,7 @@ extern "C" int crnn_bn_update(const crnn_config* cfg, float* bn_mean, float* bn_
       cum += C;
     }
   tab.cum[14] = cum;
-  hipLaunchKernelGGL(bn_moving_kernel, dim3(cdiv(cum, 256)), dim3(256), 0, stream, tab, bn_mean, bn_var, ws, cum, 0.99f, 1e-3f);
+  hipLaunchKernelGGL(bn_moving_kernel, dim3(cdiv(cum, 256)), dim3(256), 0, stream, tab, bn_mean, bn_var, ws, cum, 0.99f, BN_EPS);
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;
 }

@@ -155,8 +155,7 @@ __device__ __forceinline__ bool cluster_shares_xcd(unsigned char* xbuf, int cl, 
 // 512-thread workgroups share a CU only below 128 VGPRs, and several instantiations (wide fp32 tiles) need more.  A grid sized past
 // what is resident would stall every cluster wait for its 2 s bound.
 inline int resident_cap(size_t lds_bytes, int threads, const void* fn) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  const int cus = crnn_cu_count(1);
   int per_cu = (lds_bytes * 2 <= 160 * 1024) ? 2 : 1;
   if (threads * per_cu > 1024) per_cu = 1;
   if (fn && per_cu > 1) {

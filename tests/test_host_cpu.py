@@ -232,6 +232,31 @@ def test_workspace_plan_and_block_output_fusion_equal_the_recorded_plan():
     assert all(r[0] > 0 for r in got) and any(r[1] for r in got) and any(not r[1] for r in got)
 
 
+def test_streamed_gemm_grid_plans_equal_the_recorded_plans():
+    """Host arithmetic only: what the streamed pointwise GEMMs' plans answer -- supported / refused, partial-statistics rows (a function of the stripe
+    grid: XCDs x stripe lanes) and scratch bytes (a function of the reduction-split grid: ranges) -- equals tests/golden/stream_grid_plan.json over the
+    CRNN's pointwise shapes at batch 8 and 256, dense1's 36-tile case, single-stripe and few-stripe M and refused shapes, at the 256-CU fallback.  The
+    grids are planned in one place (csrc/stream_grid.h); no launch may change size because of where its plan is written."""
+    import importlib.util
+    gold_dir = os.path.join(os.path.dirname(__file__), "golden")
+    spec = importlib.util.spec_from_file_location("make_stream_grid_plan", os.path.join(gold_dir, "make_stream_grid_plan.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    gold = json.load(open(os.path.join(gold_dir, "stream_grid_plan.json")))
+    assert gold["ms"] == gen.MS and gold["nk"] == [list(s) for s in gen.NK] and gold["tn"] == [list(s) for s in gen.TN]
+    got, want = gen.records(native.LIB_PATH), gold["records"]
+    assert list(got) == list(want) and len(got) == len(gen.NK) + len(gen.MS) * len(gen.NK) * 12 + 2 * len(gen.TN)
+    bad = [(k, got[k], want[k]) for k in want if got[k] != want[k]]
+    assert not bad, "%d plan values differ, first: %s" % (len(bad), bad[:3])
+    # the recording covers what it is meant to: accepted and refused shapes of every entry point, a single stripe lane, dense1's 7 ranges of 36 tiles
+    for name in ("gemm_wres_bnstats_rows", "pwconv_fwd_wres_rows", "gemm_wres3_stat_rows", "gemm_pres_stat_rows p2", "gemm_pres_stat_rows p3",
+                 "pwconv_wgrad_stream_scratch_bytes", "pwconv_wgrad_planes_stream_scratch_bytes", "gemm_tn_bf16_stream_scratch_bytes"):
+        vals = [v for k, v in want.items() if k.startswith(name + " ")]
+        assert any(v == 0 for v in vals) and any(v > 0 for v in vals), name
+    assert want["gemm_pres_stat_rows p2 M128 N128 K256"] == 8 and want["gemm_wres_bnstats_rows M5120 N128 K256"] == 2 * 40
+    assert want["gemm_tn_bf16_stream_scratch_bytes M4608 N128 K13312"] == 7 * 4608 * 128 * 4
+
+
 def test_row_stream_kernels_keep_their_row_loops_spill_free():
     """The bf16 row-stream kernels sit at their 168-register ceiling; a harmless-looking edit (an address spelled with one multiplication instead of two)
     once put a 16-byte spill into the depthwise-stage backward's row loop and cost the kernel 22 %.  hipcc cross-compiles gfx950 without a GPU: no
@@ -296,7 +321,7 @@ def test_native_sources_read_no_environment_and_have_no_experiment_hooks():
     csrc/ calls getenv or carries the run-time knobs of the old experiment builds (crnn_knob, CRNN_EXPERIMENT_HOOKS)."""
     csrc = os.path.join(os.path.dirname(native.LIB_PATH), "csrc")
     files = sorted(os.listdir(csrc))
-    assert "common.h" in files and "stream_ops.h" in files and len([f for f in files if f.endswith(".hip")]) >= 29
+    assert "common.h" in files and "stream_ops.h" in files and "stream_grid.h" in files and len([f for f in files if f.endswith(".hip")]) >= 29
     bad = []
     for name in files:
         path = os.path.join(csrc, name)
