@@ -63,7 +63,7 @@ __device__ __forceinline__ float hs_grad_from_out(float a) { return (a > 0.f && 
 // BatchNorm backward, second pass, one element: dx = scale * (gy - c1 - xhat * c2) with c1 = mean(gy), c2 = mean(gy * xhat),
 // xhat = (x - mean) * inv, evaluated as two fused multiply-adds on per-channel constants:
 //     dx = fma(x, P, fma(gy, scale, Q)),   P = -scale * c2 * inv,   Q = scale * c2 * inv * mean - scale * c1.
-// One spelling (explicit fma, no compiler contraction) shared by the stand-alone pass (conv.hip) and the kernel that applies it
+// One spelling (explicit fma, no compiler contraction) shared by the stand-alone pass (batchnorm.hip) and the kernel that applies it
 // while it fills its tiles (conv_bwd_fused.hip), so both produce the same bits; 2 instead of 5 VALU operations per element is what
 // the fused kernel (VALU-bound) cares about.
 __device__ __forceinline__ void bn_bwd_pq(float sc, float c1, float c2, float mu, float inv, float& P, float& Q) {

@@ -1,7 +1,7 @@
 // Depthwise 3x3 convolution (reference utils.py:44, DepthwiseConv2D(3x3, padding='same', no bias)) of a bf16 NHWC map as a ROW STREAM:
 //     out[n][y][x][c] = sum_{i,j} k[3i+j][c] * in[n][y+i-1][x+j-1][c]      (+ BatchNorm statistics of out, or the folded BN + ReLU6)
 //
-// The halo-tile kernel (conv.hip) alternates "fill a tile" and "compute it" inside a workgroup and relies on three workgroups per
+// The halo-tile kernel (dwconv_tile.hip) alternates "fill a tile" and "compute it" inside a workgroup and relies on three workgroups per
 // CU to overlap the two; its waves are parked a third of the time.  Here one workgroup walks a band of image rows top to bottom:
 //   * a LOADER wave puts whole rows (all channels: W*C*2 contiguous bytes, 9 KiB for every block of the CRNN) into an LDS ring with
 //     global_load_lds (16 B per lane, no VGPR staging) D rows ahead, under a counted s_waitcnt vmcnt(N);

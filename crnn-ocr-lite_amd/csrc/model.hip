@@ -199,7 +199,7 @@ Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
     const bool dws = dtd == CRNN_BF16 && !dw_tile && crnn_dwconv_fwd_stream_supported(B, H, W, ci) == CRNN_OK;
     const int slab = (dtd == CRNN_BF16) ? 64 : 32;
     const bool one = ci == 1 && dtd == CRNN_F32;                                               // block 1: an outer product, not a GEMM
-    const bool blk1 = one && !(fl & CRNN_FLAG_BLOCK1_KERNELS) && c->imgw + 4 <= 255;          // ... with BatchNorm-1 folded into the neighbouring kernels (conv.hip)
+    const bool blk1 = one && !(fl & CRNN_FLAG_BLOCK1_KERNELS) && c->imgw + 4 <= 255;          // ... with BatchNorm-1 folded into the neighbouring kernels (block1.hip)
     const bool wres_ok = b.pwT_off >= 0 && dtq == CRNN_BF16 && !tile_gemms;
     // ---- inference: BatchNorm + ReLU6 fold into the conv that feeds them; a pooled block on bf16 maps pools in the GEMM epilogue too (groups of 2 | 4
     // consecutive rows; for the (2,2) window the depthwise row stream writes its rows in window-major order)
@@ -454,7 +454,7 @@ int gemm32(const Ctx& c, int mode, const float* A, const float* B, float* C, int
 }
 
 int colsum(const Ctx& c, const float* x, long M, int C, int ld, float* out) {
-  CRNN_TRY(crnn_colreduce(x, c.partials(), M, C, ld, 1, c.s));
+  CRNN_TRY(crnn_colreduce_ex(x, c.partials(), M, C, ld, 1, CRNN_F32, c.s));
   return crnn_partials_sum(c.partials(), crnn_colreduce_chunks(M), C, out, 1.f, c.s);
 }
 

@@ -680,13 +680,8 @@ int crnn_dwconv_bwd_stream_pro_supported_ex(int B, int H, int W, int C, int dtyp
 int crnn_dwconv3x3_bwd_stream_pro_ex(const void* d, const void* da, const float* bnstate, const float* coef, const void* q, const float* pro_bnstate,
                                      float rate, const void* keep, const float* k, void* dx, float* dk, float* scratch, float* bn2_stat_partials,
                                      int B, int H, int W, int C, int dtype, crnn_stream_t stream);
-int crnn_dwconv3x3_fwd(const float* x, const float* k, float* out, float* stat_partials, int B, int H, int W, int C,
-                       int flip, crnn_stream_t stream);
-int crnn_dwconv3x3_wgrad(const float* x, const float* g, float* dk, float* scratch, int B, int H, int W, int C,
-                         crnn_stream_t stream);
-/* column reductions of a [M][C] matrix (sum / sum+sumsq) and their second stage */
+/* column reductions of a [M][C] matrix (sum / sum+sumsq: crnn_colreduce_ex) and their second stage */
 int crnn_colreduce_chunks(long M);
-int crnn_colreduce(const float* x, float* partials, long M, int C, int ld, int nv, crnn_stream_t stream);
 int crnn_partials_sum(const float* partials, int nparts, int n, float* out, float scale, crnn_stream_t stream);
 /* BatchNormalization(axis=-1, eps 1e-3) (utils.py:45,48): bnstate = [mean|var|scale|shift] */
 int crnn_bn_finalize(const float* partials, int nparts, int C, long n, const float* gamma, const float* beta,
@@ -703,13 +698,7 @@ int crnn_bn_infer_state(const float* mmean, const float* mvar, const float* gamm
 int crnn_bn_infer_state_batch(int n, const float* const* mmean, const float* const* mvar, const float* const* gamma, const float* const* beta,
                               const int* C, float* const* bnstate, crnn_stream_t stream);
 int crnn_bn_act(const float* x, const float* bnstate, float* y, long M, int C, crnn_stream_t stream);
-/* y = Dropout(MaxPool(ReLU6(BN(x))))  (utils.py:45-56) */
-int crnn_bn_act_pool_drop(const float* x, const float* bnstate, float* y, int B, int H, int W, int C, int ph, int pw,
-                          float rate, uint64_t seed, uint32_t layer, crnn_stream_t stream);
 int crnn_bn_bwd_chunks(long M);
-int crnn_bn_bwd(const float* x, const float* g, const float* bnstate, const float* gamma, float* dx, float* dgamma,
-                float* dbeta, float* scratch_partials, float* coef, int B, int H, int W, int C, int ph, int pw,
-                float rate, uint64_t seed, uint32_t layer, crnn_stream_t stream);
 int crnn_add(const float* a, const float* b, float* o, long n, crnn_stream_t stream);
 int crnn_dropout(const float* x, float* y, long rows, int C, int ldx, int ldy, float rate, uint64_t seed,
                  uint32_t layer, crnn_stream_t stream);
@@ -724,9 +713,7 @@ int crnn_dropout_keep_bytes(void* out, long ngroups, float rate, uint64_t seed, 
 /* the same for n <= CRNN_KEEP_BATCH_MAX dropout sites of one step in one launch (host arrays of n entries) */
 #define CRNN_KEEP_BATCH_MAX 8
 int crnn_dropout_keep_bytes_batch(int n, void* const* out, const long* ngroups, const uint32_t* layer, float rate, uint64_t seed, crnn_stream_t stream);
-int crnn_relu_bwd(const float* y, const float* g, float* go, long rows, int C, float scale, int permP,
-                  crnn_stream_t stream);
-/* the same with a bf16 copy of the result (go_bf16, may be NULL; round to nearest even) -- round 5: dense1's data gradient runs on the weights-resident GEMM */
+/* go[perm(r)][c] = g[r][c] * scale where y[r][c] > 0 (backward of ReLU and of Dropout after ReLU), with a bf16 copy of the result (go_bf16, may be NULL; round to nearest even) -- round 5: dense1's data gradient runs on the weights-resident GEMM */
 int crnn_relu_bwd_ex(const float* y, const float* g, float* go, void* go_bf16, long rows, int C, float scale, int permP, crnn_stream_t stream);
 /* spatial transformer pieces (utils.py:116-258) */
 int crnn_maxpool_fwd(const float* x, float* y, int B, int H, int W, int C, int ph, int pw, crnn_stream_t stream);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """BatchNorm-backward statistics pass (crnn_bn_bwd_ex with dx = NULL) on the step's shapes at batch 256, rotating buffers (cold), product
-library and any variant builds of conv.hip found as scripts/_trace/libbnb_*.so (the chunking experiments are gone: conv.hip, bn_bwd_rows_per_chunk)."""
+library and any variant builds of batchnorm.hip found as scripts/_trace/libbnb_*.so (the chunking experiments are gone: batchnorm.hip, bn_bwd_rows_per_chunk)."""
 import ctypes, glob, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "crnn-ocr-lite_amd")]

@@ -2,7 +2,7 @@
 """Fused depthwise-stage backward of blocks 2-7 at batch B: the halo-tile kernel (crnn_dwconv3x3_bwd_fused) against the row-stream kernel
 (crnn_dwconv3x3_bwd_stream), the six launches issued round-robin on their own buffers (cold like in the step), each timed with its own
 events; 4 tensor passes (d, da, x in; dx out) per launch.  Also times any variant builds of
-dwconv_bwd_stream.hip + conv.hip found as scripts/_trace/libdbs_*.so (the ablation builds are gone: profiles/r03_dw_bwd_stream_bench.txt)."""
+dwconv_bwd_stream.hip + batchnorm.hip found as scripts/_trace/libdbs_*.so (the ablation builds are gone: profiles/r03_dw_bwd_stream_bench.txt)."""
 import ctypes, glob, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "crnn-ocr-lite_amd")]

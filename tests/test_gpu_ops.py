@@ -20,9 +20,9 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 # implemented ReLU would pass them.  Each test_*_hot case re-runs its test -- same assertions, same tolerances -- with BatchNorm parameters that put the
 # pre-activation at about N(3, 2^2): 6-7 % of the decided elements at each end, and asserts on the host that it got there.
 # Which hot case holds which spelling of the gate 0 < t < 6 to a host reference (each fails with the `< 6` term taken out of the kernels):
-#   conv.hip  BatchNorm backward, statistics and apply passes   bn_relu6_pool_dropout, batchnorm_backward_..._as_planes, pooled_..._saved_window_maxima (sum gy)
-#   conv.hip  saved-window-maxima passes (`best`)               pooled_..._saved_window_maxima (bit identity with the pass above)
-#   conv.hip  block 1: one backward pass over dq, c1 backward   block1_kernels_with_batchnorm1_folded_in (sum gy, BatchNorm-1 input gradient)
+#   batchnorm.hip  BatchNorm backward, statistics and apply passes   bn_relu6_pool_dropout, batchnorm_backward_..._as_planes, pooled_..._saved_window_maxima (sum gy)
+#   batchnorm.hip  saved-window-maxima passes (`best`)               pooled_..._saved_window_maxima (bit identity with the pass above)
+#   block1.hip  one backward pass over dq, c1 backward               block1_kernels_with_batchnorm1_folded_in (sum gy, BatchNorm-1 input gradient)
 #   conv_bwd_fused.hip                                          fused_depthwise_stage_backward (dx, dk against the oracle)
 #   dwconv_bwd_stream.hip  BatchNorm-1 gate of every form       fused_depthwise_stage_backward[(1, 3, 18, 256)], fp32_row_stream_depthwise_stage_backward
 #   dwconv_bwd_stream.hip  producer's BatchNorm-2 statistics    row_stream_..._batchnorm2_prologue (bf16: the statistics wave), its fp32 twin (the DX waves)
@@ -227,17 +227,17 @@ def test_dwconv_fwd_flip_wgrad_stats(shape):
     out = zeros(*shape)
     ntiles = L().crnn_dwconv_num_tiles(B, H, W)
     parts = zeros(ntiles, 2, C) if C % 32 == 0 else None
-    ok(L().crnn_dwconv3x3_fwd(P(xd), P(kd), P(out), P(parts), B, H, W, C, 0, S()))
+    ok(L().crnn_dwconv3x3_fwd_ex(P(xd), P(kd), P(out), P(parts), B, H, W, C, 0, 0, S()))      # (dtype 0 = CRNN_F32 here and below)
     assert_close(host(out), ref, what="fwd")
     if parts is not None:
         st = host(parts).sum(0)
         assert_close(st[0], ref.sum((0, 1, 2)), rtol=1e-4, atol=1e-3, what="sum")
         assert_close(st[1], (ref ** 2).sum((0, 1, 2)), rtol=1e-4, atol=1e-3, what="sumsq")
     dx = zeros(*shape)
-    ok(L().crnn_dwconv3x3_fwd(P(gd), P(kd), P(dx), None, B, H, W, C, 1, S()))
+    ok(L().crnn_dwconv3x3_fwd_ex(P(gd), P(kd), P(dx), None, B, H, W, C, 1, 0, S()))
     assert_close(host(dx), dx_ref, what="dgrad")
     dk = zeros(9, C); scr = zeros(max(1, ntiles * 9 * C))
-    ok(L().crnn_dwconv3x3_wgrad(P(xd), P(gd), P(dk), P(scr), B, H, W, C, S()))
+    ok(L().crnn_dwconv3x3_wgrad_ex(P(xd), P(gd), P(dk), P(scr), B, H, W, C, 0, S()))
     assert_close(host(dk).reshape(3, 3, C), dk_ref, rtol=1e-4, atol=1e-4, what="wgrad")
 
 
@@ -390,14 +390,16 @@ def _bn_state(x, gamma, beta):
     xd = dev(x)
     chunks = L().crnn_colreduce_chunks(Mrows)
     parts = zeros(chunks, 2, C)
-    ok(L().crnn_colreduce(P(xd), P(parts), Mrows, C, C, 2, S()))
+    ok(L().crnn_colreduce_ex(P(xd), P(parts), Mrows, C, C, 2, 0, S()))
     st = zeros(4 * C)
     ok(L().crnn_bn_finalize(P(parts), chunks, C, Mrows, P(dev(gamma)), P(dev(beta)), P(st), S()))
     return xd, st
 
 
 @pytest.mark.parametrize("shape,pool,rate", [((3, 8, 6, 64), (1, 1), 0.0), ((2, 8, 6, 32), (2, 2), 0.0), ((2, 6, 8, 128), (1, 2), 0.1),
-                                            ((2, 7, 5, 1), (1, 1), 0.0), ((2, 9, 7, 36), (2, 2), 0.1)])
+                                            ((2, 7, 5, 1), (1, 1), 0.0), ((2, 9, 7, 36), (2, 2), 0.1),
+                                            # a window the kernels take at run time (the CRNN pools 2 x 2 and 1 x 2 only): four channels per thread, and one
+                                            ((2, 6, 8, 12), (2, 1), 0.1), ((2, 6, 8, 3), (2, 1), 0.0)])
 def test_bn_relu6_pool_dropout_fwd_bwd(shape, pool, rate, hot=False, seed=None):
     B, H, W, C = shape
     ph, pw = pool
@@ -425,7 +427,7 @@ def test_bn_relu6_pool_dropout_fwd_bwd(shape, pool, rate, hot=False, seed=None):
     r = ops.relu6_fwd(y_bn)
     ref = ops.maxpool_fwd(r, ph, pw) * mk
     y = zeros(B, Ho, Wo, C)
-    ok(L().crnn_bn_act_pool_drop(P(xd), P(st), P(y), B, H, W, C, ph, pw, rate, seed, layer, S()))
+    ok(L().crnn_bn_act_pool_drop_ex(P(xd), P(st), P(y), B, H, W, C, ph, pw, rate, seed, layer, 0, 0, S()))
     assert_close(host(y), ref, what="fwd")
     # backward
     g = rs.normal(size=(B, Ho, Wo, C))
@@ -434,8 +436,8 @@ def test_bn_relu6_pool_dropout_fwd_bwd(shape, pool, rate, hot=False, seed=None):
     dx_ref, dg_ref, db_ref = ops.bn_train_bwd(x, gamma, mean, var, gr)
     dx = zeros(*shape); dgm = zeros(C); dbt = zeros(C)
     parts = zeros(L().crnn_bn_bwd_chunks(B * H * W), 2, C); coef = zeros(2 * C)
-    ok(L().crnn_bn_bwd(P(xd), P(dev(g)), P(st), P(dev(gamma)), P(dx), P(dgm), P(dbt), P(parts), P(coef), B, H, W, C, ph, pw, rate, seed,
-                       layer, S()))
+    ok(L().crnn_bn_bwd_ex(P(xd), P(dev(g)), P(st), P(dev(gamma)), P(dx), P(dgm), P(dbt), P(parts), P(coef), B, H, W, C, ph, pw, rate, seed,
+                          layer, 0, S()))
     assert_close(host(dgm), dg_ref, rtol=2e-4, atol=1e-4, what="dgamma")
     assert_close(host(dbt), db_ref, rtol=2e-4, atol=1e-4, what="dbeta")
     assert_close(host(dx), dx_ref, rtol=2e-4, atol=1e-5, what="dx")
@@ -494,7 +496,7 @@ def test_bn_inference_state_and_colsum():
         z = rs.normal(size=(Mr, Cc))
         ch = L().crnn_colreduce_chunks(Mr)
         parts = zeros(ch, Cc); out = zeros(Cc)
-        ok(L().crnn_colreduce(P(dev(z)), P(parts), Mr, Cc, Cc, 1, S()))
+        ok(L().crnn_colreduce_ex(P(dev(z)), P(parts), Mr, Cc, Cc, 1, 0, S()))
         ok(L().crnn_partials_sum(P(parts), ch, Cc, P(out), 1.0, S()))
         assert_close(host(out), z.sum(0), rtol=1e-4, atol=1e-3, what="colsum")
 
