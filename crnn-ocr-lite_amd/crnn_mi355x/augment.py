@@ -16,6 +16,7 @@ import math
 import numpy as np
 
 from . import native
+from .hashing import mix32                                 # the noise stage's hash (shared with synth.py)
 
 FIELDS = ("a00", "a01", "a10", "a11", "t0", "t1", "fill", "morph", "blur", "gain", "bias", "noise")
 MAX_COEF, MAX_MORPH, MAX_BLUR, MAX_GAIN, MAX_BIAS, MAX_NOISE = 262144, 2, 2, 1024, 255, 64
@@ -54,18 +55,6 @@ def check_items(items, img_size):
         raise ValueError("augment item out of range (|a..| <= %d, |t0| <= T0 << 17, |t1| <= T1 << 17, fill -1..255, morph -%d..%d, blur 0..%d, "
                          "gain 0..%d, bias -%d..%d, noise 0..%d)" % (MAX_COEF, MAX_MORPH, MAX_MORPH, MAX_BLUR, MAX_GAIN, MAX_BIAS, MAX_BIAS, MAX_NOISE))
     return items
-
-
-def mix32(x):
-    """The noise stage's hash on uint32 (arrays or scalars) -> uint64 values below 2^32."""
-    m = np.uint64(0xffffffff)
-    x = np.asarray(x, dtype=np.uint64) & m
-    x ^= x >> np.uint64(16)
-    x = (x * np.uint64(0x7feb352d)) & m
-    x ^= x >> np.uint64(15)
-    x = (x * np.uint64(0x846ca68b)) & m
-    x ^= x >> np.uint64(16)
-    return x
 
 
 def _warp(v, it):

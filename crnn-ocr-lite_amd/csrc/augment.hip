@@ -9,11 +9,6 @@
 #define AUG_MAX_PIXELS 16384               // imgh * imgw: two 16 KiB LDS buffers
 #define AUG_MAX_COEF 262144
 
-__device__ __forceinline__ unsigned aug_mix32(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
-
 __global__ __launch_bounds__(AUG_THREADS) void augment_batch_kernel(const unsigned char* __restrict__ in, const crnn_augment_item* __restrict__ items,
                                                                     int n, int T0, int T1, const float* __restrict__ table, float* __restrict__ out,
                                                                     unsigned char* __restrict__ out_u8) {
@@ -120,7 +115,7 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_batch_kernel(const unsign
     int v = cur[o];
     if (tone) v = page_clampi(((v - 128) * it.gain + tone_off) >> 8, 0, 255);
     if (it.noise != 0) {
-      const unsigned h = aug_mix32(it.seed ^ ((unsigned)o * 0x9E3779B9u));
+      const unsigned h = crnn_mix32(it.seed ^ ((unsigned)o * 0x9E3779B9u));
       const int s = (int)((h & 255u) + ((h >> 8) & 255u) + ((h >> 16) & 255u) + (h >> 24)) - 510;
       v = page_clampi(v + ((s * it.noise) >> 8), 0, 255);
     }

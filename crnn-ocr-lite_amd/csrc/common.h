@@ -57,6 +57,13 @@ static inline int crnn_lds_attr(const void* fn, int bytes, std::atomic<unsigned 
     CRNN_TRY(crnn_lds_attr((const void*)(fn), (bytes), latch__));             \
   } while (0)
 
+// The integer hash of the input side (include/crnn_mi355x.h: the noise of crnn_augment_batch, the baseline jitter of crnn_synth_words), modulo 2^32;
+// in Python: crnn_mi355x/hashing.py mix32.
+__host__ __device__ __forceinline__ unsigned crnn_mix32(unsigned x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+
 __device__ __forceinline__ float relu6f(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 __device__ __forceinline__ float hard_sigmoid(float z) { return fminf(fmaxf(0.2f * z + 0.5f, 0.f), 1.f); }
 __device__ __forceinline__ float hs_grad_from_out(float a) { return (a > 0.f && a < 1.f) ? 0.2f : 0.f; }

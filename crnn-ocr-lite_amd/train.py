@@ -3,6 +3,7 @@
 
   python train.py --path DATA --save_path OUT --model_name NAME --opt adam --lr 1e-4 --norm [--mjsynth ...]
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...      # data parallel: one rank per GPU
+  python train.py --path VALDATA --synth WORDS.txt --synth_fonts A.ttf,B.ttf ...    # training words rendered on the GPU; --path validates
 
 Differences from the reference, on purpose: `--GRU` / `--norm` mean what they say (the reference's
 `from utils import *` shadows both, SURVEY F3: it always builds GRU and always normalises); `--G` selects the
@@ -53,7 +54,26 @@ def build_parser():
                              'placeholders); on the GPU with --device_ingest.  The validation batches are never augmented')
     parser.add_argument('--augment_p', type=float, default=None, metavar='P',
                         help='with --augment: the probability that switches each augmentation stage on per image (default: the policy\'s own)')
+    parser.add_argument('--synth', type=str, default=None, metavar='WORDLIST',
+                        help='train on word images rendered on the GPU (crnn_mi355x.synth) from this word list, one word per line, with '
+                             '--synth_fonts or --synth_atlas; the files under --path are then the validation set only (none: no validation)')
+    parser.add_argument('--synth_fonts', type=str, default=None, metavar='A.ttf,B.ttf', help='with --synth: the font files the glyph atlas is rasterised from')
+    parser.add_argument('--synth_font_size', type=int, default=28, metavar='N', help='with --synth_fonts: the font size in pixels')
+    parser.add_argument('--synth_atlas', type=str, default=None, metavar='FILE.npz', help='with --synth: a glyph atlas saved by GlyphAtlas.save')
+    parser.add_argument('--synth_epoch', type=int, default=65536, metavar='N', help='with --synth: images per epoch (over all ranks)')
     return parser
+
+
+def load_wordlist(path, alphabet, max_len):
+    """One word per line -> the words that can be drawn and learnt: lower case, every character in the alphabet, at most max_len long."""
+    lines = [line.strip().lower() for line in open(path)]
+    words = [w for w in lines if w and len(w) <= max_len and all(ch in alphabet for ch in w)]
+    dropped = sum(1 for w in lines if w) - len(words)
+    if dropped:
+        print(' [INFO] %d words of %s dropped: a character outside the alphabet, or longer than %d ' % (dropped, path, max_len))
+    if not words:
+        raise SystemExit("--synth: no usable word in %s" % path)
+    return words
 
 
 def main(argv=None):
@@ -89,7 +109,7 @@ def main(argv=None):
     lexicon = U.get_lexicon()
     classes = {ch: i for i, ch in enumerate(lexicon)}
     if args.mjsynth:
-        train = U.parse_mjsynth(args.path, open(os.path.join(args.path, args.training_fname)).readlines())
+        train = [] if args.synth is not None else U.parse_mjsynth(args.path, open(os.path.join(args.path, args.training_fname)).readlines())
         prng.shuffle(train)
         val = U.parse_mjsynth(args.path, open(os.path.join(args.path, args.val_fname)).readlines())
     else:
@@ -97,7 +117,22 @@ def main(argv=None):
         prng.shuffle(train)
         cut = int(len(train) * args.train_portion)
         train, val = train[:cut], train[cut:]
-    max_len = max(U.get_lengths(train).values())
+    words = None
+    if args.synth is not None:      # the training words are rendered on the device; every file under --path validates
+        from crnn_mi355x.labels import MAX_WORD_LEN
+        if (args.synth_fonts is None) == (args.synth_atlas is None):
+            raise SystemExit("--synth goes with exactly one of --synth_fonts and --synth_atlas")
+        words = load_wordlist(args.synth, set(lexicon), MAX_WORD_LEN)
+        atlas = (U.GlyphAtlas.load(args.synth_atlas) if args.synth_atlas is not None
+                 else U.GlyphAtlas.from_fonts(args.synth_fonts.split(","), args.synth_font_size, lexicon))
+        val = train + val                   # (--mjsynth: the list --val_fname names)
+        train = [None] * max(args.synth_epoch, 1)
+        max_len = max([len(w) for w in words] + list(U.get_lengths(val).values()))      # the word list's, unless a validation word is longer
+        args.device_ingest = True
+    elif args.synth_fonts is not None or args.synth_atlas is not None:
+        raise SystemExit("--synth_fonts and --synth_atlas go with --synth")
+    else:
+        max_len = max(U.get_lengths(train).values())
     print(' [INFO] %d train and %d validation images loaded ' % (len(train), len(val)))
     lo, hi = shard(len(train), rank, world)    # equal shards: every rank runs the same number of steps (= collectives) per epoch
     train = train[lo:hi]
@@ -112,8 +147,13 @@ def main(argv=None):
         return (U.DeviceReadf if args.device_ingest else U.Readf)(
             img_size=(args.imgh, args.imgW, 1), normed=args.norm, batch_size=args.batch_size, classes=classes, max_len=max_len, transform_p=0.7,
             workers=args.workers, seed=args.random_state, **({} if augment is None else {"augment": augment}))
-    reader = make_reader(policy)
-    val_reader = reader if policy is None else make_reader(None)      # validation: a reader of its own, without augmentation
+    if words is not None:      # seeded per rank, so the ranks draw different words and placements
+        reader = U.SynthReadf(words, atlas, img_size=(args.imgh, args.imgW, 1), normed=args.norm, batch_size=args.batch_size, classes=classes,
+                              max_len=max_len, policy=U.SynthPolicy(seed=_chunk_seed(args.random_state, world + rank)), augment=policy)
+        val_reader = make_reader(None)
+    else:
+        reader = make_reader(policy)
+        val_reader = reader if policy is None else make_reader(None)      # validation: a reader of its own, without augmentation
     print(" [INFO] Number of classes: {}; Max. string length: {} ".format(len(classes) + 1, max_len))
     init_model = U.CRNN(num_classes=len(classes) + 1, shape=(args.imgh, args.imgW, 1), GRU=args.GRU,
                         time_dense_size=args.time_dense_size, n_units=args.n_units, max_string_len=max_len)
@@ -136,12 +176,15 @@ def main(argv=None):
     model.compile(loss={"ctc": lambda y_true, y_pred: y_pred}, optimizer=optimizer)
     callbacks_list = []
     if rank == 0:
-        callbacks_list.append(U.ModelCheckpoint(filepath=out_dir + '/checkpoint_weights.h5', verbose=1, save_best_only=True, save_weights_only=True))
+        monitor = 'loss' if words is not None and not val else 'val_loss'      # --synth without validation files: the best training loss
+        callbacks_list.append(U.ModelCheckpoint(filepath=out_dir + '/checkpoint_weights.h5', monitor=monitor, verbose=1, save_best_only=True,
+                                                save_weights_only=True))
     if args.early_stopping:
         callbacks_list.append(U.EarlyStoppingIter(monitor='loss', min_delta=.0001, patience=args.early_stopping, verbose=1,
                                                   restore_best_weights=True, mode="auto"))
     down = 2 ** init_model.pooling_counter_h
-    H = model.fit_generator(generator=reader.run_generator(train, downsample_factor=down), steps_per_epoch=train_steps,
+    train_gen = reader.run_generator(downsample_factor=down) if words is not None else reader.run_generator(train, downsample_factor=down)
+    H = model.fit_generator(generator=train_gen, steps_per_epoch=train_steps,
                             epochs=args.nbepochs, validation_data=val_reader.run_generator(val, downsample_factor=down) if val else None,
                             validation_steps=test_steps, shuffle=False, verbose=1 if rank == 0 else 0, callbacks=callbacks_list)
     if rank == 0:

@@ -16,6 +16,7 @@ from crnn_mi355x.align import CTCAligner, Alignment, CharSpan  # noqa: F401  (be
 from crnn_mi355x.data import (Readf, open_img, read_img, norm, parse_mjsynth, get_lengths, get_lexicon, make_ohe)  # noqa: F401
 from crnn_mi355x.ingest import DeviceIngest, DeviceReadf, plan_crop, box_slices  # noqa: F401  (beyond the reference: batches built on the device)
 from crnn_mi355x.augment import AugmentPolicy, Augmenter, augment_host, neutral_items  # noqa: F401  (beyond the reference: training augmentation on the device)
+from crnn_mi355x.synth import GlyphAtlas, SynthPolicy, SynthReadf, WordSynth, synth_host  # noqa: F401  (beyond the reference: training words rendered on the device)
 from crnn_mi355x.detect import WordDetector, detect_words_host, reading_order  # noqa: F401  (beyond the reference: the word boxes, found on the device)
 from crnn_mi355x.binarize import Binarizer, sauvola_host  # noqa: F401  (beyond the reference: adaptive binarisation in front of the detector)
 from crnn_mi355x.deskew import Deskewer, deskew_host, estimate_skew_host, rotate_host  # noqa: F401  (beyond the reference: page deskew in front of the detector)

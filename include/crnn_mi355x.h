@@ -351,6 +351,45 @@ typedef struct {
 int crnn_augment_batch(const void* in_u8, const crnn_augment_item* items, const crnn_augment_item* items_dev, int n, int batch, int imgh, int imgw,
                        const float* table, float* out, void* out_u8, crnn_stream_t stream);
 
+/* ---- synthetic training words: a glyph atlas and glyph codes -> the batch (csrc/synth.hip; the same rule in NumPy: crnn_mi355x.synth.synth_host) ----
+ * The output is the uint8 batch [batch][T0][T1] that crnn_ingest_crops writes as out_u8 (axis 0 = i runs along the text, axis 1 = j across it,
+ * j = 0 the bottom of the word, ink bright) and its fp32 table[v]; crnn_augment_batch takes it as it is.  The host draws every random decision
+ * (crnn_mi355x.synth.SynthPolicy); the kernel has no random numbers of its own, no floating point before the table lookup and no atomics.
+ * ATLAS: a byte arena of uint8 coverage bitmaps and a table crnn_glyph[nfaces][nglyphs], nglyphs = the classes without the blank.  The bitmap
+ *   of a glyph is [h][w] row-major at byte `off`, 0 = no ink, 255 = full ink; `left` = columns from the pen to the bitmap's first column (may be
+ *   negative), `top` = rows from the top of the face's line box to the bitmap's first row.  w = h = 0 is a glyph without ink (a space, a class
+ *   the face lacks); a glyph with ink has w, h >= 1.  Limits: 0 <= w, h <= 64, 0 <= top, top + h <= 64, |left| <= 64, 0 <= advance <= 128.
+ * IMAGE b < n: one crnn_synth_item and the `len` glyph codes codes[b][0 .. len) of a row of codes[n][Lmax] (the numbers Readf.make_target
+ *   puts into the_labels).
+ * LAYOUT in line space, x along the text and y downwards, glyph k = glyphs[face][codes[b][k]]:
+ *     pen_0 = 0, pen_{k+1} = pen_k + advance_k + track;
+ *     dy_k = (((mix32(seed ^ (k * 0x9E3779B9 mod 2^32)) & 0xffff) * (2 jitter + 1)) >> 16) - jitter      (mix32: crnn_augment_batch's hash);
+ *     cov(x, y) = the maximum over k < len of bitmap_k[y - top_k - dy_k][x - pen_k - left_k], positions outside a bitmap counting as 0
+ *   (0 where no glyph covers; the maximum makes overlapping glyphs well defined and independent of order).
+ * SAMPLING of output pixel (i, j), 16.16 fixed point in 64-bit integers, every shift arithmetic (the floor):
+ *     X = sx i + ox, Y = sy (T1 - 1 - j) + oy;  x0 = X >> 16, fx = (X >> 8) & 255, y0 = Y >> 16, fy = (Y >> 8) & 255;
+ *     c = ((256 - fy)(256 - fx) cov(x0, y0) + (256 - fy) fx cov(x0 + 1, y0) + fy (256 - fx) cov(x0, y0 + 1) + fy fx cov(x0 + 1, y0 + 1) + 32768) >> 16;
+ *     v = (bg (255 - c) + fg c + 127) / 255      (the numerator is never negative: the floor);
+ *     out_u8[b][i][j] = v, out[b][i][j] = table[v]; rows n <= b < batch are 0 and 0.f.
+ *   sx = sy = 65536 with ox = oy = 0 reads line pixel (i, T1 - 1 - j): an upright word, oriented as an ingest crop.
+ * Ranges: 0 <= face < nfaces, 0 <= len <= Lmax <= 64, -8 <= track <= 32, 0 <= jitter <= 8, 16384 <= sx, sy <= 262144, |ox|, |oy| <= 2^28,
+ * fg, bg 0..255, the codes inside len in [0, nglyphs). */
+typedef struct { long off; int w, h, left, top, advance; } crnn_glyph;
+typedef struct { int face, len, track, jitter; int sx, sy, ox, oy; int fg, bg; unsigned seed; } crnn_synth_item;
+/* out [batch][imgh][imgw] fp32 (and out_u8, or NULL) = the rule above; one launch, one workgroup per image: one wave turns the advances into
+ * pens with a wave prefix sum, the glyph boxes then live in LDS, and every thread gathers its output pixels (16 in a row when imgh * imgw is a
+ * multiple of 16 and both outputs lie on 16-byte boundaries: 16-byte stores) straight from the atlas, testing only the glyphs that overlap its
+ * text column.  The design adds no limit of its own: no composed line is stored.  Bit-equal between calls and to synth_host.  glyphs, codes and
+ * items are the tables in HOST memory, judged before anything is launched; glyphs_dev, codes_dev, items_dev the copies of the same entries in
+ * device memory that the kernel reads (as crnn_ingest_crops takes its table); the kernel clamps every index and every read into the tables
+ * and the atlas on its own.  CRNN_ERR_ARG (-2), with nothing launched: n < 0 or n > batch, batch < 1, a non-positive imgh, imgw, nfaces,
+ * nglyphs, Lmax or atlas_bytes, Lmax > 64, a null atlas, glyphs, glyphs_dev, table or out, null codes or item pointers when n > 0, a glyph
+ * outside its limits or with ink outside the arena, an item or a code out of range.  CRNN_ERR_UNSUPPORTED (-3): imgh * imgw > 16384
+ * (crnn_augment_batch's limit, so the two launches always compose).  batch >= 1 with n == 0 writes the zero rows. */
+int crnn_synth_words(const void* atlas, long atlas_bytes, const crnn_glyph* glyphs, const crnn_glyph* glyphs_dev, int nfaces, int nglyphs,
+                     const int* codes, const int* codes_dev, const crnn_synth_item* items, const crnn_synth_item* items_dev, int n, int batch,
+                     int Lmax, int imgh, int imgw, const float* table, float* out, void* out_u8, crnn_stream_t stream);
+
 /* ---- word detection: page images -> the word boxes crnn_ingest_crops takes (csrc/detect.hip; the same rule in NumPy: crnn_mi355x.detect) ---- */
 /* A page: a row-major uint8 image at byte `page_off` of the arena, 1 <= rows, cols <= 4096 -- the page fields of crnn_crop_item.  The arena and
  * the checks of a page table are defined once, in csrc/pages.h for the library and in crnn_mi355x/pages.py for Python. */
