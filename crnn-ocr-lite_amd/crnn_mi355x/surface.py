@@ -568,18 +568,27 @@ class Model:
             outs.append(self.predict_on_batch(x))
         return np.concatenate(outs, 0)
 
-    def score_generator(self, generator, steps, decoder, length=None):
+    def score_generator(self, generator, steps, decoder, length=None, confusions=False, maps=False):
         """Validation without the host in the middle: per batch the forward (learning_phase=0), `decoder`'s beam or greedy kernel on the
         device output and the edit distance of the decoded rows against the batch's `the_labels` (csrc/score.hip; blank and -1 skipped on
         both sides) -> metrics.Score.  Only the label rows and three integers per pair come back, in one copy per batch; no softmax map leaves
         the device.  Batch k+1 is drawn from the generator while batch k runs, as fit_generator does.  `length`: number of real pairs -- the
         stale rows of the generator's short tail batch are dropped, as predict.py does with `[:length]`.  Works over Readf and DeviceReadf.
         Raises ValueError unless every class decodes to one distinct character (metrics.check_label_metric): only then is the distance over
-        labels the distance over texts that edit_distance / normalized_edit_distance report."""
+        labels the distance over texts that edit_distance / normalized_edit_distance report.
+        confusions=True: per batch one launch of crnn_edit_ops (csrc/editops.hip) takes the place of the crnn_edit_distance launch -- it writes
+        the same three integers -- and adds the batch's character confusions to a matrix that stays on the device for the whole pass, zeroed
+        once and read once after the last batch; per pair the four counts of its edit script join the batch's one copy.  Score.ops and
+        Score.confusions then hold them.  Only the `length` real pairs are aligned: the launch of the short tail batch covers its real rows
+        alone, so its stale rows reach neither the matrix nor Score.  maps=True (with confusions=True): the alignment maps join the copy too,
+        Score.truth_maps / Score.pred_maps (metrics.device_edit_ops).  Without confusions: the launches of before."""
         import torch
-        from .metrics import Score, check_label_metric, device_edit_distances
+        from .metrics import Confusions, Score, check_label_metric, device_edit_distances, launch_edit_ops
         check_label_metric(decoder.inverse_classes)
+        if maps and not confusions:
+            raise ValueError("the maps come from the edit-ops launch: maps=True needs confusions=True")
         blank = len(decoder.inverse_classes)
+        matrix = None
         rows, cols = [], None
         batch = next(generator) if steps > 0 else None
         for k in range(steps):
@@ -592,23 +601,42 @@ class Model:
             truth = truth.reshape(len(x), -1)
             y = eng.forward(x, train=False)
             labels, _ = decoder.decode_labels(y, device=True)
-            dist, plen, tlen = device_edit_distances(labels, truth, (blank, -1))
+            n = len(x)
+            extra = []
+            if confusions:
+                if matrix is None:
+                    matrix = torch.zeros((blank + 1, blank + 1), dtype=torch.int32, device=eng.device)
+                real = n if length is None else max(0, min(n, length - k * n))      # the tail batch's stale rows are not aligned
+                labels = labels.to(torch.int32).contiguous()
+                outs = launch_edit_ops(labels[:real], truth.contiguous()[:real], (blank, -1), blank, matrix, maps)
+                ops, dist, plen, tlen = (torch.cat([t, t.new_zeros((n - real,) + tuple(t.shape[1:]))]) for t in outs[:4])
+                extra = [ops.reshape(-1)] + [torch.cat([t, t.new_full((n - real, t.shape[1]), -2)]).reshape(-1) for t in outs[4:] if maps]
+            else:
+                dist, plen, tlen = device_edit_distances(labels, truth, (blank, -1))
             status = eng._rnn_giveups if eng._rnn_giveups is not None else torch.zeros(1, dtype=torch.int32, device=eng.device)
-            packed = torch.cat([labels.reshape(-1), dist, plen, tlen, status.reshape(-1)])
+            packed = torch.cat([labels.reshape(-1), dist, plen, tlen] + extra + [status.reshape(-1)])
             cols = labels.shape[1]
             if k + 1 < steps:
                 batch = next(generator)               # host decoding / device ingest of batch k+1 while batch k runs
             packed = packed.cpu().numpy()             # the one host synchronisation of the batch
             eng.raise_if_rnn_gave_up(packed[-1])
-            n = len(x)
-            rows.append((packed[:n * cols].reshape(n, cols), packed[n * cols:n * cols + n], packed[n * cols + n:n * cols + 2 * n],
-                         packed[n * cols + 2 * n:n * cols + 3 * n]))
+            widths = [cols, 1, 1, 1] + ([4] if confusions else []) + ([truth.shape[1], cols] if maps else [])
+            starts = np.cumsum([0] + [n * w for w in widths])
+            rows.append(tuple(packed[a:b] if 1 <= f <= 3 else packed[a:b].reshape(n, w)      # labels | dist, lengths | ops, maps
+                              for f, (a, b, w) in enumerate(zip(starts[:-1], starts[1:], widths))))
+            if confusions and (rows[-1][4][:, 0] < 0).any():
+                raise ValueError("row %d of batch %d has a label outside [0, %d)" % (int(np.nonzero(rows[-1][4][:, 0] < 0)[0][0]), k, blank))
         if not rows:
             return Score(np.zeros((0, 0), np.int32), [], [], [])
         parts = [np.concatenate(p, 0) for p in zip(*rows)]
         if length is not None:
             parts = [p[:length] for p in parts]
-        return Score(*parts)
+        if not confusions:
+            return Score(*parts)
+        score = Score(*parts[:4], ops=parts[4], confusions=Confusions(matrix.cpu().numpy(), decoder.inverse_classes))    # the one matrix read of the pass
+        if maps:
+            score.truth_maps, score.pred_maps = parts[5], parts[6]
+        return score
 
 
 def init_predictor(model):

@@ -2,6 +2,9 @@
 """Prediction CLI with the reference's flag surface (predict.py:62-79): forward on the GPU, whole-batch
 HIP beam-search decode (beam_width=10, top_paths=1, merge_repeated as TF 1.8), optional edit-distance report
 and prediction.csv.  --device_score (with --validate) keeps decoding and scoring on the GPU: same report, same prediction.csv.
+--confusions [K] (with --validate) aligns every prediction to its truth and adds the totals of matches, substitutions, deletions and insertions
+and the K (default 20) most frequent character confusions to the report, and writes confusions.csv (truth, predicted, count of every non-zero
+cell) next to prediction.csv; with --device_score on the GPU (crnn_edit_ops), else on the host (metrics.confusion_matrix): same lines, same file.
 --lexicon FILE decodes to the most probable word of a list (crnn_mi355x.lexicon) instead of the beam search.
 --lexicon_shortlist K (with --lexicon) scores per image only the K words nearest in edit distance to the beam search's --lexicon_paths best paths.
 --align (with --result_path) aligns every prediction to its own softmax map (crnn_mi355x.align) and writes alignment.csv: per character its frames
@@ -49,6 +52,9 @@ def build_parser():
                         help='build the batches on the GPU: pages go up as uint8 with a box table, one kernel crops, pads and normalises')
     parser.add_argument('--device_score', action='store_true',
                         help='with --validate: decode and score on the GPU (one edit-distance kernel per batch); no softmax map is copied to the host')
+    parser.add_argument('--confusions', type=int, nargs='?', const=20, default=None, metavar='K',
+                        help='with --validate: report the totals of the edit scripts and the K (default 20) most frequent character confusions, '
+                             'and write confusions.csv next to prediction.csv; with --device_score aligned and counted on the GPU')
     parser.add_argument('--lexicon', type=str, default=None,
                         help='a word list, one word per line: decode to the word of the list with the highest CTC probability instead of the beam search')
     parser.add_argument('--lexicon_shortlist', type=int, default=None,
@@ -121,6 +127,10 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.device_score and not args.validate:
         parser.error("--device_score scores against the truth: it needs --validate")
+    if args.confusions is not None and not args.validate:
+        parser.error("--confusions aligns the predictions to the truth: it needs --validate")
+    if args.confusions is not None and args.confusions < 0:
+        parser.error("--confusions must be 0 or more")
     if args.align and args.result_path is None:
         parser.error("--align writes alignment.csv next to prediction.csv: it needs --result_path")
     if args.align and args.device_score:
@@ -319,7 +329,8 @@ def main(argv=None):
     start = time.time()
     score = None
     if args.device_score:                                    # forward, beam search and edit distance per batch, all on the device
-        score = model.score_generator(reader.run_generator(fnames, bboxs=bboxs, downsample_factor=2), steps=steps, decoder=decoder, length=length)
+        score = model.score_generator(reader.run_generator(fnames, bboxs=bboxs, downsample_factor=2), steps=steps, decoder=decoder, length=length,
+                                      confusions=args.confusions is not None)
         print(" [INFO] %d images processed in %s sec. " % (len(fnames), round(time.time() - start, 2)))
         start = time.time()
         predicted_text = score.texts(decoder)
@@ -365,6 +376,15 @@ def main(argv=None):
             ned = U.normalized_edit_distance(predicted_text, true_text)
         print(" [INFO] edit distances calculated in %s sec. " % round(time.time() - start, 2))
         print(" [INFO] mean edit distance: %f ; normalized edit distance score: %f " % (ed, ned))
+        if args.confusions is not None:
+            if score is not None:                            # counted on the device, batch by batch, and read once
+                confusions = score.confusions
+            else:
+                pairs = [([classes[c] for c in p], [classes[c] for c in t]) for p, t in zip(predicted_text, true_text)]
+                confusions = U.Confusions(U.confusion_matrix(pairs, len(inverse_classes)), inverse_classes)
+            print(confusions.report(args.confusions))
+            if args.result_path is not None:
+                confusions.to_csv(os.path.join(args.result_path, "confusions.csv"))
 
 
 if __name__ == '__main__':

@@ -22,4 +22,5 @@ from crnn_mi355x.binarize import Binarizer, sauvola_host  # noqa: F401  (beyond 
 from crnn_mi355x.deskew import Deskewer, deskew_host, estimate_skew_host, rotate_host  # noqa: F401  (beyond the reference: page deskew in front of the detector)
 from crnn_mi355x.metrics import levenshtein, edit_distance, normalized_edit_distance  # noqa: F401
 from crnn_mi355x.metrics import Score, device_edit_distances, check_label_metric  # noqa: F401  (beyond the reference: scored on the device)
+from crnn_mi355x.metrics import edit_ops, confusion_matrix, device_edit_ops, Confusions  # noqa: F401  (edit scripts and character confusions)
 from crnn_mi355x.callbacks import Callback, EarlyStoppingIter, ModelCheckpoint  # noqa: F401

@@ -226,6 +226,28 @@ int crnn_ctc_beam_decode_lm(const float* y, const int* input_len, const float* l
  * may pass the operands swapped. */
 int crnn_edit_distance(const int* pred, int pred_cols, const int* truth, int truth_cols, int skip0, int skip1,
                        int* dist, int* pred_len, int* truth_len, int n, crnn_stream_t stream);
+/* Edit scripts and character confusions of the same pairs (csrc/editops.hip; the host definition is metrics.edit_ops), one launch for the batch.
+ * Both rows are filtered as crnn_edit_distance filters them: b[0..m) the truth, a[0..n') the prediction, D the Levenshtein matrix with i over
+ * the truth and j over the prediction.  The script is the backtrace from (m, n') to (0, 0); at each cell the FIRST rule that applies is taken:
+ *   1. i > 0 && j > 0 && D[i][j] == D[i-1][j-1] + (b[i-1] != a[j-1]): diagonal -- a match if the symbols are equal, else a substitution of
+ *      b[i-1] by a[j-1];   2. i > 0 && D[i][j] == D[i-1][j] + 1: deletion, b[i-1] has no counterpart;   3. otherwise: insertion, a[j-1] has none.
+ * So "ab" / "ba" is two substitutions, of a doubled letter read once the FIRST is the dropped one, of a letter read twice the first is spurious.
+ * Per row r < n, all int32: ops[r][4] = {matches, substitutions, deletions, insertions} (sub + del + ins = dist, match + sub + del = m,
+ * match + sub + ins = n'); dist / pred_len / truth_len as crnn_edit_distance writes them; truth_map[r][k] ([n, truth_cols]) = the filtered
+ * prediction position aligned to truth symbol k, -1 for a deletion, -2 for k >= m; pred_map[r][k] ([n, pred_cols]) the mirror image: the truth
+ * position, -1 for an insertion, -2 for k >= n'.  Positions index the FILTERED rows: the characters of labels_to_text(row) and of
+ * crnn_ctc_align's per-character output.  truth_map and pred_map may each be NULL: that map is not written.  Rows past n are not written.
+ * conf [(C + 1)][(C + 1)] int32, C = num_classes, row = truth class, column = predicted class, index C = "nothing": a match or substitution
+ * adds 1 to conf[b][a], a deletion to conf[b][C], an insertion to conf[C][a]; conf[C][C] is never touched.  The kernel ADDS to what is there:
+ * the caller zeroes the matrix once and any number of launches accumulate into it (a private matrix per workgroup in LDS, one global integer
+ * atomic per non-zero cell; integers only, so the result is the same bits whatever the order).  A cell overflows at 2^31 symbols.  conf may be
+ * NULL: skipped.  Here a label indexes memory: a pair with a kept symbol outside [0, C) on either side gets ops = {-1, -1, -1, -1} and maps of
+ * -2 throughout, its dist and lengths as usual, and adds nothing to conf.  One wavefront per pair; LDS: 20 bytes per prediction column and
+ * wavefront (sized from pred_cols) plus the matrix.  Supported: truth_cols <= 64, pred_cols <= 1024, num_classes <= 128, else -3; -2 for a null
+ * pred / truth / ops / dist / pred_len / truth_len, n < 0, a column count or num_classes < 1; n == 0 launches nothing.  The script is NOT
+ * symmetric: the operands cannot be swapped. */
+int crnn_edit_ops(const int* pred, int pred_cols, const int* truth, int truth_cols, int skip0, int skip1, int num_classes, int* ops,
+                  int* dist, int* pred_len, int* truth_len, int* truth_map, int* pred_map, int* conf, int n, crnn_stream_t stream);
 
 /* ---- lexicon decoding: CTC log-probabilities of a word list (csrc/lexicon.hip) ------------------------------ */
 /* scores[b][j] = log p(word | y[b, skip : skip + Tb]) in Keras' semantics: the negative of what K.ctc_batch_cost / crnn_ctc_loss_grad return for
