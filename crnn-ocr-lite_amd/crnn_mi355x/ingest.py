@@ -205,8 +205,35 @@ class DeviceIngest:
                 words.append(b[0] if b[0] is not None else "-")
         return self.crops(pages, index, rects, self.plan(rects, transform_p), batch=batch, return_u8=return_u8), words
 
-    def files(self, names, transform_p=0., batch=None, return_u8=False):
-        """One word per image file (mjsynth, IAM words): decoded with data.read_img on the host, every file a whole-image box."""
+    def _jpeg(self):
+        if getattr(self, "_decoder", None) is None:
+            from .jpeg import JpegDecoder
+            self._decoder = JpegDecoder(self.device)
+        return self._decoder
+
+    def decoded(self, files, names=None):
+        """Image files (byte strings or names) -> PageArena of their grey pages, decoded on the device (jpeg.JpegDecoder: baseline JPEG there,
+        everything else by read_img on the host, in the same upload).  Reads the per-file status back -- one small synchronising copy per call,
+        4 bytes per file -- and raises ValueError naming the first file whose data is corrupt or truncated."""
+        from .jpeg import CORRUPT, TRUNCATED
+        arena, status, _ = self._jpeg().decode(files)
+        bad = np.flatnonzero(status.cpu().numpy() & (CORRUPT | TRUNCATED))
+        if len(bad):
+            which = (names if names is not None else files)[int(bad[0])]
+            raise ValueError("corrupt or truncated JPEG data: %s" % (which if isinstance(which, str) else "file %d" % int(bad[0])))
+        return arena
+
+    def files(self, names, transform_p=0., batch=None, return_u8=False, decode="host"):
+        """One word per image file (mjsynth, IAM words), every file a whole-image box.  decode="host": decoded with data.read_img on the host.
+        decode="device": the files' bytes go up and are decoded there (`decoded`); bit-equal on greyscale files, and on colour files equal
+        but for the grey of exact rounding ties (jpeg.py)."""
+        if decode not in ("host", "device"):
+            raise ValueError("decode is 'host' or 'device', not %r" % (decode,))
+        if decode == "device":
+            arena = self.decoded(names)
+            rects = [(0, pg.shape[0], 0, pg.shape[1]) for pg in arena.pages]
+            words = [_word_of(name).lower() for name in names]
+            return self.crops(None, list(range(len(rects))), rects, self.plan(rects, transform_p), batch=batch, return_u8=return_u8, arena=arena), words
         pages = [read_img(name) for name in names]
         rects = [(0, pg.shape[0], 0, pg.shape[1]) for pg in pages]
         words = [_word_of(name).lower() for name in names]
@@ -218,18 +245,49 @@ def _decode_files(names):
     return [read_img(name) for name in names]
 
 
+class FileRef:
+    """An image file still encoded (DeviceReadf(device_decode=True)): its name, its bytes and the (rows, cols) its header states, so that crops
+    are planned before anything is decoded."""
+
+    def __init__(self, name, data):
+        from .jpeg import header_size
+        self.name, self.data = name, data
+        self.shape = header_size(data)
+        if self.shape is None:                                 # no JPEG: the host decodes it later; its size from the container's header
+            import io
+            from PIL import Image
+            w, h = Image.open(io.BytesIO(data)).size
+            self.shape = (h, w)
+
+
+def _read_files(names):
+    """Worker entry of device_decode: the files' bytes, nothing decoded."""
+    out = []
+    for name in names:
+        with open(name, "rb") as fh:
+            out.append(FileRef(name, fh.read()))
+    return out
+
+
 class DeviceReadf(Readf):
     """Readf whose batches are built on the device: run_generator yields the same dictionaries with 'the_input' as a device fp32 tensor
     (B,) + img_size -- same visiting order, first-pass tail rule, labels, lengths and source_str as the serial Readf (workers=0), and for
     transform_p > 0 the same draws from np.random, so under one seed the images are the serial loop's bit for bit.  Rows past a short tail
     batch's items are zero (Readf leaves them undefined).  `workers=N` decodes the image files in N processes, in order and a bounded
     number ahead (the one piece of work left on the host); everything after the decoding is the same for any worker count.
+    `device_decode=True`: the files are read, not decoded -- crops are planned from the header's dimensions, `workers=N` only read bytes, and
+    each batch's files are decoded on the device in front of its crop launch (DeviceIngest.decoded: baseline JPEG there, anything else by
+    read_img on the host; one 4-byte-per-file status read-back per batch, after which a corrupt or truncated file raises ValueError with its
+    name).  Same labels, lengths, source_str, visiting order and np.random draws; the images are bit-equal on greyscale files, and on colour
+    files differ at most by the grey of exact rounding ties (jpeg.py).  A page file with many boxes is decoded once per batch that cuts from
+    it: the mode is meant for one-word files.
     `augment` (an augment.AugmentPolicy): every emitted batch is augmented on the device, in a second launch on the same stream, with the
     items the policy draws for it -- the batches of Readf(augment=policy) under the same seeds, bit for bit."""
 
-    def __init__(self, *args, device=None, **kwargs):
+    def __init__(self, *args, device=None, device_decode=False, **kwargs):
         super().__init__(*args, **kwargs)
         self._device, self._ingest, self._augmenter = device, None, None
+        self._load = _read_files if device_decode else _decode_files
 
     def _get_ingest(self):
         if self._ingest is None:
@@ -261,13 +319,13 @@ class DeviceReadf(Readf):
                     yield run
         if self.workers <= 0:
             for group in groups():
-                yield [(name, read_img(name)) for name in group]
+                yield list(zip(group, self._load(group)))
         from collections import deque
         pool, pending, tasks = self._get_pool(), deque(), groups()
         while True:
             while len(pending) < 2 * self.workers:
                 group = next(tasks)
-                pending.append((group, pool.apply_async(_decode_files, (group,))))
+                pending.append((group, pool.apply_async(self._load, (group,))))
             group, res = pending.popleft()
             yield list(zip(group, res.get()))
 
@@ -299,9 +357,12 @@ class DeviceReadf(Readf):
             index.append(k)
         plans = tuple(np.stack([it[2] for it in items], axis=1))
         rects = [it[1] for it in items]
+        arena = None
+        if self._load is _read_files:                                  # device_decode: the batch's files are decoded where the crops are cut
+            arena, pages = self._get_ingest().decoded([ref.data for ref in pages], [ref.name for ref in pages]), None
         if self.augment is None:
-            return self._get_ingest().crops(pages, index, rects, plans, batch=self.batch_size)
-        _, u8 = self._get_ingest().crops(pages, index, rects, plans, batch=self.batch_size, return_u8=True)
+            return self._get_ingest().crops(pages, index, rects, plans, batch=self.batch_size, arena=arena)
+        _, u8 = self._get_ingest().crops(pages, index, rects, plans, batch=self.batch_size, return_u8=True, arena=arena)
         return self._get_augmenter().run(u8, self.augment.draw(len(items), self.img_size))
 
     def run_generator(self, names, downsample_factor=2, bboxs={}):

@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 LIB_PATH = os.path.join(PKG_ROOT, "libcrnn_mi355x.so")
 HOOKS_HEADER = os.path.join(REPO_ROOT, "include", "crnn_testhooks.h")
 HOOKS_PATH = os.path.join(PKG_ROOT, "libcrnn_testhooks.so")     # measurement / test hooks: never loaded by the product path
-SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_planes.hip", "gemm_nt.hip", "gemm_wres.hip", "gemm_wres3.hip", "gemm_wgrad.hip", "gemm_wgrad3.hip", "gemm_pres.hip", "dwconv_tile.hip", "reduce.hip", "batchnorm.hip", "elementwise.hip", "block1.hip", "conv_bwd_fused.hip", "dwconv_stream.hip", "dwconv_bwd_stream.hip", "stn.hip", "rnn.hip", "rnn_persist.hip", "gru_persist.hip", "ctc.hip", "dense.hip", "beam.hip", "score.hip", "editops.hip", "lexicon.hip", "lexicon_nearest.hip", "align.hip", "optim.hip", "ingest.hip", "augment.hip", "synth.hip", "detect.hip", "binarize.hip", "deskew.hip", "model.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_planes.hip", "gemm_nt.hip", "gemm_wres.hip", "gemm_wres3.hip", "gemm_wgrad.hip", "gemm_wgrad3.hip", "gemm_pres.hip", "dwconv_tile.hip", "reduce.hip", "batchnorm.hip", "elementwise.hip", "block1.hip", "conv_bwd_fused.hip", "dwconv_stream.hip", "dwconv_bwd_stream.hip", "stn.hip", "rnn.hip", "rnn_persist.hip", "gru_persist.hip", "ctc.hip", "dense.hip", "beam.hip", "score.hip", "editops.hip", "lexicon.hip", "lexicon_nearest.hip", "align.hip", "optim.hip", "ingest.hip", "augment.hip", "synth.hip", "detect.hip", "binarize.hip", "deskew.hip", "jpeg.hip", "model.hip"]
 
 
 class crnn_config(ctypes.Structure):

@@ -50,6 +50,8 @@ def build_parser():
                         help='image decoding processes feeding the generator (0 = the reference\'s single-threaded loader)')
     parser.add_argument('--device_ingest', action='store_true',
                         help='build the batches on the GPU: pages go up as uint8 with a box table, one kernel crops, pads and normalises')
+    parser.add_argument('--device_decode', action='store_true',
+                        help='with --device_ingest: decode baseline JPEG files on the GPU too (crnn_mi355x.jpeg); other files are decoded on the host as before')
     parser.add_argument('--device_score', action='store_true',
                         help='with --validate: decode and score on the GPU (one edit-distance kernel per batch); no softmax map is copied to the host')
     parser.add_argument('--confusions', type=int, nargs='?', const=20, default=None, metavar='K',
@@ -281,8 +283,11 @@ def main(argv=None):
             fnames = fnames[int(len(fnames) * args.train_portion):]
     if args.num_instances is not None:
         fnames = fnames[np.random.randint(0, len(fnames), min(args.num_instances, len(fnames)))]
+    if args.device_decode and not args.device_ingest:
+        raise SystemExit("--device_decode goes with --device_ingest")
     if args.device_ingest:
-        reader = U.DeviceReadf(img_size=img_size, normed=True, batch_size=args.batch_size, transform_p=0., classes=classes, max_len=args.max_len, workers=args.workers)
+        reader = U.DeviceReadf(img_size=img_size, normed=True, batch_size=args.batch_size, transform_p=0., classes=classes, max_len=args.max_len, workers=args.workers,
+                               device_decode=args.device_decode)
     else:
         reader = U.Readf(img_size=img_size, normed=True, batch_size=args.batch_size, transform_p=0., classes=classes, max_len=args.max_len, workers=args.workers)
     length = len(fnames)

@@ -49,6 +49,8 @@ def build_parser():
                         help='image decoding processes feeding the generator (0 = the reference\'s single-threaded loader)')
     parser.add_argument('--device_ingest', action='store_true',
                         help='build the training and validation batches on the GPU (crnn_mi355x.ingest.DeviceReadf)')
+    parser.add_argument('--device_decode', action='store_true',
+                        help='with --device_ingest: decode baseline JPEG files on the GPU too (crnn_mi355x.jpeg); other files are decoded on the host as before')
     parser.add_argument('--augment', action='store_true',
                         help='augment the training batches (crnn_mi355x.augment: warp, stroke width, blur, tone, noise; the default ranges are '
                              'placeholders); on the GPU with --device_ingest.  The validation batches are never augmented')
@@ -143,10 +145,14 @@ def main(argv=None):
     if args.augment:      # seeded per rank, so the ranks' shards are augmented differently
         policy = U.AugmentPolicy(seed=_chunk_seed(args.random_state, rank), **({} if args.augment_p is None else {"p": args.augment_p}))
 
+    if args.device_decode and not args.device_ingest:
+        raise SystemExit("--device_decode goes with --device_ingest")
+
     def make_reader(augment):
         return (U.DeviceReadf if args.device_ingest else U.Readf)(
             img_size=(args.imgh, args.imgW, 1), normed=args.norm, batch_size=args.batch_size, classes=classes, max_len=max_len, transform_p=0.7,
-            workers=args.workers, seed=args.random_state, **({} if augment is None else {"augment": augment}))
+            workers=args.workers, seed=args.random_state, **({} if augment is None else {"augment": augment}),
+            **({"device_decode": True} if args.device_decode else {}))
     if words is not None:      # seeded per rank, so the ranks draw different words and placements
         reader = U.SynthReadf(words, atlas, img_size=(args.imgh, args.imgW, 1), normed=args.norm, batch_size=args.batch_size, classes=classes,
                               max_len=max_len, policy=U.SynthPolicy(seed=_chunk_seed(args.random_state, world + rank)), augment=policy)

@@ -15,6 +15,7 @@ from crnn_mi355x.lm import CharLM, LMDecoder  # noqa: F401  (beyond the referenc
 from crnn_mi355x.align import CTCAligner, Alignment, CharSpan  # noqa: F401  (beyond the reference: character alignment on the device)
 from crnn_mi355x.data import (Readf, open_img, read_img, norm, parse_mjsynth, get_lengths, get_lexicon, make_ohe)  # noqa: F401
 from crnn_mi355x.ingest import DeviceIngest, DeviceReadf, plan_crop, box_slices  # noqa: F401  (beyond the reference: batches built on the device)
+from crnn_mi355x.jpeg import JpegDecoder, jpeg_decode_host, jpeg_gray_host  # noqa: F401  (beyond the reference: baseline JPEG decoded on the device)
 from crnn_mi355x.augment import AugmentPolicy, Augmenter, augment_host, neutral_items  # noqa: F401  (beyond the reference: training augmentation on the device)
 from crnn_mi355x.synth import GlyphAtlas, SynthPolicy, SynthReadf, WordSynth, synth_host  # noqa: F401  (beyond the reference: training words rendered on the device)
 from crnn_mi355x.detect import WordDetector, detect_words_host, reading_order  # noqa: F401  (beyond the reference: the word boxes, found on the device)

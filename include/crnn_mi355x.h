@@ -515,6 +515,63 @@ int crnn_deskew_estimate(const void* arena, long arena_bytes, const crnn_page_it
 int crnn_rotate_pages(const void* arena, long arena_bytes, const crnn_page_item* pages, const crnn_page_item* pages_dev, int P,
                       const int* index_dev, const crnn_deskew_params* prm, void* out_arena, long out_bytes, crnn_stream_t stream);
 
+/* ---- baseline JPEG files -> grey pages in a page arena (csrc/jpeg.hip; the same rule in NumPy: crnn_mi355x.jpeg.jpeg_decode_host) ---- */
+/* Per-file status: 0 or a sum of these.  UNSUPPORTED and CORRUPT come from the plan (the headers), CORRUPT and TRUNCATED from the device
+ * (the entropy-coded data).  SKIP is the caller's: set in crnn_jpeg_item.status it makes crnn_jpeg_decode leave the file and its page alone
+ * (the caller decodes it itself); it is never reported. */
+#define CRNN_JPEG_OK 0
+#define CRNN_JPEG_UNSUPPORTED 1
+#define CRNN_JPEG_CORRUPT 2
+#define CRNN_JPEG_TRUNCATED 4
+#define CRNN_JPEG_SKIP 8
+#define CRNN_JPEG_QUANT_INTS 64   /* a quantiser table in the pool: 64 int32 in natural (row-major) order */
+#define CRNN_JPEG_HUFF_INTS 548   /* a Huffman table in the pool: maxcode[18] (index = code length; -1: no code of that length), valoff[18]
+                                   * (symbol index = valoff[l] + code), the 256 symbols as int32, then the 8-bit look-ahead: for each 8-bit
+                                   * prefix, length << 8 | symbol of the code of up to 8 bits that the length search finds there, or 0 */
+#define CRNN_JPEG_POOL_INTS_PER_FILE 3480  /* 3 quantiser and 6 Huffman tables: the most one file can add to the pool */
+/* One file.  hs / vs: the sampling factors (1 component: 1, 1).  mcux x mcuy: the MCU grid; component c has (mcux hs[c]) x (mcuy vs[c]) blocks.
+ * samp_off: the file's first sample in the workspace (a multiple of 64; its components follow one another, each block-row-major there as
+ * coefficients and row-major as a plane).  qt / dc / ac: int offsets of the component's tables in the pool.  seg0, nseg: its entropy segments
+ * in the segment table (nseg = 1, or ceil(mcux mcuy / restart)).  page_off, stride: the page in the output arena (pages.h's layout). */
+typedef struct { long data_off, scan_off, scan_end, page_off, samp_off; int rows, cols, stride, ncomp, hs[3], vs[3], qt[3], dc[3], ac[3], restart, mcux, mcuy, seg0, nseg, status; } crnn_jpeg_item;
+/* One entropy-coded segment: bytes [begin, end) of the blob, MCUs mcu0 .. mcu0 + nmcu - 1 of file `item`. */
+typedef struct { long begin, end; int item, mcu0, nmcu, pad; } crnn_jpeg_seg;
+/* PLAN (host only, no GPU call).  blob: the bytes of all files; file i is blob[offs[i] : offs[i] + lens[i]].  Fills items[n]; adds the tables of
+ * the supported files to pool (int32, pool_cap ints; a table equal to one of the 16 before it is shared) and their segments to segs (seg_cap
+ * entries); the supported files' pages are laid out back to back on 16-byte boundaries, stride = cols.  totals[4] = pool ints used, segments
+ * NEEDED, arena bytes, workspace samples.  When the segments needed exceed seg_cap the call returns CRNN_ERR_ARG with totals[1] set: call again
+ * with a table of that size.  Supported: SOF0 / SOF1 at 8 bits; 1 component, or 3 as YCbCr with chroma 1x1 and luma 1x1, 2x1 or 2x2; 8-bit
+ * quantiser tables; one interleaved scan; restart markers; fill bytes.  Everything else that parses, and a file that does not begin with a JPEG's
+ * SOI (a PNG), gets the per-file status CRNN_JPEG_UNSUPPORTED (rows and cols are filled when the frame header was reached); headers cut short
+ * or inconsistent (a segment length past the end, a missing table, Huffman counts that overflow the code space, zero dimensions, no scan) get
+ * CRNN_JPEG_CORRUPT.  A scan that ends early is NOT a header fault: its missing segments are planned empty, and the device reports
+ * CRNN_JPEG_TRUNCATED.  CRNN_ERR_ARG (-2): a null pointer, n < 1, a negative offset or length, a file outside the blob, a pool too small. */
+int crnn_jpeg_plan(const void* blob, long blob_bytes, const long* offs, const long* lens, int n, crnn_jpeg_item* items, int* pool, long pool_cap,
+                   crnn_jpeg_seg* segs, long seg_cap, long* totals);
+/* DECODE (device).  blob_dev, pool_dev, items_dev, segs_dev: device copies of what the plan made (items / segs: the host tables, validated
+ * before anything is launched -- every offset, count and table index the kernels use; the caller may have set CRNN_JPEG_SKIP or moved pages).
+ * Three launches after the workspace's coefficients are zeroed:
+ * 1 ENTROPY, one lane per segment: baseline Huffman decode with byte unstuffing (FF xx -> FF, xx skipped), DC prediction from 0 per segment,
+ *   extend(v, s) = v >= 2^(s-1) ? v : v - 2^s + 1, int16 coefficients in natural order.  A code is the shortest length l whose first l bits are
+ *   <= maxcode[l] (the look-ahead answers for l <= 8).  Every loop is bounded by the plan's counts (MCUs per
+ *   segment, blocks per MCU, 63 AC positions, 16 code lengths); every byte index is inside the segment: bits past its end read as zero, and
+ *   consuming one sets CRNN_JPEG_TRUNCATED.  No code of <= 16 bits, a DC size above 11, or a run past position 63 sets CRNN_JPEG_CORRUPT and
+ *   ends that lane's segment.
+ * 2 DEQUANTISE + IDCT, eight lanes per block: jidctint's islow (CONST_BITS 13, PASS1_BITS 2) in uint32 arithmetic, columns then rows, descaled
+ *   by arithmetic shifts of the wrapped value, + 128, clamped to 0..255 (libjpeg's range-limit table wraps where this saturates: equal for
+ *   every file an encoder makes from 8-bit pixels).
+ * 3 UPSAMPLE + COLOUR + GREY: libjpeg's "fancy" h2v1 / h2v2 upsampling (plain replication when the chroma plane is at most 2 columns wide),
+ *   YCbCr -> RGB in 16-bit fixed point, grey = floor(fma(0.114, B, fma(0.587, G, 0.299 R)) + 0.5) in float64; 1 component: Y.  The page of a
+ *   file whose status is non-zero by then is zero-filled; a SKIP or plan-refused file's page is not written at all.
+ * status_dev [n] int32: the item's status without SKIP, or-ed with what the lanes found.  Integer atomics (or) only: two calls agree bit for bit.
+ * ws: crnn_jpeg_workspace_bytes(samples) = 3 bytes per sample (int16 coefficients, uint8 planes), 16-byte aligned.
+ * CRNN_ERR_ARG (-2), nothing launched: a null pointer, n < 1, an item, segment or table index out of range, a page outside out_arena
+ * (pages.h), a short or misaligned workspace.  CRNN_ERR_UNSUPPORTED (-3): more than 2^31 samples in one call. */
+size_t crnn_jpeg_workspace_bytes(long samples);
+int crnn_jpeg_decode(const void* blob_dev, long blob_bytes, const crnn_jpeg_item* items, const crnn_jpeg_item* items_dev, int n,
+                     const crnn_jpeg_seg* segs, const crnn_jpeg_seg* segs_dev, long nsegs, const int* pool_dev, long pool_ints,
+                     void* out_arena, long out_bytes, int* status_dev, void* ws, size_t ws_bytes, crnn_stream_t stream);
+
 /* ---- individual operators (unit-tested one by one; the drivers above chain them) --------------------------- */
 /* mode 0: C=A[M,K]*B[K,N]; 1: C=A[M,K]*Bt[N,K]^T; 2: C=At[K,M]^T*B[K,N].  bias[N]|NULL, act 0|1(relu),
  * accumulate: C+=, permP: out_row=(m%P)*(M/P)+m/P (0=off), scratch: split-reduction partials (may be NULL) */
