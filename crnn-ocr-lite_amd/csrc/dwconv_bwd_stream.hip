@@ -592,6 +592,7 @@ struct DbsGeom { int nsplit, nwgb, HB, cols, cppw; bool ok; };
 DbsGeom dbs_geom(int B, int H, int W, int C, int epc = 8) {   // epc: elements per 16-byte chunk (8 bf16 | 4 fp32)
   DbsGeom g; g.ok = false; g.nsplit = g.nwgb = g.HB = g.cols = g.cppw = 0;
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return g;
+  if ((long)H * W * C * (16 / epc) >= (1L << 31)) return g;   // a sample stays below 2^31 bytes: part of the shape rule, so the queries state all of it
   const long cols1 = (long)W * C / epc;
   int ns = 0;
   for (int n = 1; n <= C / epc; ++n) {
@@ -616,131 +617,110 @@ DbsGeom dbs_geom(int B, int H, int W, int C, int epc = 8) {   // epc: elements p
   return g;
 }
 
+// prologue form: the keep bytes of a stage travel as whole dwords (32 / epc columns of one pixel: 4 bf16 | 8 fp32; bf16 maps: whole dwords per image row
+// too), fewer than 2^31 dropout groups
+bool dbs_pro_ok(const DbsGeom& g, int B, int H, int W, int C, int epc) {
+  const int n = 32 / epc;
+  return g.ok && g.cppw % n == 0 && g.cols % n == 0 && (epc != 8 || (W * (C / 8)) % 4 == 0) && (long)B * H * W * (C / 8) < (1L << 31);
+}
+int dbs_epc(int dtype) { return dtype == CRNN_BF16 ? 8 : dtype == CRNN_F32 ? 4 : 0; }   // elements per 16-byte chunk, 0: not a storage type
+
+// one latch of CRNN_LDS_ATTR per kernel symbol: the launch stays a template on the kernel's parameters
+template <bool PRO, bool DROP, bool STATS, bool F32>
+int dbs_launch(const DbsParams& p, const DbsGeom& g, int B, hipStream_t stream) {
+  constexpr bool DXS = STATS && F32;
+  constexpr int KD = PRO ? kD + 1 : kD;                 // (prologue form: one more stage in flight)
+  constexpr int block = (STATS && !F32) ? 768 : 704;    // (the statistics wave)
+  constexpr int lds = PRO ? DbsLds<kD + 1, STATS, DXS>::Total : DbsLds<kD>::XtOff;
+  CRNN_LDS_ATTR((dw_bwd_stream_kernel<KD, PRO, DROP, STATS, F32>), lds);
+  hipLaunchKernelGGL((dw_bwd_stream_kernel<KD, PRO, DROP, STATS, F32>), dim3(B * g.nwgb * g.nsplit), dim3(block), lds, stream, p);
+  CRNN_LAUNCH_CHECK();
+  return CRNN_OK;
+}
+template <bool F32>
+int dbs_launch_dt(const DbsParams& p, const DbsGeom& g, int B, hipStream_t stream) {
+  if (!p.pro_bn) return dbs_launch<false, false, false, F32>(p, g, B, stream);
+  const bool drop = p.rate > 0.f;
+  if (p.bn2_partials) return drop ? dbs_launch<true, true, true, F32>(p, g, B, stream) : dbs_launch<true, false, true, F32>(p, g, B, stream);
+  return drop ? dbs_launch<true, true, false, F32>(p, g, B, stream) : dbs_launch<true, false, false, F32>(p, g, B, stream);
+}
+
+// The one launcher behind every entry point below (they keep the CRNN_ERR_ARG checks of their own arguments).  pro_bn != NULL: the prologue form (xin = q,
+// `rate`, `keep`, bn2_partials), else the plain form.  CRNN_ERR_UNSUPPORTED for a shape the queries refuse and for an operand that is not 16-byte
+// aligned (keep: 4-byte).
+int dbs_run(const void* d, const void* da, const float* bnstate, const float* coef, const void* xin, const float* pro_bn, float rate, const void* keep,
+            const float* k, void* dx, float* dk, float* scratch, float* bn2_partials, int B, int H, int W, int C, int epc, hipStream_t stream) {
+  const DbsGeom g = dbs_geom(B, H, W, C, epc);
+  if (pro_bn ? !dbs_pro_ok(g, B, H, W, C, epc) : !g.ok) return CRNN_ERR_UNSUPPORTED;
+  if ((((uintptr_t)d | (uintptr_t)da | (uintptr_t)xin | (uintptr_t)dx | (uintptr_t)bnstate | (uintptr_t)coef | (uintptr_t)k | (uintptr_t)pro_bn) & 15) ||
+      ((uintptr_t)keep & 3))
+    return CRNN_ERR_UNSUPPORTED;
+  DbsParams p;
+  p.d = (const unsigned char*)d; p.da = (const unsigned char*)da; p.xin = (const unsigned char*)xin; p.dx = (unsigned char*)dx;
+  p.bnstate = bnstate; p.coef = coef; p.k = k; p.partials = scratch;
+  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.nwgb = g.nwgb; p.nsplit = g.nsplit; p.cols = g.cols; p.cppw = g.cppw; p.rowbytes = W * C * (16 / epc);
+  p.pro_bn = pro_bn; p.keep = (const unsigned char*)keep; p.rate = rate; p.bn2_partials = bn2_partials;
+  CRNN_TRY(epc == 4 ? dbs_launch_dt<true>(p, g, B, stream) : dbs_launch_dt<false>(p, g, B, stream));
+  return crnn_partials_sum(scratch, B * g.nwgb, 9 * C, dk, 1.f, stream);
+}
+
 }  // namespace
 
-// CRNN_OK when crnn_dwconv3x3_bwd_stream takes the shape (W * C / 8 sixteen-byte columns split over whole channel octets into
-// workgroups of 129..320 columns: every block of the CRNN at image widths 32, 48, 64), else CRNN_ERR_UNSUPPORTED -> crnn_dwconv3x3_bwd_fused.
-extern "C" int crnn_dwconv_bwd_stream_supported(int B, int H, int W, int C) { return dbs_geom(B, H, W, C).ok ? CRNN_OK : CRNN_ERR_UNSUPPORTED; }
-// rows of [9][C] weight-gradient partials the launch writes (scratch = rows * 9 * C floats)
-extern "C" int crnn_dwconv_bwd_stream_rows(int B, int H, int W, int C) { DbsGeom g = dbs_geom(B, H, W, C); return g.ok ? B * g.nwgb : 0; }
-// Same contract as crnn_dwconv3x3_bwd_fused (d, da, xin, dx: bf16 [B,H,W,C]; bnstate = [mean|var|scale|shift]; coef = [c1|c2];
-// k [9][C]; dk [9][C] out); dx bit-identical, dk to the summation order of its partial sums.
-extern "C" int crnn_dwconv3x3_bwd_stream(const void* d, const void* da, const float* bnstate, const float* coef, const void* xin, const float* k,
-                                         void* dx, float* dk, float* scratch, int B, int H, int W, int C, hipStream_t stream) {
-  if (!d || !da || !bnstate || !coef || !xin || !k || !dx || !dk || !scratch) return CRNN_ERR_ARG;
-  const DbsGeom g = dbs_geom(B, H, W, C);
-  if (!g.ok) return CRNN_ERR_UNSUPPORTED;
-  if ((((uintptr_t)d | (uintptr_t)da | (uintptr_t)xin | (uintptr_t)dx | (uintptr_t)bnstate | (uintptr_t)coef | (uintptr_t)k) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)H * W * C * 2 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
-  DbsParams p;
-  p.d = (const unsigned char*)d; p.da = (const unsigned char*)da; p.xin = (const unsigned char*)xin; p.dx = (unsigned char*)dx;
-  p.bnstate = bnstate; p.coef = coef; p.k = k; p.partials = scratch;
-  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.nwgb = g.nwgb; p.nsplit = g.nsplit; p.cols = g.cols; p.cppw = g.cppw; p.rowbytes = W * C * 2;
-  p.pro_bn = nullptr; p.keep = nullptr; p.rate = 0.f; p.bn2_partials = nullptr;
-  CRNN_LDS_ATTR((dw_bwd_stream_kernel<kD, false, false>), DbsLds<kD>::XtOff);
-  hipLaunchKernelGGL((dw_bwd_stream_kernel<kD, false, false>), dim3(B * g.nwgb * g.nsplit), dim3(704), DbsLds<kD>::XtOff, stream, p);
-  CRNN_LAUNCH_CHECK();
-  return crnn_partials_sum(scratch, B * g.nwgb, 9 * C, dk, 1.f, stream);
-}
-// The same stage on fp32 tensors (dtype CRNN_F32; CRNN_BF16 = the entry points above): four channels per lane, W * C / 4 columns split into
-// workgroups of 129..320 -- the parity mode's crnn_bn_bwd_apply_ex + crnn_dwconv3x3_wgrad_ex + crnn_dwconv3x3_fwd_ex(flip) in one pass over
-// d, da, xin (4 tensor passes instead of 7); dx bit-identical to that sequence, dk to the summation order of its partial sums.
+// Entry points (contract: include/crnn_mi355x.h).  The form with a `dtype` is the definition; the form without is the same call with CRNN_BF16.
+// An unknown dtype: CRNN_ERR_ARG from the launchers and the _supported queries, 0 rows.
+//
+// _supported: CRNN_OK when the shape is taken (dbs_geom: W * C / 8 (fp32: / 4) sixteen-byte columns split over whole channel groups into workgroups of
+// 129..320 columns -- every block of the CRNN at image widths 32, 48, 64 --, a sample below 2^31 bytes), else CRNN_ERR_UNSUPPORTED ->
+// crnn_dwconv3x3_bwd_fused (bf16) / the three-kernel sequence.
 extern "C" int crnn_dwconv_bwd_stream_supported_ex(int B, int H, int W, int C, int dtype) {
-  if (dtype == CRNN_BF16) return crnn_dwconv_bwd_stream_supported(B, H, W, C);
-  if (dtype != CRNN_F32) return CRNN_ERR_ARG;
-  return dbs_geom(B, H, W, C, 4).ok ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+  const int epc = dbs_epc(dtype);
+  if (!epc) return CRNN_ERR_ARG;
+  return dbs_geom(B, H, W, C, epc).ok ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
 }
+// rows of [9][C] weight-gradient partials the launch writes (scratch = rows * 9 * C floats)
 extern "C" int crnn_dwconv_bwd_stream_rows_ex(int B, int H, int W, int C, int dtype) {
-  if (dtype == CRNN_BF16) return crnn_dwconv_bwd_stream_rows(B, H, W, C);
-  DbsGeom g = dbs_geom(B, H, W, C, 4); return (dtype == CRNN_F32 && g.ok) ? B * g.nwgb : 0;
+  const int epc = dbs_epc(dtype);
+  if (!epc) return 0;
+  const DbsGeom g = dbs_geom(B, H, W, C, epc);
+  return g.ok ? B * g.nwgb : 0;
 }
+extern "C" int crnn_dwconv_bwd_stream_pro_supported_ex(int B, int H, int W, int C, int dtype) {
+  const int epc = dbs_epc(dtype);
+  if (!epc) return CRNN_ERR_ARG;
+  return dbs_pro_ok(dbs_geom(B, H, W, C, epc), B, H, W, C, epc) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
+// Same contract as crnn_dwconv3x3_bwd_fused (d, da, xin, dx: [B,H,W,C] of the storage type; bnstate = [mean|var|scale|shift]; coef = [c1|c2];
+// k [9][C]; dk [9][C] out); dx bit-identical, dk to the summation order of its partial sums.  fp32 tensors (four channels per lane): the parity mode's
+// crnn_bn_bwd_apply_ex + crnn_dwconv3x3_wgrad_ex + crnn_dwconv3x3_fwd_ex(flip) in one pass over d, da, xin (4 tensor passes instead of 7).
 extern "C" int crnn_dwconv3x3_bwd_stream_ex(const void* d, const void* da, const float* bnstate, const float* coef, const void* xin, const float* k,
                                             void* dx, float* dk, float* scratch, int B, int H, int W, int C, int dtype, hipStream_t stream) {
-  if (dtype == CRNN_BF16) return crnn_dwconv3x3_bwd_stream(d, da, bnstate, coef, xin, k, dx, dk, scratch, B, H, W, C, stream);
-  if (dtype != CRNN_F32 || !d || !da || !bnstate || !coef || !xin || !k || !dx || !dk || !scratch) return CRNN_ERR_ARG;
-  const DbsGeom g = dbs_geom(B, H, W, C, 4);
-  if (!g.ok) return CRNN_ERR_UNSUPPORTED;
-  if ((((uintptr_t)d | (uintptr_t)da | (uintptr_t)xin | (uintptr_t)dx | (uintptr_t)bnstate | (uintptr_t)coef | (uintptr_t)k) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)H * W * C * 4 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
-  DbsParams p;
-  p.d = (const unsigned char*)d; p.da = (const unsigned char*)da; p.xin = (const unsigned char*)xin; p.dx = (unsigned char*)dx;
-  p.bnstate = bnstate; p.coef = coef; p.k = k; p.partials = scratch;
-  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.nwgb = g.nwgb; p.nsplit = g.nsplit; p.cols = g.cols; p.cppw = g.cppw; p.rowbytes = W * C * 4;
-  p.pro_bn = nullptr; p.keep = nullptr; p.rate = 0.f; p.bn2_partials = nullptr;
-  CRNN_LDS_ATTR((dw_bwd_stream_kernel<kD, false, false, false, true>), DbsLds<kD>::XtOff);
-  hipLaunchKernelGGL((dw_bwd_stream_kernel<kD, false, false, false, true>), dim3(B * g.nwgb * g.nsplit), dim3(704), DbsLds<kD>::XtOff, stream, p);
-  CRNN_LAUNCH_CHECK();
-  return crnn_partials_sum(scratch, B * g.nwgb, 9 * C, dk, 1.f, stream);
+  const int epc = dbs_epc(dtype);
+  if (!epc || !d || !da || !bnstate || !coef || !xin || !k || !dx || !dk || !scratch) return CRNN_ERR_ARG;
+  return dbs_run(d, da, bnstate, coef, xin, nullptr, 0.f, nullptr, k, dx, dk, scratch, nullptr, B, H, W, C, epc, stream);
 }
-// Prologue form: xin = q of the previous block ([B,H,W,C] bf16), pro_bnstate = its BatchNorm-2 state, keep = the keep bytes of the dropout site of
-// its output (crnn_dropout_keep_bytes; NULL allowed when rate == 0): x = Dropout(ReLU6(q * scale + shift)) is re-formed in LDS instead of read.  dx / dk bit-identical to
-// crnn_dwconv3x3_bwd_stream on the materialised x.  Same shape rule + fewer than 2^32 dropout groups (B*H*W*C/8).
-extern "C" int crnn_dwconv_bwd_stream_pro_supported(int B, int H, int W, int C) {
-  const DbsGeom g = dbs_geom(B, H, W, C);       // (+ the keep bytes of a stage travel as whole dwords: 4 columns of one pixel)
-  return (g.ok && g.cppw % 4 == 0 && g.cols % 4 == 0 && (W * (C / 8)) % 4 == 0 && (long)B * H * W * (C / 8) < (1L << 31)) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
-}
-// bn2_stat_partials != NULL: [crnn_dwconv_bwd_stream_rows][2][C] partial sums (sum gy | sum gy * xhat) of the PRODUCER's BatchNorm-2 backward, gy = dx routed
+// Prologue form: xin = q of the previous block ([B,H,W,C]), pro_bnstate = its BatchNorm-2 state, keep = the keep bytes of the dropout site of its output
+// (crnn_dropout_keep_bytes, one per 8 elements -- fp32 tensors read them as nibbles; NULL allowed when rate == 0): x = Dropout(ReLU6(q * scale + shift)) is
+// re-formed in LDS instead of read.  dx / dk bit-identical to the plain form on the materialised x.
+// bn2_stat_partials != NULL: [crnn_dwconv_bwd_stream_rows_ex][2][C] partial sums (sum gy | sum gy * xhat) of the PRODUCER's BatchNorm-2 backward, gy = dx routed
 // through the dropout mask and the ReLU6 gate of q -- the statistics pass of crnn_bn_bwd_ex(q, dx, pro_bnstate, ..., rate, seed, layer) (finish with
 // crnn_bn_bwd_finalize, then crnn_bn_bwd_apply_ex); the same sums in another order.
-extern "C" int crnn_dwconv3x3_bwd_stream_pro(const void* d, const void* da, const float* bnstate, const float* coef, const void* q, const float* pro_bnstate,
-                                             float rate, const void* keep, const float* k, void* dx, float* dk, float* scratch, float* bn2_stat_partials,
-                                             int B, int H, int W, int C, hipStream_t stream) {
-  if (!d || !da || !bnstate || !coef || !q || !pro_bnstate || !k || !dx || !dk || !scratch || rate < 0.f || rate >= 1.f || (rate > 0.f && !keep)) return CRNN_ERR_ARG;
-  const DbsGeom g = dbs_geom(B, H, W, C);
-  if (crnn_dwconv_bwd_stream_pro_supported(B, H, W, C) != CRNN_OK) return CRNN_ERR_UNSUPPORTED;
-  if ((((uintptr_t)d | (uintptr_t)da | (uintptr_t)q | (uintptr_t)dx | (uintptr_t)bnstate | (uintptr_t)coef | (uintptr_t)k | (uintptr_t)pro_bnstate) & 15) || ((uintptr_t)keep & 3)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)H * W * C * 2 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
-  DbsParams p;
-  p.d = (const unsigned char*)d; p.da = (const unsigned char*)da; p.xin = (const unsigned char*)q; p.dx = (unsigned char*)dx;
-  p.bnstate = bnstate; p.coef = coef; p.k = k; p.partials = scratch;
-  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.nwgb = g.nwgb; p.nsplit = g.nsplit; p.cols = g.cols; p.cppw = g.cppw; p.rowbytes = W * C * 2;
-  p.pro_bn = pro_bnstate; p.keep = (const unsigned char*)keep; p.rate = rate; p.bn2_partials = bn2_stat_partials;
-  constexpr int KD = kD + 1;
-  const dim3 grid(B * g.nwgb * g.nsplit);
-#define DBS_PRO_LAUNCH(DROP, STATS)                                                                                     \
-  do {                                                                                                                  \
-    CRNN_LDS_ATTR((dw_bwd_stream_kernel<KD, true, DROP, STATS>), (DbsLds<KD, STATS>::Total));                           \
-    hipLaunchKernelGGL((dw_bwd_stream_kernel<KD, true, DROP, STATS>), grid, dim3(STATS ? 768 : 704), (DbsLds<KD, STATS>::Total), stream, p); \
-  } while (0)
-  if (bn2_stat_partials) { if (rate > 0.f) DBS_PRO_LAUNCH(true, true); else DBS_PRO_LAUNCH(false, true); }
-  else { if (rate > 0.f) DBS_PRO_LAUNCH(true, false); else DBS_PRO_LAUNCH(false, false); }
-#undef DBS_PRO_LAUNCH
-  CRNN_LAUNCH_CHECK();
-  return crnn_partials_sum(scratch, B * g.nwgb, 9 * C, dk, 1.f, stream);
-}
-// The prologue form by storage type (CRNN_BF16 = the entry points above; CRNN_F32, round 4 -- the parity mode): d, da, q, dx fp32, four channels per
-// lane, the keep bytes (one per 8 elements) as nibbles.  dx / dk / the statistics partials as for the bf16 form, against the fp32 sequence
-// crnn_bn_act_pool_drop_ex(q -> x) + crnn_dwconv3x3_bwd_stream_ex(x) [+ crnn_bn_bwd_ex's statistics pass].
-extern "C" int crnn_dwconv_bwd_stream_pro_supported_ex(int B, int H, int W, int C, int dtype) {
-  if (dtype == CRNN_BF16) return crnn_dwconv_bwd_stream_pro_supported(B, H, W, C);
-  if (dtype != CRNN_F32) return CRNN_ERR_ARG;
-  const DbsGeom g = dbs_geom(B, H, W, C, 4);   // (+ the keep bytes of a stage travel as whole dwords: 8 columns of one pixel)
-  return (g.ok && g.cppw % 8 == 0 && g.cols % 8 == 0 && (long)B * H * W * (C / 8) < (1L << 31)) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
-}
 extern "C" int crnn_dwconv3x3_bwd_stream_pro_ex(const void* d, const void* da, const float* bnstate, const float* coef, const void* q, const float* pro_bnstate,
                                                 float rate, const void* keep, const float* k, void* dx, float* dk, float* scratch, float* bn2_stat_partials,
                                                 int B, int H, int W, int C, int dtype, hipStream_t stream) {
-  if (dtype == CRNN_BF16) return crnn_dwconv3x3_bwd_stream_pro(d, da, bnstate, coef, q, pro_bnstate, rate, keep, k, dx, dk, scratch, bn2_stat_partials, B, H, W, C, stream);
-  if (dtype != CRNN_F32 || !d || !da || !bnstate || !coef || !q || !pro_bnstate || !k || !dx || !dk || !scratch || rate < 0.f || rate >= 1.f || (rate > 0.f && !keep)) return CRNN_ERR_ARG;
-  const DbsGeom g = dbs_geom(B, H, W, C, 4);
-  if (crnn_dwconv_bwd_stream_pro_supported_ex(B, H, W, C, CRNN_F32) != CRNN_OK) return CRNN_ERR_UNSUPPORTED;
-  if ((((uintptr_t)d | (uintptr_t)da | (uintptr_t)q | (uintptr_t)dx | (uintptr_t)bnstate | (uintptr_t)coef | (uintptr_t)k | (uintptr_t)pro_bnstate) & 15) || ((uintptr_t)keep & 3)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)H * W * C * 4 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
-  DbsParams p;
-  p.d = (const unsigned char*)d; p.da = (const unsigned char*)da; p.xin = (const unsigned char*)q; p.dx = (unsigned char*)dx;
-  p.bnstate = bnstate; p.coef = coef; p.k = k; p.partials = scratch;
-  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.nwgb = g.nwgb; p.nsplit = g.nsplit; p.cols = g.cols; p.cppw = g.cppw; p.rowbytes = W * C * 4;
-  p.pro_bn = pro_bnstate; p.keep = (const unsigned char*)keep; p.rate = rate; p.bn2_partials = bn2_stat_partials;
-  constexpr int KD = kD + 1;
-  const dim3 grid(B * g.nwgb * g.nsplit);
-#define DBS_PRO_LAUNCH(DROP, STATS)                                                                                     \
-  do {                                                                                                                  \
-    CRNN_LDS_ATTR((dw_bwd_stream_kernel<KD, true, DROP, STATS, true>), (DbsLds<KD, STATS, STATS>::Total));              \
-    hipLaunchKernelGGL((dw_bwd_stream_kernel<KD, true, DROP, STATS, true>), grid, dim3(704), (DbsLds<KD, STATS, STATS>::Total), stream, p); \
-  } while (0)
-  if (bn2_stat_partials) { if (rate > 0.f) DBS_PRO_LAUNCH(true, true); else DBS_PRO_LAUNCH(false, true); }
-  else { if (rate > 0.f) DBS_PRO_LAUNCH(true, false); else DBS_PRO_LAUNCH(false, false); }
-#undef DBS_PRO_LAUNCH
-  CRNN_LAUNCH_CHECK();
-  return crnn_partials_sum(scratch, B * g.nwgb, 9 * C, dk, 1.f, stream);
+  const int epc = dbs_epc(dtype);
+  if (!epc || !d || !da || !bnstate || !coef || !q || !pro_bnstate || !k || !dx || !dk || !scratch || rate < 0.f || rate >= 1.f || (rate > 0.f && !keep)) return CRNN_ERR_ARG;
+  return dbs_run(d, da, bnstate, coef, q, pro_bnstate, rate, keep, k, dx, dk, scratch, bn2_stat_partials, B, H, W, C, epc, stream);
+}
+// the untyped forms: CRNN_BF16
+extern "C" int crnn_dwconv_bwd_stream_supported(int B, int H, int W, int C) { return crnn_dwconv_bwd_stream_supported_ex(B, H, W, C, CRNN_BF16); }
+extern "C" int crnn_dwconv_bwd_stream_rows(int B, int H, int W, int C) { return crnn_dwconv_bwd_stream_rows_ex(B, H, W, C, CRNN_BF16); }
+extern "C" int crnn_dwconv_bwd_stream_pro_supported(int B, int H, int W, int C) { return crnn_dwconv_bwd_stream_pro_supported_ex(B, H, W, C, CRNN_BF16); }
+extern "C" int crnn_dwconv3x3_bwd_stream(const void* d, const void* da, const float* bnstate, const float* coef, const void* xin, const float* k,
+                                         void* dx, float* dk, float* scratch, int B, int H, int W, int C, hipStream_t stream) {
+  return crnn_dwconv3x3_bwd_stream_ex(d, da, bnstate, coef, xin, k, dx, dk, scratch, B, H, W, C, CRNN_BF16, stream);
+}
+extern "C" int crnn_dwconv3x3_bwd_stream_pro(const void* d, const void* da, const float* bnstate, const float* coef, const void* q, const float* pro_bnstate,
+                                             float rate, const void* keep, const float* k, void* dx, float* dk, float* scratch, float* bn2_stat_partials,
+                                             int B, int H, int W, int C, hipStream_t stream) {
+  return crnn_dwconv3x3_bwd_stream_pro_ex(d, da, bnstate, coef, q, pro_bnstate, rate, keep, k, dx, dk, scratch, bn2_stat_partials, B, H, W, C, CRNN_BF16, stream);
 }

@@ -398,6 +398,7 @@ constexpr int kDwsMinWaves = 5;      // step rows that fill fewer compute waves 
 DwsGeom dws_geom(int B, int H, int W, int C, int es = 2) {
   DwsGeom g; g.ok = false; g.NS = g.nwgb = g.HB = g.cols = g.ncw = g.cppw = 0; g.nsplit = 1; g.xstride = 1;
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return g;
+  if ((long)H * W * C * es >= (1L << 31)) return g;   // a sample stays below 2^31 bytes: part of the shape rule, so the queries state all of it
   const int epc = 16 / es;
   int ns = 0;
   for (int n = 1; n <= C / 8; ++n) {               // smallest number of channel ranges that fits the step row
@@ -464,13 +465,55 @@ int dws_launch_pro(const DwsParams& p, const DwsGeom& g, int B, hipStream_t stre
   return CRNN_OK;
 }
 
+int dws_es(int dtype) { return dtype == CRNN_BF16 ? 2 : dtype == CRNN_F32 ? 4 : 0; }   // bytes per element, 0: not a storage type
+
+// The one launcher behind every entry point below (they keep the CRNN_ERR_ARG checks of their own arguments).  pro_bn != NULL: the prologue form (x = q,
+// `rate`, `keep`), else the plain form; bnstate != NULL: the inference epilogue (bf16 maps only: the entry points pass it for es == 2 alone).
+// CRNN_ERR_UNSUPPORTED for a shape the queries refuse and for an operand that is not 16-byte aligned (keep: 4-byte).
+int dws_run(const void* x, const float* k, void* out, float* stat_partials, const float* bnstate, const float* pro_bn, float rate, const void* keep,
+            int B, int H, int W, int C, int flip, int out_order, int es, hipStream_t stream) {
+  const DwsGeom g = dws_geom(B, H, W, C, es);
+  if (pro_bn ? !dws_pro_ok(g, B, H, W, C, es) : !g.ok) return CRNN_ERR_UNSUPPORTED;
+  if ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)k | (uintptr_t)bnstate | (uintptr_t)pro_bn) & 15) || ((uintptr_t)keep & 3)) return CRNN_ERR_UNSUPPORTED;
+  DwsParams p;
+  p.x = (const unsigned char*)x; p.k = k; p.out = (unsigned char*)out; p.partials = bnstate ? nullptr : stat_partials; p.bnstate = bnstate;
+  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.NS = g.NS; p.nwgb = g.nwgb; p.flip = flip; p.cols = g.cols; p.rowbytes = W * C * es; p.wmaj = out_order;
+  p.nsplit = g.nsplit; p.cppw = g.cppw; p.xstride = g.xstride;
+  p.pro_bn = pro_bn; p.keep = (const unsigned char*)keep; p.rate = rate;
+  const bool f32 = es == 4, drop = rate > 0.f;
+  // exactly these instantiations: the prologue form on the nine-wave step row, the inference epilogue on bf16 maps
+  if (pro_bn) {
+    if (f32) return drop ? dws_launch_pro<true, true>(p, g, B, stream) : dws_launch_pro<false, true>(p, g, B, stream);
+    return drop ? dws_launch_pro<true>(p, g, B, stream) : dws_launch_pro<false>(p, g, B, stream);
+  }
+  if (f32) return dws_launch<false, true>(p, g, B, stream);
+  return bnstate ? dws_launch<true>(p, g, B, stream) : dws_launch<false>(p, g, B, stream);
+}
+
 }  // namespace
 
-// CRNN_OK when crnn_dwconv3x3_fwd_stream takes the shape (bf16 storage; dws_geom: 257..576 sixteen-byte columns per step row after cutting the row into
-// channel ranges / laying bands side by side), else CRNN_ERR_UNSUPPORTED: the caller uses the halo-tile kernel (crnn_dwconv3x3_fwd_ex).
-extern "C" int crnn_dwconv_fwd_stream_supported(int B, int H, int W, int C) { return dws_geom(B, H, W, C).ok ? CRNN_OK : CRNN_ERR_UNSUPPORTED; }
-// rows [2][C] of statistics partials the launch writes (one per workgroup)
-extern "C" int crnn_dwconv_fwd_stream_rows(int B, int H, int W, int C) { DwsGeom g = dws_geom(B, H, W, C); return g.ok ? B * g.nwgb : 0; }
+// Entry points (contract: include/crnn_mi355x.h).  The form with a `dtype` is the definition; the form without is the same call with CRNN_BF16.
+// An unknown dtype: CRNN_ERR_ARG from the launchers and the _supported queries, 0 rows.
+//
+// _supported: CRNN_OK when the shape is taken (dws_geom: 257..576 sixteen-byte columns per step row after cutting the row into channel ranges / laying
+// bands side by side, a sample below 2^31 bytes), else CRNN_ERR_UNSUPPORTED: the caller uses the halo-tile kernel (crnn_dwconv3x3_fwd_ex).
+extern "C" int crnn_dwconv_fwd_stream_supported_ex(int B, int H, int W, int C, int dtype) {
+  const int es = dws_es(dtype);
+  if (!es) return CRNN_ERR_ARG;
+  return dws_geom(B, H, W, C, es).ok ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
+// rows [2][C] of statistics partials the launch writes (one per workgroup band)
+extern "C" int crnn_dwconv_fwd_stream_rows_ex(int B, int H, int W, int C, int dtype) {
+  const int es = dws_es(dtype);
+  if (!es) return 0;
+  const DwsGeom g = dws_geom(B, H, W, C, es);
+  return g.ok ? B * g.nwgb : 0;
+}
+extern "C" int crnn_dwconv_fwd_stream_pro_supported_ex(int B, int H, int W, int C, int dtype) {
+  const int es = dws_es(dtype);
+  if (!es) return CRNN_ERR_ARG;
+  return dws_pro_ok(dws_geom(B, H, W, C, es), B, H, W, C, es) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 // out = dwconv3x3(x, k[9][C]) on bf16 NHWC maps (flip = 1: the data gradient).  stat_partials != NULL: [rows][2][C] sums / sums of squares of
 // the fp32 results (BatchNorm batch statistics); bnstate != NULL ([mean|var|scale|shift]): out = ReLU6(conv * scale + shift) (inference), no
 // statistics.  Results bit-identical to crnn_dwconv3x3_fwd_ex / crnn_dwconv3x3_bn_relu6_fwd.
@@ -481,85 +524,37 @@ extern "C" int crnn_dwconv3x3_fwd_stream_ex(const void* x, const float* k, void*
                                             int C, int flip, int out_order, hipStream_t stream) {
   if (!x || !k || !out || out_order < 0 || out_order > 1) return CRNN_ERR_ARG;
   if (out_order && (!bnstate || (H & 1) || (W & 1))) return CRNN_ERR_ARG;
-  DwsGeom g = dws_geom(B, H, W, C);
-  if (!g.ok || (((uintptr_t)x | (uintptr_t)out | (uintptr_t)k | (uintptr_t)bnstate) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)H * W * C * 2 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
-  DwsParams p;
-  p.x = (const unsigned char*)x; p.k = k; p.out = (unsigned char*)out; p.partials = bnstate ? nullptr : stat_partials; p.bnstate = bnstate;
-  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.NS = g.NS; p.nwgb = g.nwgb; p.flip = flip; p.cols = g.cols; p.rowbytes = W * C * 2; p.wmaj = out_order;
-  p.nsplit = g.nsplit; p.cppw = g.cppw; p.xstride = g.xstride;
-  p.pro_bn = nullptr; p.keep = nullptr; p.rate = 0.f;
-  return bnstate ? dws_launch<true>(p, g, B, stream) : dws_launch<false>(p, g, B, stream);
+  return dws_run(x, k, out, stat_partials, bnstate, nullptr, 0.f, nullptr, B, H, W, C, flip, out_order, 2, stream);
+}
+// The training form by storage type (statistics, no folded BatchNorm).  fp32 maps: rows of 18 KiB as two channel ranges of 9 KiB, four channels per
+// lane; out bit-identical to crnn_dwconv3x3_fwd_ex on fp32 tensors, the statistics one partial row per workgroup band.
+extern "C" int crnn_dwconv3x3_fwd_stream_dt(const void* x, const float* k, void* out, float* stat_partials, int B, int H, int W, int C, int flip, int dtype,
+                                            hipStream_t stream) {
+  const int es = dws_es(dtype);
+  if (!es || !x || !k || !out) return CRNN_ERR_ARG;
+  return dws_run(x, k, out, stat_partials, nullptr, nullptr, 0.f, nullptr, B, H, W, C, flip, 0, es, stream);
 }
 // Prologue form (training): `q` is the previous block's pointwise output, pro_bnstate its BatchNorm-2 state [mean|var|scale|shift]; the
 // kernel convolves x = Dropout(ReLU6(q * scale + shift)) without x ever existing in HBM.  rate > 0: `keep` = the site's keep bytes
 // (crnn_dropout_keep_bytes(keep, B*H*W*C/8, rate, seed, layer) for the dropout site of crnn_bn_act_pool_drop_ex); rate == 0: keep may be NULL.
-// out / stat_partials bit-identical to crnn_bn_act_pool_drop_ex(q -> x, ph = pw = 1) + crnn_dwconv3x3_fwd_stream(x).
-// CRNN_ERR_UNSUPPORTED where crnn_dwconv_fwd_stream_pro_supported says so (the caller materialises x).
-extern "C" int crnn_dwconv_fwd_stream_pro_supported(int B, int H, int W, int C) {
-  return dws_pro_ok(dws_geom(B, H, W, C), B, H, W, C) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
-}
-extern "C" int crnn_dwconv3x3_fwd_stream_pro(const void* q, const float* pro_bnstate, float rate, const void* keep, const float* k, void* out,
-                                             float* stat_partials, int B, int H, int W, int C, hipStream_t stream) {
-  if (!q || !pro_bnstate || !k || !out || rate < 0.f || rate >= 1.f || (rate > 0.f && !keep)) return CRNN_ERR_ARG;
-  DwsGeom g = dws_geom(B, H, W, C);
-  if (!dws_pro_ok(g, B, H, W, C) || (((uintptr_t)q | (uintptr_t)out | (uintptr_t)k | (uintptr_t)pro_bnstate) & 15) || ((uintptr_t)keep & 3)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)H * W * C * 2 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
-  DwsParams p;
-  p.x = (const unsigned char*)q; p.k = k; p.out = (unsigned char*)out; p.partials = stat_partials; p.bnstate = nullptr;
-  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.NS = g.NS; p.nwgb = g.nwgb; p.flip = 0; p.cols = g.cols; p.rowbytes = W * C * 2; p.wmaj = 0;
-  p.nsplit = 1; p.cppw = C / 8;
-  p.pro_bn = pro_bnstate; p.keep = (const unsigned char*)keep; p.rate = rate;
-  return rate > 0.f ? dws_launch_pro<true>(p, g, B, stream) : dws_launch_pro<false>(p, g, B, stream);
-}
-// The training form on fp32 maps (dtype CRNN_F32; CRNN_BF16 = crnn_dwconv3x3_fwd_stream without bnstate): rows of 18 KiB as two channel ranges of
-// 9 KiB, four channels per lane.  out bit-identical to crnn_dwconv3x3_fwd_ex on fp32 tensors, the statistics one partial row per workgroup band.
-extern "C" int crnn_dwconv_fwd_stream_supported_ex(int B, int H, int W, int C, int dtype) {
-  if (dtype == CRNN_BF16) return crnn_dwconv_fwd_stream_supported(B, H, W, C);
-  if (dtype != CRNN_F32) return CRNN_ERR_ARG;
-  return dws_geom(B, H, W, C, 4).ok ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
-}
-extern "C" int crnn_dwconv3x3_fwd_stream_dt(const void* x, const float* k, void* out, float* stat_partials, int B, int H, int W, int C, int flip, int dtype,
-                                            hipStream_t stream) {
-  if (dtype == CRNN_BF16) return crnn_dwconv3x3_fwd_stream_ex(x, k, out, stat_partials, nullptr, B, H, W, C, flip, 0, stream);
-  if (dtype != CRNN_F32 || !x || !k || !out) return CRNN_ERR_ARG;
-  DwsGeom g = dws_geom(B, H, W, C, 4);
-  if (!g.ok || (((uintptr_t)x | (uintptr_t)out | (uintptr_t)k) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)H * W * C * 4 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
-  DwsParams p;
-  p.x = (const unsigned char*)x; p.k = k; p.out = (unsigned char*)out; p.partials = stat_partials; p.bnstate = nullptr;
-  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.NS = g.NS; p.nwgb = g.nwgb; p.flip = flip; p.cols = g.cols; p.rowbytes = W * C * 4; p.wmaj = 0;
-  p.nsplit = g.nsplit; p.cppw = g.cppw; p.xstride = g.xstride;
-  p.pro_bn = nullptr; p.keep = nullptr; p.rate = 0.f;
-  return dws_launch<false, true>(p, g, B, stream);
-}
-// The prologue form by storage type (dtype CRNN_BF16 = the entry points above; CRNN_F32, round 4 -- the parity mode): q, out fp32; rows of 18 KiB run as
-// two channel ranges of 9 KiB (one workgroup each), four channels per lane, the keep bytes (still one per 8 elements) as nibbles.  out / stat_partials
-// bit-identical to crnn_bn_act_pool_drop_ex(q -> x) + crnn_dwconv3x3_fwd_ex(x) on fp32 tensors (the statistics to the order of their partial sums).
-extern "C" int crnn_dwconv_fwd_stream_pro_supported_ex(int B, int H, int W, int C, int dtype) {
-  if (dtype == CRNN_BF16) return crnn_dwconv_fwd_stream_pro_supported(B, H, W, C);
-  if (dtype != CRNN_F32) return CRNN_ERR_ARG;
-  return dws_pro_ok(dws_geom(B, H, W, C, 4), B, H, W, C, 4) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
-}
-extern "C" int crnn_dwconv_fwd_stream_rows_ex(int B, int H, int W, int C, int dtype) {
-  if (dtype == CRNN_BF16) return crnn_dwconv_fwd_stream_rows(B, H, W, C);
-  DwsGeom g = dws_geom(B, H, W, C, 4); return (dtype == CRNN_F32 && g.ok) ? B * g.nwgb : 0;
-}
+// out / stat_partials bit-identical to crnn_bn_act_pool_drop_ex(q -> x, ph = pw = 1) + the plain form on x (fp32 maps: the statistics to the order of
+// their partial sums; the keep bytes, still one per 8 elements, are read as nibbles).
+// CRNN_ERR_UNSUPPORTED where crnn_dwconv_fwd_stream_pro_supported_ex says so (the caller materialises x).
 extern "C" int crnn_dwconv3x3_fwd_stream_pro_ex(const void* q, const float* pro_bnstate, float rate, const void* keep, const float* k, void* out,
                                                 float* stat_partials, int B, int H, int W, int C, int dtype, hipStream_t stream) {
-  if (dtype == CRNN_BF16) return crnn_dwconv3x3_fwd_stream_pro(q, pro_bnstate, rate, keep, k, out, stat_partials, B, H, W, C, stream);
-  if (dtype != CRNN_F32 || !q || !pro_bnstate || !k || !out || rate < 0.f || rate >= 1.f || (rate > 0.f && !keep)) return CRNN_ERR_ARG;
-  DwsGeom g = dws_geom(B, H, W, C, 4);
-  if (!dws_pro_ok(g, B, H, W, C, 4) || (((uintptr_t)q | (uintptr_t)out | (uintptr_t)k | (uintptr_t)pro_bnstate) & 15) || ((uintptr_t)keep & 3)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)H * W * C * 4 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
-  DwsParams p;
-  p.x = (const unsigned char*)q; p.k = k; p.out = (unsigned char*)out; p.partials = stat_partials; p.bnstate = nullptr;
-  p.H = H; p.W = W; p.C = C; p.HB = g.HB; p.NS = g.NS; p.nwgb = g.nwgb; p.flip = 0; p.cols = g.cols; p.rowbytes = W * C * 4; p.wmaj = 0;
-  p.nsplit = g.nsplit; p.cppw = g.cppw;
-  p.pro_bn = pro_bnstate; p.keep = (const unsigned char*)keep; p.rate = rate;
-  return rate > 0.f ? dws_launch_pro<true, true>(p, g, B, stream) : dws_launch_pro<false, true>(p, g, B, stream);
+  const int es = dws_es(dtype);
+  if (!es || !q || !pro_bnstate || !k || !out || rate < 0.f || rate >= 1.f || (rate > 0.f && !keep)) return CRNN_ERR_ARG;
+  return dws_run(q, k, out, stat_partials, nullptr, pro_bnstate, rate, keep, B, H, W, C, 0, 0, es, stream);
 }
+// the untyped forms: CRNN_BF16
+extern "C" int crnn_dwconv_fwd_stream_supported(int B, int H, int W, int C) { return crnn_dwconv_fwd_stream_supported_ex(B, H, W, C, CRNN_BF16); }
+extern "C" int crnn_dwconv_fwd_stream_rows(int B, int H, int W, int C) { return crnn_dwconv_fwd_stream_rows_ex(B, H, W, C, CRNN_BF16); }
+extern "C" int crnn_dwconv_fwd_stream_pro_supported(int B, int H, int W, int C) { return crnn_dwconv_fwd_stream_pro_supported_ex(B, H, W, C, CRNN_BF16); }
 extern "C" int crnn_dwconv3x3_fwd_stream(const void* x, const float* k, void* out, float* stat_partials, const float* bnstate, int B, int H, int W,
                                          int C, int flip, hipStream_t stream) {
   return crnn_dwconv3x3_fwd_stream_ex(x, k, out, stat_partials, bnstate, B, H, W, C, flip, 0, stream);
+}
+extern "C" int crnn_dwconv3x3_fwd_stream_pro(const void* q, const float* pro_bnstate, float rate, const void* keep, const float* k, void* out,
+                                             float* stat_partials, int B, int H, int W, int C, hipStream_t stream) {
+  return crnn_dwconv3x3_fwd_stream_pro_ex(q, pro_bnstate, rate, keep, k, out, stat_partials, B, H, W, C, CRNN_BF16, stream);
 }

@@ -106,14 +106,14 @@ const size_t kGemmScratchBytes = 64UL * 1024 * 1024;
 enum { AL_WS = 1, AL_PARAMS = 2, AL_GRADS = 4, AL_ALL = 7 };
 enum DwInfer { DWI_STREAM, DWI_FOLDED, DWI_PLAIN };          // inference depthwise: row stream | halo tile with BatchNorm-1 + ReLU6 folded in | plain kernel + apply pass
 enum PwInfer { PWI_ONE, PWI_WRES, PWI_TILE };                // inference pointwise: block 1's outer product | weights resident (bf16 W^T) | tile kernel
-enum DwFwd { DWF_PRO, DWF_STREAM_BF16, DWF_STREAM_F32, DWF_TILE_STATS, DWF_C1, DWF_TILE_COLREDUCE };   // training depthwise (+ BatchNorm-1 statistics)
+enum DwFwd { DWF_PRO, DWF_STREAM, DWF_TILE_STATS, DWF_C1, DWF_TILE_COLREDUCE };   // training depthwise (+ BatchNorm-1 statistics)
 enum Bn1 { BN1_PASS, BN1_GEMM_BF16, BN1_GEMM_PLANES, BN1_PW1 };   // who applies BatchNorm-1 + ReLU6: a pass of its own (writes `a`) | the pointwise GEMMs' staging (bf16 | planes) | block 1's outer product
 enum PwFwd { PWF_PW1_BN, PWF_PW1, PWF_WRES3, PWF_PLANES_TILE, PWF_WRES, PWF_BNRELU6_TILE, PWF_TILE };   // training pointwise (+ BatchNorm-2 statistics)
 enum BlockOut { OUT_NEXT_BLOCK, OUT_QMAX, OUT_PLAIN };       // x_i: formed inside block i+1's depthwise kernels (both passes) | written with q at the arg-max | written
 enum Bn2Bwd { BN2_APPLY, BN2_QMAX, BN2_PLAIN };              // BatchNorm-2 backward: pass 2 alone (statistics from block i+1) | arg-max statistics | two-pass; each as planes where dq_planes
 enum Wgrad { WG_PW1_BN, WG_PW1, WG_STREAM_BF16, WG_TILE_BF16, WG_PLANES_STREAM, WG_PLANES_TILE, WG_GEMM };
 enum Dgrad { DG_PW1, DG_PRES, DG_WRES_BF16, DG_WRES3, DG_PLANES_TILE, DG_GEMM };
-enum DwBwd { DWB_PRO, DWB_STREAM_F32, DWB_STREAM_BF16, DWB_TILE_FUSED, DWB_C1, DWB_THREE_KERNELS };   // depthwise stage backward; up to DWB_TILE_FUSED: one kernel
+enum DwBwd { DWB_PRO, DWB_STREAM, DWB_TILE_FUSED, DWB_C1, DWB_THREE_KERNELS };   // depthwise stage backward; up to DWB_TILE_FUSED: one kernel
 
 struct BlockSched {
   int dtd, dtq, dtx;            // storage of d / a, of q, of the block output x
@@ -196,7 +196,8 @@ Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
     if (i >= 2) S.pwT_count += (long)ci * co;
     b.has_qm = !(fl & CRNN_FLAG_NO_POOL_ARGMAX_Q) && pooled;
     b.has_dm = i < 7 && (!pooled || b.has_qm) && co % 8 == 0 && (mode == 2 || bn2_dw);
-    const bool dws = dtd == CRNN_BF16 && !dw_tile && crnn_dwconv_fwd_stream_supported(B, H, W, ci) == CRNN_OK;
+    const bool dws = dtd == CRNN_BF16 && !dw_tile && crnn_dwconv_fwd_stream_supported_ex(B, H, W, ci, CRNN_BF16) == CRNN_OK;
+    const bool dws_f32 = dtd == CRNN_F32 && i > 1 && !dw_tile && crnn_dwconv_fwd_stream_supported_ex(B, H, W, ci, CRNN_F32) == CRNN_OK && al_wp;
     const int slab = (dtd == CRNN_BF16) ? 64 : 32;
     const bool one = ci == 1 && dtd == CRNN_F32;                                               // block 1: an outer product, not a GEMM
     const bool blk1 = one && !(fl & CRNN_FLAG_BLOCK1_KERNELS) && c->imgw + 4 <= 255;          // ... with BatchNorm-1 folded into the neighbouring kernels (block1.hip)
@@ -212,11 +213,8 @@ Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
     b.inf_pw = one ? PWI_ONE : (wres_ok && dtd == CRNN_BF16 && M <= 0x7fffffffL) ? PWI_WRES : PWI_TILE;
     // ---- training forward
     const bool pro = i > 1 && S.b[i - 1].out == OUT_NEXT_BLOCK;
-    if (pro) { b.dw = DWF_PRO; b.dw_rows = crnn_dwconv_fwd_stream_rows_ex(B, H, W, ci, dtd); }
-    else if (dws) { b.dw = DWF_STREAM_BF16; b.dw_rows = crnn_dwconv_fwd_stream_rows(B, H, W, ci); }
-    else if (dtd == CRNN_F32 && i > 1 && !dw_tile && crnn_dwconv_fwd_stream_supported_ex(B, H, W, ci, CRNN_F32) == CRNN_OK && al_wp) {
-      b.dw = DWF_STREAM_F32; b.dw_rows = crnn_dwconv_fwd_stream_rows_ex(B, H, W, ci, CRNN_F32);
-    } else if (ci % 32 == 0 && ci % slab == 0) { b.dw = DWF_TILE_STATS; b.dw_rows = crnn_dwconv_num_tiles(B, H, W); }
+    if (pro || dws || dws_f32) { b.dw = pro ? DWF_PRO : DWF_STREAM; b.dw_rows = crnn_dwconv_fwd_stream_rows_ex(B, H, W, ci, dtd); }
+    else if (ci % 32 == 0 && ci % slab == 0) { b.dw = DWF_TILE_STATS; b.dw_rows = crnn_dwconv_num_tiles(B, H, W); }
     else if (blk1) { b.dw = DWF_C1; b.dw_rows = crnn_dwconv_c1_stat_rows(B, H, W); }
     else { b.dw = DWF_TILE_COLREDUCE; b.dw_rows = crnn_colreduce_chunks(M); }
     const bool fuse_a = dw_bn && mode == 2 && dtd == CRNN_BF16 && dtq == CRNN_BF16 && ci % 8 == 0 && ci <= 512;
@@ -247,9 +245,11 @@ Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
     b.bn2_bwd = b.bn2_rows > 0 ? BN2_APPLY : qmax ? BN2_QMAX : BN2_PLAIN;
     const int dtx_in = i > 1 ? S.b[i - 1].dtx : CRNN_F32;
     const bool fused_bf = i > 1 && dtd == CRNN_BF16 && dtx_in == CRNN_BF16 && dw_bwd && crnn_dwconv_bwd_fused_supported(H, W, ci) == CRNN_OK;
-    const bool fused_f32 = i > 1 && dtd == CRNN_F32 && dtq == CRNN_F32 && dtx_in == CRNN_F32 && dw_bwd && !dw_tile &&
-                           crnn_dwconv_bwd_stream_supported_ex(B, H, W, ci, CRNN_F32) == CRNN_OK && al_wp;
-    b.dwb = pro ? DWB_PRO : fused_f32 ? DWB_STREAM_F32 : fused_bf ? (dw_tile ? DWB_TILE_FUSED : DWB_STREAM_BF16) : blk1 ? DWB_C1 : DWB_THREE_KERNELS;
+    // the row stream (dwconv_bwd_stream.hip) where its query takes the shape and its operands -- workspace tensors and the depthwise weights -- are aligned;
+    // bf16 tensors otherwise on the halo tiles (conv_bwd_fused.hip), fp32 tensors as three kernels
+    const bool dbs = dw_bwd && !dw_tile && crnn_dwconv_bwd_stream_supported_ex(B, H, W, ci, dtd) == CRNN_OK && al_wp;
+    const bool fused_f32 = i > 1 && dtd == CRNN_F32 && dtq == CRNN_F32 && dtx_in == CRNN_F32 && dbs;
+    b.dwb = pro ? DWB_PRO : fused_f32 ? DWB_STREAM : fused_bf ? (dbs ? DWB_STREAM : DWB_TILE_FUSED) : blk1 ? DWB_C1 : DWB_THREE_KERNELS;
     b.dq_planes = fuse_x3 && S.planes_bwd == 2 && !tile_gemms && bn_stats && !(fl & CRNN_FLAG_NO_GRADIENT_PLANES) && crnn_gemm_pres_supported(M, ci, co, 2) == CRNN_OK &&
                   crnn_pwconv_wgrad_planes_stream_supported(M, co, ci) == CRNN_OK && crnn_pwconv_wgrad_planes_stream_scratch_bytes(M, co, ci) <= kGemmScratchBytes && al_wp;
     if (one) { b.wgrad = blk1 ? WG_PW1_BN : WG_PW1; b.dgrad = DG_PW1; b.dgrad_rows = blk1 ? crnn_pw1_bn_bwd_rows(M) : 0; continue; }
@@ -302,10 +302,10 @@ Plan make_plan(const crnn_config* c, const Dims& d, const Sched& S) {
     long tiles = crnn_dwconv_num_tiles(d.B, d.bh[i], d.bw[i]);
     maxparts = lmax(maxparts, tiles * 9L * ci);
     maxparts = lmax(maxparts, (long)crnn_dwconv_bwd_fused_rows(d.B, d.bh[i], d.bw[i], ci) * 9L * ci);
-    maxparts = lmax(maxparts, (long)crnn_dwconv_fwd_stream_rows(d.B, d.bh[i], d.bw[i], ci) * 2L * ci);
-    maxparts = lmax(maxparts, (long)crnn_dwconv_fwd_stream_rows_ex(d.B, d.bh[i], d.bw[i], ci, CRNN_F32) * 2L * ci);
-    maxparts = lmax(maxparts, (long)crnn_dwconv_bwd_stream_rows(d.B, d.bh[i], d.bw[i], ci) * 9L * ci);
-    maxparts = lmax(maxparts, (long)crnn_dwconv_bwd_stream_rows_ex(d.B, d.bh[i], d.bw[i], ci, CRNN_F32) * 9L * ci);
+    for (int dt : {CRNN_BF16, CRNN_F32}) {
+      maxparts = lmax(maxparts, (long)crnn_dwconv_fwd_stream_rows_ex(d.B, d.bh[i], d.bw[i], ci, dt) * 2L * ci);
+      maxparts = lmax(maxparts, (long)crnn_dwconv_bwd_stream_rows_ex(d.B, d.bh[i], d.bw[i], ci, dt) * 9L * ci);
+    }
     maxparts = lmax(maxparts, (long)crnn_colreduce_chunks(M) * 2L * lmax(ci, co));
     if (ci == 1) maxparts = lmax(maxparts, lmax((long)crnn_dwconv_c1_stat_rows(d.B, d.bh[i], d.bw[i]) * 2L, (long)crnn_pw1_bn_bwd_rows(M) * (co + 2L) + 64));
     maxparts = lmax(maxparts, (long)crnn_pwconv_stat_rows(M) * 2L * co);
@@ -725,8 +725,7 @@ extern "C" int crnn_forward_ex(const crnn_config* cfg, const float* params, cons
         if (keep_pending) { CRNN_TRY(fj.join()); keep_pending = false; }   // the keep bytes are complete
         CRNN_TRY(crnn_dwconv3x3_fwd_stream_pro_ex(pro_src(c, i - 1), c.w("bn2s" + std::to_string(i - 1)), drop_block, keep_bytes(c, i - 1), kdw, dd, parts, B, H, W, ci, dtd, stream));
         break;
-      case DWF_STREAM_BF16: CRNN_TRY(crnn_dwconv3x3_fwd_stream(in, kdw, dd, parts, nullptr, B, H, W, ci, 0, stream)); break;
-      case DWF_STREAM_F32: CRNN_TRY(crnn_dwconv3x3_fwd_stream_dt(in, kdw, dd, parts, B, H, W, ci, 0, CRNN_F32, stream)); break;
+      case DWF_STREAM: CRNN_TRY(crnn_dwconv3x3_fwd_stream_dt(in, kdw, dd, parts, B, H, W, ci, 0, dtd, stream)); break;
       case DWF_TILE_STATS: CRNN_TRY(crnn_dwconv3x3_fwd_ex(in, kdw, dd, parts, B, H, W, ci, 0, dtd, stream)); break;
       case DWF_C1: CRNN_TRY(crnn_dwconv3x3_c1_fwd(in, kdw, dd, parts, B, H, W, stream)); break;   // block 1: the one-channel kernel takes its own statistics
       default:
@@ -1153,11 +1152,7 @@ int backward_bottom(const Ctx& c, const float* x, uint64_t seed, hipStream_t aux
                                                  c.g(bp + "_dw"), parts, prev.bn2_rows > 0 ? c.w("bn2parts") : nullptr, B, H, W, ci, dtd, stream);
           break;
         }
-        case DWB_STREAM_F32: rcd = crnn_dwconv3x3_bwd_stream_ex(dd, gA, s1, coef, xin, kdw, gC, c.g(bp + "_dw"), parts, B, H, W, ci, CRNN_F32, stream); break;
-        case DWB_STREAM_BF16:   // rows streamed through LDS (dwconv_bwd_stream.hip); its shape rule has a query, its limit on a sample's bytes has none: else the halo tiles
-          rcd = crnn_dwconv3x3_bwd_stream(dd, gA, s1, coef, xin, kdw, gC, c.g(bp + "_dw"), parts, B, H, W, ci, stream);
-          if (rcd != CRNN_ERR_UNSUPPORTED) break;
-          [[fallthrough]];
+        case DWB_STREAM: rcd = crnn_dwconv3x3_bwd_stream_ex(dd, gA, s1, coef, xin, kdw, gC, c.g(bp + "_dw"), parts, B, H, W, ci, dtd, stream); break;
         default: rcd = crnn_dwconv3x3_bwd_fused(dd, gA, s1, coef, xin, kdw, gC, c.g(bp + "_dw"), parts, B, H, W, ci, stream);
       }
       CRNN_TRY(rcd);

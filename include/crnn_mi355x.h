@@ -705,7 +705,18 @@ int crnn_pw1_bn_bwd(const float* d, const float* in_bnstate, const float* w, con
  * out = ReLU6(dwconv3x3(x, k) * scale + shift); C must be a multiple of 32 (fp32 storage) / 64 (bf16 storage). */
 int crnn_dwconv3x3_bn_relu6_fwd(const void* x, const float* k, const float* bnstate, void* out, int B, int H, int W, int C,
                                 int dtype, crnn_stream_t stream);
-/* Depthwise 3x3 of a bf16 NHWC map as a row stream (dwconv_stream.hip): a loader wave keeps whole rows (W*C*2 contiguous bytes) in flight
+/* The depthwise ROW STREAMS (dwconv_stream.hip, dwconv_bwd_stream.hip): the launchers crnn_dwconv3x3_{fwd,bwd}_stream* and their queries
+ * crnn_dwconv_{fwd,bwd}_stream_* -- the declarations with these names below, no other.  One contract for all of them:
+ *  - the form with a `dtype` (_ex, _dt, _pro_ex, _supported_ex, _rows_ex, _pro_supported_ex; CRNN_BF16 | CRNN_F32 maps) is the definition; the form without
+ *    is the same call with CRNN_BF16.  crnn_dwconv3x3_fwd_stream_ex (inference epilogue, out_order) exists for bf16 maps only;
+ *  - an unknown dtype: CRNN_ERR_ARG from the launchers and the _supported queries, 0 from the _rows queries; a NULL operand, a rate outside [0, 1),
+ *    rate > 0 without keep bytes, a bad out_order: CRNN_ERR_ARG;
+ *  - the queries state the launchers' WHOLE shape rule -- the column rule described with each kernel below AND a sample (H * W * C elements) below 2^31
+ *    bytes (part of the queries' answer; earlier revisions refused such a sample in the launchers only, after the query had said yes): a launcher returns CRNN_ERR_UNSUPPORTED for a shape exactly when
+ *    its _supported (prologue form: _pro_supported) query does, and _rows is 0 for such a shape;
+ *  - the one refusal the queries cannot know: CRNN_ERR_UNSUPPORTED for an operand that is not 16-byte aligned (the keep bytes: 4-byte).
+ *
+ * Depthwise 3x3 of a bf16 NHWC map as a row stream (dwconv_stream.hip): a loader wave keeps whole rows (W*C*2 contiguous bytes) in flight
  * into an LDS ring with global_load_lds, the compute waves own a 16-byte column each and add every arriving row's taps to three running output
  * rows (nothing is held or re-read).  stat_partials != NULL: [crnn_dwconv_fwd_stream_rows][2][C] BatchNorm partial sums of the fp32 results;
  * bnstate != NULL ([mean|var|scale|shift]): out = ReLU6(conv * scale + shift) (inference), no statistics; flip = 1: the data gradient.
@@ -725,8 +736,8 @@ int crnn_dwconv3x3_fwd_stream_ex(const void* x, const float* k, void* out, float
  * kernel convolves x = Dropout(ReLU6(q * scale + shift)) (utils.py:48-56), formed in LDS by two transform waves one row ahead of the compute
  * waves -- the block output x never exists in HBM.  rate > 0: `keep` = crnn_dropout_keep_bytes(B*H*W*C/8 groups, rate, seed, layer) of the dropout
  * site crnn_bn_act_pool_drop_ex would use (one byte per 16-byte chunk); rate == 0: keep may be NULL.  out / stat_partials bit-identical to
- * crnn_bn_act_pool_drop_ex(q -> x, no pooling) + crnn_dwconv3x3_fwd_stream(x).  _supported: the stream shape rule, 128 % (C/8) == 0 and fewer than
- * 2^32 dropout groups (B*H*W*C/8). */
+ * crnn_bn_act_pool_drop_ex(q -> x, no pooling) + crnn_dwconv3x3_fwd_stream(x).  _pro_supported: the stream shape rule, the nine-wave step row, 128 % (C/8) == 0
+ * and fewer than 2^31 dropout groups (B*H*W*C/8). */
 int crnn_dwconv_fwd_stream_pro_supported(int B, int H, int W, int C);
 int crnn_dwconv3x3_fwd_stream_pro(const void* q, const float* pro_bnstate, float rate, const void* keep, const float* k, void* out,
                                   float* stat_partials, int B, int H, int W, int C, crnn_stream_t stream);
@@ -762,13 +773,13 @@ int crnn_dwconv3x3_bwd_fused(const void* d, const void* da, const float* bnstate
  * waves run the three running output rows of the data gradient on the dd row the others left in LDS.  Same contract and arithmetic as
  * crnn_dwconv3x3_bwd_fused (dx bit-identical, dk to the order of its partial sums); scratch: crnn_dwconv_bwd_stream_rows() * 9 * C floats.
  * _supported: CRNN_OK when W * C / 8 sixteen-byte columns split over whole channel octets into workgroups of 129..320 columns (every block
- * of the CRNN), else CRNN_ERR_UNSUPPORTED. */
+ * of the CRNN) and a sample is below 2^31 bytes (the contract above), else CRNN_ERR_UNSUPPORTED. */
 int crnn_dwconv_bwd_stream_supported(int B, int H, int W, int C);
 int crnn_dwconv_bwd_stream_rows(int B, int H, int W, int C);
 int crnn_dwconv3x3_bwd_stream(const void* d, const void* da, const float* bnstate, const float* coef, const void* xin, const float* k, void* dx,
                               float* dk, float* scratch, int B, int H, int W, int C, crnn_stream_t stream);
-/* The same stage by storage type (dtype: CRNN_BF16 = the three entry points above; CRNN_F32, round 4: four channels per lane, W * C / 4 columns
- * in workgroups of 129..320): the parity mode's crnn_bn_bwd_apply_ex + crnn_dwconv3x3_wgrad_ex + crnn_dwconv3x3_fwd_ex(flip = 1) in one pass over
+/* The same stage by storage type -- the definition of the three entry points above, which pass CRNN_BF16 (CRNN_F32, round 4: four channels per lane,
+ * W * C / 4 columns in workgroups of 129..320): the parity mode's crnn_bn_bwd_apply_ex + crnn_dwconv3x3_wgrad_ex + crnn_dwconv3x3_fwd_ex(flip = 1) in one pass over
  * d, da, xin -- 4 tensor passes instead of 7; dx bit-identical to that sequence, dk to the order of its partial sums. */
 int crnn_dwconv_bwd_stream_supported_ex(int B, int H, int W, int C, int dtype);
 int crnn_dwconv_bwd_stream_rows_ex(int B, int H, int W, int C, int dtype);
@@ -783,7 +794,8 @@ int crnn_dwconv_bwd_stream_pro_supported(int B, int H, int W, int C);
 int crnn_dwconv3x3_bwd_stream_pro(const void* d, const void* da, const float* bnstate, const float* coef, const void* q, const float* pro_bnstate,
                                   float rate, const void* keep, const float* k, void* dx, float* dk, float* scratch, float* bn2_stat_partials,
                                   int B, int H, int W, int C, crnn_stream_t stream);
-/* Round 4: the row-stream kernels on fp32 maps (the parity mode; dtype CRNN_F32, CRNN_BF16 = the entry points above).  Rows of 18 KiB run as two
+/* The typed forms of the forward and of the prologue forms (the definitions: the entry points above without a dtype pass CRNN_BF16).  Round 4: the
+ * row-stream kernels on fp32 maps (the parity mode; dtype CRNN_F32).  Rows of 18 KiB run as two
  * channel ranges of 9 KiB (one workgroup each), four channels per lane; the keep bytes (still one per 8 elements) are read as nibbles.
  * crnn_dwconv3x3_fwd_stream_dt: training form (statistics, no folded BatchNorm); out bit-identical to crnn_dwconv3x3_fwd_ex on fp32 tensors.
  * The prologue forms: bit-identical to crnn_bn_act_pool_drop_ex(q -> x) + the plain forms on the materialised x, as for bf16. */

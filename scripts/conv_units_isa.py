@@ -2,8 +2,10 @@
 """Device code of the conv stack's units against a reference source, kernel by kernel, without a GPU.
 
     python scripts/conv_units_isa.py --ref-rev <commit> [--ref-file crnn-ocr-lite_amd/csrc/conv.hip] [-o profiles/conv_units_refactor.txt]
+    python scripts/conv_units_isa.py --ref-rev <commit> --units dwconv_stream.hip,dwconv_bwd_stream.hip [-o ...]
 
-Compiles the reference file as it stood at <commit> and the five units of today's tree (hipcc --offload-arch=gfx950 -O3 -std=c++17 -S
+Compiles the reference file as it stood at <commit> and the five units of today's tree -- with --units: each named unit of csrc/ as it stood at <commit> and
+as it is today -- (hipcc --offload-arch=gfx950 -O3 -std=c++17 -S
 --cuda-device-only -Rpass-analysis=kernel-resource-usage), cuts each assembly into one body per function symbol (the instructions and the kernel
 descriptor), normalises what depends only on the file (local label numbers: .LBB<function>_<n>, .Lfunc_end<n>), and reports: the symbols missing, new or
 defined twice, the bodies that differ in anything but comments (with a unified diff), and the resource remarks (VGPRs, AGPRs, SGPRs, scratch, LDS) that differ."""
@@ -76,19 +78,27 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref-rev", required=True)
     ap.add_argument("--ref-file", default="crnn-ocr-lite_amd/csrc/conv.hip")
+    ap.add_argument("--units", default=None, help="comma-separated units of csrc/: compare each against the same path at --ref-rev")
     ap.add_argument("-o", "--out", default=None)
     a = ap.parse_args()
+    units = a.units.split(",") if a.units else UNITS
+    ref_files = ["crnn-ocr-lite_amd/csrc/" + u for u in units] if a.units else [a.ref_file]
     inc = os.path.join(ROOT, "include")
     with tempfile.TemporaryDirectory() as td:   # the reference source with the headers of its own revision
         for f in subprocess.check_output(["git", "ls-tree", "--name-only", a.ref_rev, "crnn-ocr-lite_amd/csrc/", "include/"], cwd=ROOT, text=True).split():
-            if f.endswith((".h", ".inc")) or f == a.ref_file:
+            if f.endswith((".h", ".inc")) or f in ref_files:
                 dst = os.path.join(td, f)
                 os.makedirs(os.path.dirname(dst), exist_ok=True)
                 open(dst, "wb").write(subprocess.check_output(["git", "show", "%s:%s" % (a.ref_rev, f)], cwd=ROOT))
-        ref_text, ref_res = compile_unit(os.path.join(td, a.ref_file), [os.path.join(td, "include"), os.path.dirname(os.path.join(td, a.ref_file))])
-    ref = bodies(ref_text)
+        ref, ref_res = {}, {}
+        for rf in ref_files:
+            text, res = compile_unit(os.path.join(td, rf), [os.path.join(td, "include"), os.path.dirname(os.path.join(td, rf))])
+            for sym, body in bodies(text).items():
+                assert sym not in ref, "symbol defined by two reference files: " + sym
+                ref[sym] = body
+            ref_res.update(res)
     new, new_res, where, twice = {}, {}, {}, []
-    for u in UNITS:
+    for u in units:
         text, res = compile_unit(os.path.join(CSRC, u), [inc])
         for sym, body in bodies(text).items():
             if sym in new:
@@ -96,7 +106,7 @@ def main():
             new[sym], where[sym] = body, u
         new_res.update(res)
     rep = []
-    rep.append("reference: %s at %s; units: %s" % (a.ref_file, a.ref_rev, ", ".join(UNITS)))
+    rep.append("reference: %s at %s; units: %s" % (", ".join(ref_files), a.ref_rev, ", ".join(units)))
     rep.append("function symbols: reference %d, units %d; missing %d, new %d, defined twice %d" %
                (len(ref), len(new), len(set(ref) - set(new)), len(set(new) - set(ref)), len(twice)))
     for s in sorted(set(ref) - set(new)):
@@ -122,7 +132,7 @@ def main():
     per = {}
     for s in common:
         per.setdefault(where[s], []).append(s)
-    for u in UNITS:
+    for u in units:
         rep.append("%-18s %3d functions, %5d instruction lines" % (u, len(per.get(u, [])), sum(len(new[s]) for s in per.get(u, []))))
     text = "\n".join(rep) + "\n"
     sys.stdout.write(text)

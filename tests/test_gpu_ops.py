@@ -1232,6 +1232,64 @@ def test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_p
     test_row_stream_depthwise_with_the_batchnorm2_prologue_equals_the_two_pass_path(3, 104, 36, 64, 0.1, hot=True)
 
 
+@pytest.mark.parametrize("B,H,W,C,pro", [(2, 52, 9, 512, True), (3, 104, 36, 64, True), (4, 32, 26, 256, False)])
+def test_row_stream_entry_points_without_a_dtype_are_the_typed_ones_with_bf16(B, H, W, C, pro):
+    """Every row-stream entry point without a `dtype` and its typed form called with CRNN_BF16 are one launch: outputs, statistic partials and
+    weight-gradient partials bit for bit (the two calls write buffers pre-filled with different values, so equal buffers were written whole).
+    Plain forward (both tap orders) and plain backward on one band per workgroup, on two bands side by side ((3, 104, 36, 64)) and on rows cut
+    into channel ranges whose workgroup ids lie 8 apart ((4, 32, 26, 256)); the prologue forms with and without dropout, with and without the
+    producer's BatchNorm-2 backward statistics.  What the kernels compute is held by the row-stream tests above."""
+    BF16 = 1
+    for q in ("crnn_dwconv_fwd_stream_%s", "crnn_dwconv_bwd_stream_%s"):
+        for what in ("supported", "rows") + (("pro_supported",) if pro else ()):
+            a, b = getattr(L(), q % what)(B, H, W, C), getattr(L(), q % what + "_ex")(B, H, W, C, BF16)
+            assert a == b and (a > 0 if what == "rows" else a == 0), (q % what, a, b)
+    n = B * H * W * C
+    gen = torch.Generator("cuda").manual_seed(n % 1000)
+    rnd = lambda *s: torch.randn(*s, device="cuda", generator=gen)
+    pair = lambda size, dt=torch.float32: [torch.full((size,), v, dtype=dt, device="cuda") for v in (7.0, 9.0)]
+
+    def same(what, *pairs):
+        for i, (a, b) in enumerate(pairs):
+            bits = torch.int16 if a.dtype == torch.bfloat16 else torch.int32
+            assert torch.equal(a.view(bits), b.view(bits)), "%s: buffer %d differs" % (what, i)
+    xd, kd = (rnd(n) * 1.5).to(torch.bfloat16), rnd(9 * C)
+    rows, brow = L().crnn_dwconv_fwd_stream_rows(B, H, W, C), L().crnn_dwconv_bwd_stream_rows(B, H, W, C)
+    for flip in (0, 1):
+        o, p = pair(n, torch.bfloat16), pair(rows * 2 * C)
+        ok(L().crnn_dwconv3x3_fwd_stream(P(xd), P(kd), P(o[0]), P(p[0]), None, B, H, W, C, flip, S()))
+        ok(L().crnn_dwconv3x3_fwd_stream_dt(P(xd), P(kd), P(o[1]), P(p[1]), B, H, W, C, flip, BF16, S()))
+        same("forward, flip %d" % flip, o, p)
+        if flip == 0:
+            dd = o[0]
+    # the consuming stage's BatchNorm-1 state [mean|var|scale|shift] and coefficients, the producer's BatchNorm-2 state
+    st1 = torch.cat([rnd(C), 1 + torch.rand(C, device="cuda", generator=gen), 1 + 0.3 * rnd(C), 0.5 * rnd(C) + 1.0])
+    st2 = torch.cat([rnd(C), 1 + torch.rand(C, device="cuda", generator=gen), 1 + 0.5 * rnd(C), 1.5 * rnd(C) + 1.5])
+    coef, dad = rnd(2 * C) * 1e-3, (rnd(n) * 0.7).to(torch.bfloat16)
+    dx, dk, sc = pair(n, torch.bfloat16), pair(9 * C), pair(brow * 9 * C)
+    ok(L().crnn_dwconv3x3_bwd_stream(P(dd), P(dad), P(st1), P(coef), P(xd), P(kd), P(dx[0]), P(dk[0]), P(sc[0]), B, H, W, C, S()))
+    ok(L().crnn_dwconv3x3_bwd_stream_ex(P(dd), P(dad), P(st1), P(coef), P(xd), P(kd), P(dx[1]), P(dk[1]), P(sc[1]), B, H, W, C, BF16, S()))
+    same("backward", dx, dk, sc)
+    assert float(dk[0].abs().max()) > 0
+    if not pro:
+        return
+    keep = torch.zeros(n // 8 + 64, dtype=torch.uint8, device="cuda")
+    for rate in (0.0, 0.1):
+        ok(L().crnn_dropout_keep_bytes(P(keep), n // 8, rate, 77, 4, S()))
+        o, p = pair(n, torch.bfloat16), pair(rows * 2 * C)
+        ok(L().crnn_dwconv3x3_fwd_stream_pro(P(xd), P(st2), rate, P(keep), P(kd), P(o[0]), P(p[0]), B, H, W, C, S()))
+        ok(L().crnn_dwconv3x3_fwd_stream_pro_ex(P(xd), P(st2), rate, P(keep), P(kd), P(o[1]), P(p[1]), B, H, W, C, BF16, S()))
+        same("prologue forward, rate %g" % rate, o, p)
+        for stats in (False, True):
+            dx, dk, sc, p2 = pair(n, torch.bfloat16), pair(9 * C), pair(brow * 9 * C), pair(brow * 2 * C)
+            ok(L().crnn_dwconv3x3_bwd_stream_pro(P(o[0]), P(dad), P(st1), P(coef), P(xd), P(st2), rate, P(keep), P(kd), P(dx[0]), P(dk[0]), P(sc[0]),
+                                                 P(p2[0]) if stats else None, B, H, W, C, S()))
+            ok(L().crnn_dwconv3x3_bwd_stream_pro_ex(P(o[0]), P(dad), P(st1), P(coef), P(xd), P(st2), rate, P(keep), P(kd), P(dx[1]), P(dk[1]), P(sc[1]),
+                                                    P(p2[1]) if stats else None, B, H, W, C, BF16, S()))
+            same("prologue backward, rate %g, statistics %s" % (rate, stats), dx, dk, sc, *([p2] if stats else []))
+            assert float(dk[0].abs().max()) > 0
+
+
 @pytest.mark.parametrize("B,H,W,C", [(3, 104, 36, 64), (2, 104, 36, 128), (5, 52, 18, 256), (2, 52, 9, 512), (256, 52, 9, 512), (70, 104, 36, 64)])
 @pytest.mark.parametrize("rate", [0.1, 0.0])
 def test_fp32_row_stream_depthwise_kernels_and_their_batchnorm2_prologue_forms(B, H, W, C, rate, hot=False):

@@ -174,6 +174,35 @@ def test_fp32_row_stream_and_localisation_net_shape_rules():
     assert L.crnn_loc_net_bwd_scratch(256) == 256 * (25 * 20 * 20 + 20 + 25 * 20 + 20)
 
 
+def test_row_stream_untyped_forms_equal_bf16_and_launchers_refuse_with_the_recorded_codes():
+    """Host arithmetic only.  The untyped shape queries of the depthwise row streams are their typed forms with CRNN_BF16 (an unknown dtype: -2 from
+    _supported, 0 rows), over B x H x W x C = 4 x 7 x 8 x 7 shapes; and every launcher refuses a missing operand, a bad dtype / rate / out_order, an
+    operand that is not 16-byte aligned (keep bytes: 4-byte) and a shape its query refuses with the code recorded in tests/golden/dw_stream_refusals.json
+    from the library BEFORE the launchers were merged into one per kernel (make_dw_stream_refusals.py; made-up addresses: every pattern returns before a launch)."""
+    import importlib.util
+    gold_dir = os.path.join(os.path.dirname(__file__), "golden")
+    spec = importlib.util.spec_from_file_location("make_dw_stream_refusals", os.path.join(gold_dir, "make_dw_stream_refusals.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    L = gen.load(native.LIB_PATH)
+    n = 0
+    for (B, H, W, C) in gen.sweep():
+        for q in gen.QUERIES:
+            typed = getattr(L, q + "_ex")
+            assert getattr(L, q)(B, H, W, C) == typed(B, H, W, C, gen.BF16), (q, B, H, W, C)
+            assert typed(B, H, W, C, gen.BAD_DT) == (0 if q.endswith("rows") else -2), (q, B, H, W, C)
+            n += 1
+    assert n == 4 * 7 * 8 * 7 * 6
+    gold = json.load(open(os.path.join(gold_dir, "dw_stream_refusals.json")))["records"]
+    pats = gen.patterns()
+    assert sorted(k for k, _, _ in pats) == sorted(gold) and len(gold) == len(pats) >= 200
+    assert set(gold.values()) == {-2, -3}
+    assert {fn for _, fn, _ in pats} == set(gen.LAUNCHERS)
+    got = gen.records(L)
+    bad = [(k, got[k], gold[k]) for k in gold if got[k] != gold[k]]
+    assert not bad, "%d refusals differ from the record, first: %s" % (len(bad), bad[:5])
+
+
 def test_dense_backward_shape_rule_and_scratch_size():
     """Round 5, host arithmetic only: dense2's one-pass backward (dense.hip) takes 2 * units a multiple of 128 up to 512 (units is a multiple of 64) and at most 40 classes; its scratch is
     one partial gradient ([K][C] + [C], rounded up to whole 16 bytes) per workgroup, at most 256 workgroups of at least one 8-row step."""
