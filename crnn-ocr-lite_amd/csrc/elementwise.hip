@@ -68,11 +68,17 @@ __global__ void dropout_vec8_keep_kernel(const float* __restrict__ x, float* __r
     keep[i] = (unsigned char)m;
   }
 }
+// whole groups of 8 columns, rows that start on 16 bytes, a 32-bit group counter
+extern "C" int crnn_dropout_keep_supported(long rows, int C, int ldx, int ldy) {
+  const long n = rows * C;
+  return (C % 8 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && n > 0 && n / 8 + 4096L * 256 < (1L << 31)) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 extern "C" int crnn_dropout_keep(const float* x, float* y, void* keep, long rows, int C, int ldx, int ldy, float rate, uint64_t seed, uint32_t layer,
                                  hipStream_t stream) {
   const long n = rows * C;
   if (!x || !y || !keep || rate >= 1.f) return CRNN_ERR_ARG;
-  if (C % 8 || ldx % 4 || ldy % 4 || (((uintptr_t)x | (uintptr_t)y) & 15) || n <= 0 || n / 8 + 4096L * 256 >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
+  CRNN_TRY(crnn_dropout_keep_supported(rows, C, ldx, ldy));
+  if ((((uintptr_t)x | (uintptr_t)y) & 15)) return CRNN_ERR_UNSUPPORTED;
   int blocks = cdiv(n / 8, 256); if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(dropout_vec8_keep_kernel, dim3(blocks), dim3(256), 0, stream, x, y, static_cast<unsigned char*>(keep), (unsigned)(n / 8), C / 8, ldx, ldy, rate, seed, layer);
   CRNN_LAUNCH_CHECK();

@@ -370,6 +370,9 @@ extern "C" int crnn_gemm_f32x3_bnstats_rows(long M) { return (int)(M / 128); }
 static int gemm_planes_bnstats(crnn_tile::Product product, const float* dq, const float* W, float* da, long M, int N, int K, const float* d, const float* bnstate,
                                float* stat_partials, hipStream_t stream) {
   CRNN_TRY(crnn_gemm_f32x3_bnstats_supported(M, N, K));
+  // the query is the whole shape rule (dense operands, no scratch: every tile and chunk whole, one reduction range); the unguarded epilogue's 16-byte accesses are the other
+  if (N <= 0 || K <= 0 || !d || !bnstate || !stat_partials) return CRNN_ERR_ARG;
+  if ((((uintptr_t)dq | (uintptr_t)W | (uintptr_t)da | (uintptr_t)d | (uintptr_t)bnstate) & 15)) return CRNN_ERR_UNSUPPORTED;
   const crnn_tile::BnBwdEpilogue e{d, N, bnstate, stat_partials};
   TileGemm g = tile_gemm(product, 1, dq, W, da, (int)M, N, K, K, K, N, stream);
   g.bnb = &e;

@@ -156,12 +156,15 @@ __global__ __launch_bounds__(384) void gemm_nt_kernel(NtParams p) {
 }  // namespace
 
 // Y[M][N] (bf16) = X[M][K] (bf16, row stride K) . W[N][K]^T (bf16, row stride K).  Supported: K % 64 == 0, N % 128 == 0,
-// 16-byte aligned pointers; anything else returns CRNN_ERR_UNSUPPORTED (use crnn_gemm_bf16_ex).  One persistent
-// workgroup per CU (384 threads: 4 MFMA waves + 2 LDS-DMA loader waves).
+// row offsets M * max(K, N) below 2^31 elements (_supported), 16-byte aligned X, W and Y; anything else returns CRNN_ERR_UNSUPPORTED
+// (use crnn_gemm_bf16_ex).  One persistent workgroup per CU (384 threads: 4 MFMA waves + 2 LDS-DMA loader waves).
+extern "C" int crnn_gemm_nt_bf16_supported(int M, int N, int K) {
+  return (M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 128 == 0 && (long)M * (K > N ? K : N) < (1L << 31)) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 extern "C" int crnn_gemm_nt_bf16(const void* X, const void* W, void* Y, int M, int N, int K, hipStream_t stream) {
   if (M <= 0 || N <= 0 || K <= 0) return CRNN_ERR_ARG;
-  if (K % 64 || N % 128 || (((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)M * (K > N ? K : N) >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;     // 32-bit row offsets
+  CRNN_TRY(crnn_gemm_nt_bf16_supported(M, N, K));
+  if ((((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y) & 15)) return CRNN_ERR_UNSUPPORTED;
   NtParams p;
   p.X = (const bf16_t*)X; p.W = (const bf16_t*)W; p.Y = (bf16_t*)Y; p.M = M; p.N = N; p.K = K;
   p.stripes = cdiv(M, 128); p.kch = K / 64;

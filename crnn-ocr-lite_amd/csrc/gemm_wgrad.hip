@@ -280,11 +280,11 @@ extern "C" size_t crnn_pwconv_wgrad_stream_scratch_bytes(long M, int N, int K) {
   return (size_t)p.g.nsplit * K * N * sizeof(float);
 }
 namespace {
+// (the callers' queries have compared the scratch size with the partial tiles)
 template <bool F32, bool XF = true>
-int wg_launch(WgParams& p, long M, float* out, int ldc, float* scratch, size_t scratch_bytes, hipStream_t stream) {
+int wg_launch(WgParams& p, long M, float* out, int ldc, float* scratch, hipStream_t stream) {
   int grid;
   wg_geom(M, p.N, p.K, p, grid);
-  if ((size_t)p.g.nsplit * p.K * p.N * sizeof(float) > scratch_bytes) return CRNN_ERR_UNSUPPORTED;
   if constexpr (!F32 && XF) {   // the pointwise convolutions' form (bf16 d with the BatchNorm transform, bf16 g): g by LDS-DMA from loader waves
     // (its one caller has checked what the DMA needs: g 16-byte aligned, N = ldg a multiple of 128)
     const int ldsd = kRing * kOp + kRingB * kOpB;
@@ -309,27 +309,31 @@ extern "C" int crnn_pwconv_bnrelu6_wgrad_stream(const void* d, const float* in_b
   if (!in_bnstate || !scratch) return CRNN_ERR_ARG;
   CRNN_TRY(crnn_pwconv_wgrad_stream_supported(M, N, K));
   if ((((uintptr_t)d | (uintptr_t)g | (uintptr_t)dw | (uintptr_t)scratch) & 15)) return CRNN_ERR_UNSUPPORTED;
+  if (crnn_pwconv_wgrad_stream_scratch_bytes(M, N, K) > scratch_bytes) return CRNN_ERR_UNSUPPORTED;
   WgParams p;
   p.D = (const bf16_t*)d; p.G = (const bf16_t*)g; p.part = scratch; p.scale = in_bnstate + 2L * K; p.shift = in_bnstate + 3L * K;
   p.M = (int)M; p.N = N; p.K = K; p.lda = K; p.ldg = N;
-  return wg_launch<false>(p, M, dw, N, scratch, scratch_bytes, stream);
+  return wg_launch<false>(p, M, dw, N, scratch, stream);
 }
 
 // The same stream for fp32 operands (rounded to bf16 on the way in, like crnn_gemm_bf16_ex mode 2 with fp32 A and B):
 //     C[M][N] (fp32, row stride ldc) = A^T . B,   A [K][lda >= M] fp32, B [K][ldb >= N] fp32, K = the reduction over rows.
 // The weight gradients of the recurrent layers (dW = X^T dZ, dU = H^T dZ over T*B rows).  Supported (else -3): M, N multiples of
-// 128 up to 1024, K a multiple of 64, lda / ldb / ldc multiples of 4, 16-byte aligned pointers; scratch as above.
+// 128 up to 1024, K a multiple of 64, lda / ldb / ldc multiples of 4, row offsets K * max(lda, ldb) below 2^30 elements, the partial tiles within
+// scratch_bytes (crnn_pwconv_wgrad_stream_scratch_bytes(K, N, M)) -- what _supported answers -- and 16-byte aligned A, B, C and scratch.
+extern "C" int crnn_gemm_tn_stream_supported(int M, int N, long K, int lda, int ldb, int ldc, size_t scratch_bytes) {
+  return (crnn_pwconv_wgrad_stream_supported(K, N, M) == CRNN_OK && lda >= M && ldb >= N && ldc >= N && !((lda | ldb | ldc) & 3) &&
+          K * (long)(lda > ldb ? lda : ldb) < (1L << 30) && crnn_pwconv_wgrad_stream_scratch_bytes(K, N, M) <= scratch_bytes) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 extern "C" int crnn_gemm_tn_stream(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, long K, float* scratch,
                                    size_t scratch_bytes, hipStream_t stream) {
   if (!scratch) return CRNN_ERR_ARG;
-  CRNN_TRY(crnn_pwconv_wgrad_stream_supported(K, N, M));
-  if (lda < M || ldb < N || ldc < N || ((lda | ldb | ldc) & 3)) return CRNN_ERR_UNSUPPORTED;
+  CRNN_TRY(crnn_gemm_tn_stream_supported(M, N, K, lda, ldb, ldc, scratch_bytes));
   if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)scratch) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if (K * (long)(lda > ldb ? lda : ldb) >= (1L << 30)) return CRNN_ERR_UNSUPPORTED;
   WgParams p;
   p.D = (const bf16_t*)A; p.G = (const bf16_t*)B; p.part = scratch; p.scale = nullptr; p.shift = nullptr;
   p.M = (int)K; p.N = N; p.K = M; p.lda = lda; p.ldg = ldb;
-  return wg_launch<true>(p, K, C, ldc, scratch, scratch_bytes, stream);
+  return wg_launch<true>(p, K, C, ldc, scratch, stream);
 }
 
 // The same stream for bf16 operands without a transform (round 5): C[M][N] (fp32, row stride ldc) = A^T . B, A [K][lda >= M] bf16, B [K][ldb >= N]
@@ -345,17 +349,20 @@ extern "C" size_t crnn_gemm_tn_bf16_stream_scratch_bytes(int M, int N, long K) {
   WgParams p; int grid; wg_geom(K, N, M, p, grid);
   return (size_t)p.g.nsplit * M * N * sizeof(float);
 }
+// ... the launcher's whole shape rule: with the leading dimensions (lda, ldb multiples of 8, ldc of 4, row offsets K * max(lda, ldb) below 2^31 elements) and the scratch size
+extern "C" int crnn_gemm_tn_bf16_stream_supported_ld(int M, int N, long K, int lda, int ldb, int ldc, size_t scratch_bytes) {
+  return (crnn_gemm_tn_bf16_stream_supported(M, N, K) == CRNN_OK && lda >= M && ldb >= N && ldc >= N && !((lda | ldb) & 7) && !(ldc & 3) &&
+          K * (long)(lda > ldb ? lda : ldb) < (1L << 31) && crnn_gemm_tn_bf16_stream_scratch_bytes(M, N, K) <= scratch_bytes) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 extern "C" int crnn_gemm_tn_bf16_stream(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, long K, float* scratch,
                                         size_t scratch_bytes, hipStream_t stream) {
   if (!A || !B || !C || !scratch) return CRNN_ERR_ARG;
-  CRNN_TRY(crnn_gemm_tn_bf16_stream_supported(M, N, K));
-  if (lda < M || ldb < N || ldc < N || ((lda | ldb) & 7) || (ldc & 3)) return CRNN_ERR_UNSUPPORTED;
+  CRNN_TRY(crnn_gemm_tn_bf16_stream_supported_ld(M, N, K, lda, ldb, ldc, scratch_bytes));
   if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)scratch) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if (K * (long)(lda > ldb ? lda : ldb) >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
   WgParams p;
   p.D = (const bf16_t*)A; p.G = (const bf16_t*)B; p.part = scratch; p.scale = nullptr; p.shift = nullptr;
   p.M = (int)K; p.N = N; p.K = M; p.lda = lda; p.ldg = ldb;
-  return wg_launch<false, false>(p, K, C, ldc, scratch, scratch_bytes, stream);
+  return wg_launch<false, false>(p, K, C, ldc, scratch, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -651,13 +658,16 @@ __global__ __launch_bounds__(768) void gemm_nt_f32_proj_kernel(NtpParams p) {
 extern "C" int crnn_rnn_input_proj_supported(int M, int N, int K) {
   return (M > 0 && M % 64 == 0 && N > 0 && N % 256 == 0 && K >= 64 && K <= 256 && K % 64 == 0 && 2 * (N / 256) <= 65535) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
 }
+// ... the launcher's whole shape rule: with the leading dimensions (multiples of 8, lda and ldw at least K, ldy at least N, row offsets M * max(lda, ldy) below 2^31 elements)
+extern "C" int crnn_rnn_input_proj_supported_ld(int M, int N, int K, int lda, int ldw, int ldy) {
+  return (crnn_rnn_input_proj_supported(M, N, K) == CRNN_OK && !((lda | ldw | ldy) & 7) && lda >= K && ldw >= K && ldy >= N &&
+          (long)M * (lda > ldy ? lda : ldy) < (1L << 31)) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 extern "C" int crnn_rnn_input_proj(const float* X, const void* Wf, const void* Wb, const float* bias_f, const float* bias_b, float* Yf, float* Yb, int M, int N,
                                    int K, int lda, int ldw, int ldy, hipStream_t stream) {
   if (!X || !Wf || !Wb || !Yf || !Yb || ((bias_f != nullptr) != (bias_b != nullptr))) return CRNN_ERR_ARG;
-  CRNN_TRY(crnn_rnn_input_proj_supported(M, N, K));
-  if (((lda | ldw | ldy) & 7) || lda < K || ldw < K || ldy < N) return CRNN_ERR_UNSUPPORTED;
+  CRNN_TRY(crnn_rnn_input_proj_supported_ld(M, N, K, lda, ldw, ldy));
   if ((((uintptr_t)X | (uintptr_t)Wf | (uintptr_t)Wb | (uintptr_t)Yf | (uintptr_t)Yb | (uintptr_t)bias_f | (uintptr_t)bias_b) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)M * (lda > ldy ? lda : ldy) >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
   NtpParams p;
   p.X = X; p.W[0] = (const bf16_t*)Wf; p.W[1] = (const bf16_t*)Wb; p.Y[0] = Yf; p.Y[1] = Yb; p.bias[0] = bias_f; p.bias[1] = bias_b;
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldy = ldy;
@@ -673,13 +683,21 @@ extern "C" int crnn_rnn_input_proj(const float* X, const void* Wf, const void* W
 
 // Y[M][N] (fp32, row stride ldy) = A0[M][K] . W0[N][K]^T (+ A1 . W1^T when A1 != NULL) (+ bias[N]); A fp32 (row stride lda), W bf16 (row stride
 // ldw).  Supported (else -3): M % 64 == 0, N % 128 == 0 (column slabs of 256, or of 128 when N % 256 != 0), K % 64 == 0, leading dimensions
-// multiples of 8, 16-byte aligned pointers.
+// multiples of 8 (lda, ldw at least K, ldy at least N), row offsets M * max(lda, ldy) below 2^31 elements, at most 65535 slabs -- what
+// crnn_gemm_nt_f32_stream_bias_supported answers -- and 16-byte aligned pointers (A0, W0, A1, W1, Y, bias).
+extern "C" int crnn_gemm_nt_f32_stream_bias_supported(int M, int N, int K, int lda, int ldw, int ldy) {
+  return (M > 0 && N > 0 && K > 0 && M % 64 == 0 && N % 128 == 0 && K % 64 == 0 && !((lda | ldw | ldy) & 7) && lda >= K && ldw >= K && ldy >= N &&
+          (long)M * (lda > ldy ? lda : ldy) < (1L << 31) && N <= 65535 * 128) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
+// crnn_gemm_nt_f32_stream: the same with N = 128 | 256
+extern "C" int crnn_gemm_nt_f32_stream_supported(int M, int N, int K, int lda, int ldw, int ldy) {
+  return ((N == 128 || N == 256) && crnn_gemm_nt_f32_stream_bias_supported(M, N, K, lda, ldw, ldy) == CRNN_OK) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 static int nts_launch(const float* A0, const void* W0, const float* A1, const void* W1, float* Y, const float* bias, int M, int N,
                       int K, int lda, int ldw, int ldy, int skew, hipStream_t stream) {
   if (M <= 0 || K <= 0 || N <= 0 || !A0 || !W0 || !Y || ((A1 != nullptr) != (W1 != nullptr))) return CRNN_ERR_ARG;
-  if (M % 64 || N % 128 || K % 64 || ((lda | ldw | ldy) & 7) || lda < K || ldw < K || ldy < N) return CRNN_ERR_UNSUPPORTED;
+  CRNN_TRY(crnn_gemm_nt_f32_stream_bias_supported(M, N, K, lda, ldw, ldy));
   if ((((uintptr_t)A0 | (uintptr_t)W0 | (uintptr_t)A1 | (uintptr_t)W1 | (uintptr_t)Y | (uintptr_t)bias) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)M * (lda > ldy ? lda : ldy) >= (1L << 31) || N > 65535 * 128) return CRNN_ERR_UNSUPPORTED;
   const int slab = (N % 256 == 0) ? 256 : 128;
   NtsParams p;
   p.A[0] = A0; p.A[1] = A1 ? A1 : A0; p.W[0] = (const bf16_t*)W0; p.W[1] = (const bf16_t*)(W1 ? W1 : W0); p.Y = Y; p.bias = bias;
@@ -703,11 +721,15 @@ static int nts_launch(const float* A0, const void* W0, const float* A1, const vo
 extern "C" int crnn_dense_fwd_stream_supported(long M, int N, long K) {
   return (M > 0 && M % 64 == 0 && (N == 128 || N == 256) && K >= 64 && K % 64 == 0 && M * (K > N ? K : (long)N) < (1L << 31)) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
 }
+// ... the launcher's whole shape rule: with the leading dimensions (multiples of 8, at least K) and the row permutation (permP = 0, or whole groups of permP rows)
+extern "C" int crnn_dense_fwd_stream_supported_ld(long M, int N, long K, int lda, int ldw, int permP) {
+  return (crnn_dense_fwd_stream_supported(M, N, K) == CRNN_OK && !((lda | ldw) & 7) && lda >= K && ldw >= K && permP >= 0 && (!permP || M % permP == 0)) ? CRNN_OK
+                                                                                                                                                       : CRNN_ERR_UNSUPPORTED;
+}
 extern "C" int crnn_dense_fwd_stream(const void* X, const void* WT, const float* bias, float* Y, long M, int N, long K, int lda, int ldw, int relu, int permP,
                                      float drop_rate, uint64_t seed, uint32_t layer, hipStream_t stream) {
   if (!X || !WT || !Y || permP < 0 || drop_rate < 0.f || drop_rate >= 1.f) return CRNN_ERR_ARG;
-  CRNN_TRY(crnn_dense_fwd_stream_supported(M, N, K));
-  if (((lda | ldw) & 7) || lda < K || ldw < K || (permP && M % permP)) return CRNN_ERR_UNSUPPORTED;
+  CRNN_TRY(crnn_dense_fwd_stream_supported_ld(M, N, K, lda, ldw, permP));
   if ((((uintptr_t)X | (uintptr_t)WT | (uintptr_t)Y | (uintptr_t)bias) & 15)) return CRNN_ERR_UNSUPPORTED;
   NtsParams p;
   p.A[0] = p.A[1] = reinterpret_cast<const float*>(X); p.W[0] = p.W[1] = (const bf16_t*)WT; p.Y = Y; p.bias = bias;
@@ -734,6 +756,7 @@ extern "C" int crnn_gemm_nt_f32_stream_bias(const float* A0, const void* W0, con
 // (the recurrent layers' input gradients: each workgroup starts its walk over the reduction three chunks after its neighbour's -- see the kernel)
 extern "C" int crnn_gemm_nt_f32_stream(const float* A0, const void* W0, const float* A1, const void* W1, float* Y, int M, int N, int K, int lda,
                                        int ldw, int ldy, hipStream_t stream) {
+  // (N first, as ever: with a missing operand as well, a call keeps the code it had.  With N = 128 | 256, nts_launch's query is crnn_gemm_nt_f32_stream_supported's rule)
   if (N != 128 && N != 256) return (M <= 0 || K <= 0) ? CRNN_ERR_ARG : CRNN_ERR_UNSUPPORTED;
   return nts_launch(A0, W0, A1, W1, Y, nullptr, M, N, K, lda, ldw, ldy, 3, stream);
 }

@@ -271,19 +271,22 @@ int wg3_launch_kernel(const Wg3Params& p, int grid, int lds, hipStream_t stream)
   CRNN_LAUNCH_CHECK();
   return CRNN_OK;
 }
+// the stream's whole shape rule, in the pixel-major naming of the pointwise forms (M rows reduced; d [M][lda >= K], g [M][ldg >= N], dw [K][ldc >= N])
+int wg3_rule(long M, int N, int K, int lda, int ldg, int ldc, size_t scratch_bytes) {
+  return (crnn_pwconv_wgrad_planes_stream_supported(M, N, K) == CRNN_OK && lda >= K && ldg >= N && ldc >= N && !((lda | ldg | ldc) & 3) &&
+          M * (long)(lda > ldg ? lda : ldg) < (1L << 31) && crnn_pwconv_wgrad_planes_stream_scratch_bytes(M, N, K) <= scratch_bytes) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 int wg3_run(const float* d, const float* in_bnstate, const float* g, const void* g_planes, long g_plane_stride, float* dw, long M, int N, int K, float* scratch,
             size_t scratch_bytes, hipStream_t stream, int lda = 0, int ldg = 0, int ldc = 0) {
   if (!d || (!g && !g_planes) || !dw || !scratch) return CRNN_ERR_ARG;
-  CRNN_TRY(crnn_pwconv_wgrad_planes_stream_supported(M, N, K));
-  if ((((uintptr_t)d | (uintptr_t)g | (uintptr_t)g_planes | (uintptr_t)dw | (uintptr_t)scratch | (uintptr_t)in_bnstate) & 15) || (g_plane_stride & 7)) return CRNN_ERR_UNSUPPORTED;
   lda = lda ? lda : K; ldg = ldg ? ldg : N; ldc = ldc ? ldc : N;
-  if (lda < K || ldg < N || ldc < N || ((lda | ldg | ldc) & 3) || M * (long)(lda > ldg ? lda : ldg) >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;
+  CRNN_TRY(wg3_rule(M, N, K, lda, ldg, ldc, scratch_bytes));
+  if ((((uintptr_t)d | (uintptr_t)g | (uintptr_t)g_planes | (uintptr_t)dw | (uintptr_t)scratch | (uintptr_t)in_bnstate) & 15) || (g_plane_stride & 7)) return CRNN_ERR_UNSUPPORTED;
   Wg3Params p;
   p.D = d; p.G = g; p.GP = reinterpret_cast<const unsigned short*>(g_planes); p.gps = g_plane_stride; p.part = scratch;
   p.scale = in_bnstate ? in_bnstate + 2L * K : nullptr; p.shift = in_bnstate ? in_bnstate + 3L * K : nullptr;
   p.M = (int)M; p.N = N; p.K = K; p.lda = lda; p.ldg = ldg;
   int grid; wg3_geom(M, N, K, p, grid);
-  if ((size_t)p.g.nsplit * K * N * sizeof(float) > scratch_bytes) return CRNN_ERR_UNSUPPORTED;
   const int lds = g_planes ? kRing3 * kStageA3 + kRingB3 * kStageB3 : kRing3 * kStage3;
   if (in_bnstate) CRNN_TRY(g_planes ? (wg3_launch_kernel<true, true>(p, grid, lds, stream)) : (wg3_launch_kernel<true, false>(p, grid, lds, stream)));
   else CRNN_TRY(g_planes ? (wg3_launch_kernel<false, true>(p, grid, lds, stream)) : (wg3_launch_kernel<false, false>(p, grid, lds, stream)));
@@ -311,6 +314,10 @@ extern "C" int crnn_pwconv_bnrelu6_wgrad_planes_stream_gp(const float* d, const 
 // gradients dW = x^T dz, dU = h_prev^T dz of the parity mode (utils.py:77-82 backwards), which the tile kernel ran as 8-16 tiles x 32-64 K ranges plus a
 // 64-row reduction.  Supported (else -3): crnn_pwconv_wgrad_planes_stream_supported(K, N, M), leading dimensions multiples of 4, 16-byte aligned pointers;
 // scratch: crnn_pwconv_wgrad_planes_stream_scratch_bytes(K, N, M).  Same products as crnn_gemm_f32x2 mode 2, another summation order.
+// _supported: the whole shape rule (a leading dimension of 0 stands for the dense one, as in the launcher); A, B, C and scratch 16-byte aligned beside it.
+extern "C" int crnn_gemm_tn_planes_stream_supported(int M, int N, long K, int lda, int ldb, int ldc, size_t scratch_bytes) {
+  return wg3_rule(K, N, M, lda ? lda : M, ldb ? ldb : N, ldc ? ldc : N, scratch_bytes);
+}
 extern "C" int crnn_gemm_tn_planes_stream(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, long K, float* scratch,
                                           size_t scratch_bytes, hipStream_t stream) {
   return wg3_run(A, nullptr, B, nullptr, 0, C, K, N, M, scratch, scratch_bytes, stream, lda, ldb, ldc);
@@ -445,13 +452,17 @@ __global__ __launch_bounds__(768) void gemm_nt_f32x2_stream_kernel(Nts2Params p)
 }
 }  // namespace
 // Y[M][N] (fp32, row stride ldy) = A0[M][K] . W0[N][K]^T (+ A1 . W1^T when A1 != NULL), everything fp32, two bf16 planes per operand.  Supported (else -3):
-// M % 64 == 0, N % 128 == 0, K % 64 == 0, leading dimensions multiples of 4, 16-byte aligned pointers.
+// M % 64 == 0, N % 128 == 0, K % 64 == 0, leading dimensions multiples of 4 (lda, ldw at least K, ldy at least N), row offsets M * max(lda, ldy) below 2^31
+// elements, at most 65535 slabs -- what _supported answers -- and 16-byte aligned pointers (A0, W0, A1, W1, Y).
+extern "C" int crnn_gemm_nt_f32x2_stream_supported(int M, int N, int K, int lda, int ldw, int ldy) {
+  return (M > 0 && N > 0 && K > 0 && M % 64 == 0 && N % 128 == 0 && K % 64 == 0 && !((lda | ldw | ldy) & 3) && lda >= K && ldw >= K && ldy >= N &&
+          (long)M * (lda > ldy ? lda : ldy) < (1L << 31) && N <= 65535 * 128) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
 extern "C" int crnn_gemm_nt_f32x2_stream(const float* A0, const float* W0, const float* A1, const float* W1, float* Y, int M, int N, int K, int lda, int ldw,
                                          int ldy, hipStream_t stream) {
   if (M <= 0 || K <= 0 || N <= 0 || !A0 || !W0 || !Y || ((A1 != nullptr) != (W1 != nullptr))) return CRNN_ERR_ARG;
-  if (M % 64 || N % 128 || K % 64 || ((lda | ldw | ldy) & 3) || lda < K || ldw < K || ldy < N) return CRNN_ERR_UNSUPPORTED;
+  CRNN_TRY(crnn_gemm_nt_f32x2_stream_supported(M, N, K, lda, ldw, ldy));
   if ((((uintptr_t)A0 | (uintptr_t)W0 | (uintptr_t)A1 | (uintptr_t)W1 | (uintptr_t)Y) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)M * (lda > ldy ? lda : ldy) >= (1L << 31) || N > 65535 * 128) return CRNN_ERR_UNSUPPORTED;
   Nts2Params p;
   p.A[0] = A0; p.A[1] = A1 ? A1 : A0; p.W[0] = W0; p.W[1] = W1 ? W1 : W0; p.Y = Y;
   p.M = M; p.K = K; p.lda = lda; p.ldw = ldw; p.ldy = ldy; p.npairs = A1 ? 2 : 1; p.skew = 3;

@@ -554,21 +554,26 @@ extern "C" int crnn_gemm_wres_supported(int N, int K) {
   return (N >= 128 && N % 128 == 0 && (N <= 1024 || (K <= 128 && N <= 8192)) && (K == 64 || K == 128 || K == 256 || K == 512)) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
 }
 
+// ... and the rows M: at most 2^31 - 1 of them, row offsets M * max(K, N) below 2^31 elements.  The whole shape rule of crnn_gemm_wres_bf16 and
+// crnn_pwconv_fwd_wres_folded: they refuse (-3) exactly when this does or an operand is not 16-byte aligned.
+extern "C" int crnn_gemm_wres_bf16_supported(long M, int N, int K) {
+  return (M > 0 && M <= 0x7fffffffL && crnn_gemm_wres_supported(N, K) == CRNN_OK && M * (long)(K > N ? K : N) < (1L << 31)) ? CRNN_OK : CRNN_ERR_UNSUPPORTED;
+}
+
 // Y[M][N] (bf16) = X[M][K] (bf16, row stride K) . W[N][K]^T (bf16, row stride K), weights resident in registers.
 // One persistent workgroup per CU (512 threads: 4 MFMA waves + 2 LDS-DMA loader waves + 2 storer waves, 160 KiB of LDS).
 static int wres_geom(int M, int N, WresParams& p) {             // -> grid (flat lanes when N / 128 exceeds an XCD's CUs: dense1's data gradient)
   return stripe_grid_plan(p.g, cdiv(M, 128), N / 128, crnn_cu_count(1), 1, true);
 }
-static int gemm_wres_impl(const void* X, const void* W, void* Y, int M, int N, int K, const float* cscale, const float* cshift, hipStream_t stream,
+static int gemm_wres_impl(const void* X, const void* W, void* Y, long M, int N, int K, const float* cscale, const float* cshift, hipStream_t stream,
                           const void* D = nullptr, const float* bnstate = nullptr, float* stats = nullptr, int pool = 1) {
   if (M <= 0 || N <= 0 || K <= 0) return CRNN_ERR_ARG;
-  CRNN_TRY(crnn_gemm_wres_supported(N, K));
+  CRNN_TRY(crnn_gemm_wres_bf16_supported(M, N, K));
   if ((((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y) & 15)) return CRNN_ERR_UNSUPPORTED;
-  if ((long)M * (K > N ? K : N) >= (1L << 31)) return CRNN_ERR_UNSUPPORTED;     // 32-bit row offsets
   WresParams p;
-  p.X = (const bf16_t*)X; p.W = (const bf16_t*)W; p.Y = (bf16_t*)Y; p.M = M; p.N = N; p.K = K;
+  p.X = (const bf16_t*)X; p.W = (const bf16_t*)W; p.Y = (bf16_t*)Y; p.M = (int)M; p.N = N; p.K = K;
   p.D = (const bf16_t*)D; p.bnstate = bnstate; p.stats = stats;
-  const int grid = wres_geom(M, N, p);
+  const int grid = wres_geom((int)M, N, p);
   if (D) {                                                     // storer waves take the BatchNorm-backward statistics (K = 256 | 512 here)
     if (K == 256) return launch_wres<4, 2, false, true>(p, grid, stream);
     return launch_wres<8, 2, false, true>(p, grid, stream);
@@ -618,15 +623,15 @@ extern "C" int crnn_gemm_wres_bf16_bnstats(const void* X, const void* W, void* Y
   if (!d || !bnstate || !stat_partials) return CRNN_ERR_ARG;
   CRNN_TRY(crnn_gemm_wres_bnstats_supported(M, N, K));
   if ((((uintptr_t)d | (uintptr_t)stat_partials | (uintptr_t)bnstate) & 15)) return CRNN_ERR_UNSUPPORTED;
-  return gemm_wres_impl(X, W, Y, (int)M, N, K, nullptr, nullptr, stream, d, bnstate, stat_partials);
+  return gemm_wres_impl(X, W, Y, M, N, K, nullptr, nullptr, stream, d, bnstate, stat_partials);
 }
 // Inference forward of a pointwise convolution with the BatchNorm + ReLU6 that follows folded in (utils.py:49-51, learning_phase 0):
 // Y[M][N] (bf16) = ReLU6((X . W^T) * scale[n] + shift[n]), out_bnstate = [mean|var|scale|shift] of that BatchNorm (crnn_bn_infer_state).
 // The epilogue runs on the fp32 accumulators in the MFMA waves (one rounding to bf16): bit-identical to crnn_pwconv_fwd(out_bnstate).
 extern "C" int crnn_pwconv_fwd_wres_folded(const void* a, const void* wT, void* y, long M, int N, int K, const float* out_bnstate, hipStream_t stream) {
   if (!out_bnstate) return CRNN_ERR_ARG;
-  if (M > 0x7fffffffL || (((uintptr_t)out_bnstate) & 15)) return CRNN_ERR_UNSUPPORTED;
-  return gemm_wres_impl(a, wT, y, (int)M, N, K, out_bnstate + 2L * N, out_bnstate + 3L * N, stream);
+  if ((((uintptr_t)out_bnstate) & 15)) return CRNN_ERR_UNSUPPORTED;
+  return gemm_wres_impl(a, wT, y, M, N, K, out_bnstate + 2L * N, out_bnstate + 3L * N, stream);
 }
 // The same with the MaxPooling2D that follows the block's ReLU6 (utils.py:52-54) in the epilogue: y [M / pool_rows][N] = max over every group of
 // pool_rows consecutive rows of ReLU6((X . W^T) * scale + shift).  pool_rows = 2: MaxPooling2D((1,2)) on a map of even width in NHWC order;
@@ -642,7 +647,7 @@ extern "C" int crnn_pwconv_fwd_wres_folded_pool(const void* a, const void* wT, v
   if (!out_bnstate) return CRNN_ERR_ARG;
   CRNN_TRY(crnn_pwconv_fwd_wres_folded_pool_supported(M, N, K, pool_rows));
   if ((((uintptr_t)out_bnstate) & 15)) return CRNN_ERR_UNSUPPORTED;
-  return gemm_wres_impl(a, wT, y, (int)M, N, K, out_bnstate + 2L * N, out_bnstate + 3L * N, stream, nullptr, nullptr, nullptr, pool_rows);
+  return gemm_wres_impl(a, wT, y, M, N, K, out_bnstate + 2L * N, out_bnstate + 3L * N, stream, nullptr, nullptr, nullptr, pool_rows);
 }
 
 namespace {

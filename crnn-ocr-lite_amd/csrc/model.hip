@@ -102,8 +102,12 @@ const size_t kGemmScratchBytes = 64UL * 1024 * 1024;
 // configuration, the dimensions and the 16-byte alignment of the caller's three base pointers -- and make_plan (the tensors whose presence is a schedule
 // decision), the forward and the backward only read the record: what both passes depend on is one field.  To change which kernel a block runs, change decide().
 // Alignment: workspace tensors sit at 256-byte offsets (Plan::add), parameter and gradient tensors at 16-byte offsets (Layout::add), so a tensor meets the
-// kernels' 16-byte rule exactly when its base pointer does.  make_plan and crnn_block_output_fused ask for aligned bases (AL_ALL), as torch allocations are.
-enum { AL_WS = 1, AL_PARAMS = 2, AL_GRADS = 4, AL_ALL = 7 };
+// kernels' 16-byte rule exactly when its base pointer does; a bf16 shadow of a parameter tensor ("pbf" + its layout offset, 2 bytes per element) when the
+// workspace base does and the offset is a multiple of 8.  make_plan and crnn_block_output_fused ask for aligned bases (AL_ALL), as torch allocations are.
+// A kernel the record names has had its query asked and its alignment-checked operands looked at here, and its refusal at run time is the step's error.  The one
+// exception: the depthwise row stream on bf16 maps (dws below) is chosen from the shapes alone -- the bf16-storage step has no other kernel for every stage on a
+// misaligned workspace, and keeps returning -3 there and for misaligned parameters (the stream checks the depthwise weights).
+enum { AL_WS = CRNN_ALIGNED_WORKSPACE, AL_PARAMS = CRNN_ALIGNED_PARAMS, AL_GRADS = CRNN_ALIGNED_GRADS, AL_ALL = CRNN_ALIGNED_ALL };
 enum DwInfer { DWI_STREAM, DWI_FOLDED, DWI_PLAIN };          // inference depthwise: row stream | halo tile with BatchNorm-1 + ReLU6 folded in | plain kernel + apply pass
 enum PwInfer { PWI_ONE, PWI_WRES, PWI_TILE };                // inference pointwise: block 1's outer product | weights resident (bf16 W^T) | tile kernel
 enum DwFwd { DWF_PRO, DWF_STREAM, DWF_TILE_STATS, DWF_C1, DWF_TILE_COLREDUCE };   // training depthwise (+ BatchNorm-1 statistics)
@@ -112,8 +116,12 @@ enum PwFwd { PWF_PW1_BN, PWF_PW1, PWF_WRES3, PWF_PLANES_TILE, PWF_WRES, PWF_BNRE
 enum BlockOut { OUT_NEXT_BLOCK, OUT_QMAX, OUT_PLAIN };       // x_i: formed inside block i+1's depthwise kernels (both passes) | written with q at the arg-max | written
 enum Bn2Bwd { BN2_APPLY, BN2_QMAX, BN2_PLAIN };              // BatchNorm-2 backward: pass 2 alone (statistics from block i+1) | arg-max statistics | two-pass; each as planes where dq_planes
 enum Wgrad { WG_PW1_BN, WG_PW1, WG_STREAM_BF16, WG_TILE_BF16, WG_PLANES_STREAM, WG_PLANES_TILE, WG_GEMM };
-enum Dgrad { DG_PW1, DG_PRES, DG_WRES_BF16, DG_WRES3, DG_PLANES_TILE, DG_GEMM };
+enum Dgrad { DG_PW1, DG_PRES, DG_WRES_BF16, DG_NT_BF16, DG_WRES3, DG_PLANES_TILE, DG_GEMM };   // (DG_WRES_BF16: with BatchNorm-1's backward statistics where dgrad_rows)
 enum DwBwd { DWB_PRO, DWB_STREAM, DWB_TILE_FUSED, DWB_C1, DWB_THREE_KERNELS };   // depthwise stage backward; up to DWB_TILE_FUSED: one kernel
+// the layers above the blocks.  C = A^T B over the rows (weight gradients): the pixel stream rounding fp32 operands on the way in | on bf16 operands | on two planes | tile GEMM
+enum Tn { TN_STREAM, TN_STREAM_BF16, TN_PLANES_STREAM, TN_TILE };
+enum Xw { XW_BOTH, XW_STRIPES, XW_TILE };                   // a recurrent layer's input projections: both directions in one persistent launch | one stripe-stream launch each | tile GEMMs
+enum RnnDx { DX_STREAM_BF16, DX_PLANES_STREAM, DX_TILE };    // a recurrent layer's input gradient, both directions: one stripe-stream launch (bf16 shadows | two planes) | two tile GEMMs
 
 struct BlockSched {
   int dtd, dtq, dtx;            // storage of d / a, of q, of the block output x
@@ -134,11 +142,13 @@ struct Sched {
   long bn2parts;                // floats of "bn2parts", 0: absent
   long pwT_count, d2T_off, d1T_off;   // "pwT": its size; dense2's padded W^T and dense1's W^T behind the blocks' copies
   bool loc_fused;               // localisation net as one workgroup per sample, forward and backward
-  bool dense1_stream, dense1_fwd_stream, dense2_stream, dense1_dgrad_wres, dense2_bwd_fused, dense2_bwd_small;
-  bool xw_stream, xw_both[2], rnn_persist, rnn_bwd_persist[2];   // ([layer - 1]; rnn_bwd_persist: set by make_ctx, it depends on where the weights' bf16 shadows lie)
+  // dense1_stream / dense2_stream: the W^T copies exist ("pwT"); *_fwd_stream: the stripe streams run on them.  dense1_gbm16: the bf16 copy of dense1's output gradient exists
+  bool dense1_stream, dense1_fwd_stream, dense2_stream, dense2_fwd_stream, dense1_gbm16, dense1_dgrad_wres, dense2_bwd_fused, dense2_bwd_small;
+  bool drop_keep_fused;         // Dropout(.2) under dense2: the dropped activations and the keep bytes in one pass (crnn_dropout_keep)
+  bool xw_stream, rnn_persist, rnn_bwd_persist[2];   // xw_stream: the bf16 W^T copies of the projections exist ("wt<layer><dir>"); ([layer - 1])
+  int xw[2], rnn_dw[2], rnn_du[2][2], rnn_dx[2], dense1_wgrad;           // Tn: dW of both directions, dU [layer - 1][forward | backward direction], dense1's dW; RnnDx
   int dtu, rnn_uw;
   int products, products_fwd, planes_fwd, planes_bwd;   // crnn_pwconv_fwd's product selectors; bf16 planes per operand of the parity mode's GEMMs
-  bool bwd_stream_bf16, bwd_stream_planes;              // the backward's stand-alone GEMMs on the bf16 | two-plane stream kernels where those take the shape
 };
 
 // Depthwise row streams: bf16 maps whose rows fill the 9 KiB step row, fp32 maps since round 4 (same outputs as the halo-tile kernels).  BatchNorm-1 + ReLU6
@@ -149,11 +159,13 @@ struct Sched {
 // (OUT_QMAX / BN2_QMAX, bit-identical sums).  Parity mode: three bf16 planes per operand forward (fp32-level accuracy), two backward (relative error of a
 // product <= 3 * 2^-18); the weights-resident plane kernels (gemm_wres3.hip) for reductions of at most 256 channels -- at 512 the tile kernel is faster
 // (profiles/r06_wres3_bench.txt) --, and dq written as planes for the two backward GEMMs (gemm_pres.hip, gemm_wgrad3.hip).
-Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
+Sched decide(const crnn_config* c, const Dims& d, const Layout& L, int al = AL_ALL) {
   Sched S{};
   const int fl = c->flags, mode = c->mfma_bf16, B = d.B, u = d.u, G = d.G;
   const long TB = (long)d.T * B;
   const bool al_w = al & AL_WS, al_wp = al_w && (al & AL_PARAMS), al_wg = al_w && (al & AL_GRADS);
+  auto shadow = [&](const std::string& n) { return al_w && L.off(n) % 8 == 0; };   // the bf16 shadow of parameter tensor n is 16-byte aligned
+  auto at = [](long elems) { return elems % 4 == 0; };                              // an fp32 operand offset by `elems` keeps its tensor's alignment
   const bool tile_gemms = fl & CRNN_FLAG_GEMM_TILE_KERNELS, dw_tile = fl & CRNN_FLAG_DW_TILE_KERNEL, bn_stats = !(fl & CRNN_FLAG_NO_BN_STATS_FUSION);
   const bool dw_bn = !(fl & CRNN_FLAG_NO_DW_BN_FUSION), dw_bwd = !(fl & CRNN_FLAG_NO_DW_BWD_FUSION);
   const bool bn2_dw = !(fl & CRNN_FLAG_NO_BN2_DW_FUSION) && ((fl & CRNN_FLAG_BN2_DW_FUSION) || mode != 2);
@@ -162,23 +174,46 @@ Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
   S.planes_fwd = (fl & CRNN_FLAG_TWO_PLANE_FORWARD) ? 2 : 3;
   S.planes_bwd = (fl & CRNN_FLAG_THREE_PLANE_BACKWARD) ? 3 : 2;
   S.products_fwd = (S.products == 2 && S.planes_fwd == 2) ? 3 : S.products;   // (3 = two planes)
-  S.bwd_stream_bf16 = mode && !tile_gemms;
-  S.bwd_stream_planes = S.products == 2 && S.planes_bwd == 2 && !tile_gemms;
+  // the backward's stand-alone GEMMs: the bf16 | two-plane stream kernels where their queries take the call and their operands are aligned
+  const bool stream_bf16 = mode && !tile_gemms, stream_planes = S.products == 2 && S.planes_bwd == 2 && !tile_gemms;
   S.loc_fused = c->stn && !(fl & CRNN_FLAG_LOC_NET_KERNELS) && crnn_loc_net_fused_supported(d.H0, d.W0) == CRNN_OK && al_wp;
   // dense layers: the stripe streams / weights-resident kernels in the bf16 modes (whole 64-row stripes); dense2's one-pass fp32 backward in every mode
-  S.dense2_stream = mode && !tile_gemms && TB % 64 == 0 && (2 * u) % 64 == 0 && d.C <= 128;
-  S.dense1_stream = mode == 2 && !tile_gemms && d.feat % 8 == 0 && crnn_dense_fwd_stream_supported(TB, d.tds, d.feat) == CRNN_OK;
-  S.dense1_fwd_stream = S.dense1_stream && al_wp;
-  S.dense1_dgrad_wres = mode == 2 && !tile_gemms && crnn_gemm_wres_supported(d.feat, d.tds) == CRNN_OK && TB * d.feat < (1L << 31);
+  S.dense2_stream = mode && !tile_gemms && d.C <= 128 && TB <= 0x7fffffffL && crnn_gemm_nt_f32_stream_bias_supported((int)TB, 128, 2 * u, 2 * u, 2 * u, 128) == CRNN_OK;
+  S.dense1_stream = mode == 2 && !tile_gemms && crnn_dense_fwd_stream_supported_ld(TB, d.tds, d.feat, d.feat, d.feat, d.T) == CRNN_OK;
+  S.dense1_gbm16 = mode == 2 && !tile_gemms && crnn_gemm_wres_supported(d.feat, d.tds) == CRNN_OK && TB * d.feat < (1L << 31);
+  // dense1's backward: both GEMMs read the bf16 copy of its output gradient -- dW on the pixel stream (36 feature tiles x 7 row ranges), the data gradient on the
+  // weights-resident GEMM (36 slices of 128 features keep their 128 x 128 weights in registers, the operand streams) against the bf16 shadow of W1
+  S.dense1_wgrad = (S.dense1_gbm16 && al_wg && crnn_gemm_tn_bf16_stream_supported_ld(d.feat, d.tds, TB, d.feat, d.tds, d.tds, kGemmScratchBytes) == CRNN_OK) ? TN_STREAM_BF16
+                   : (stream_planes && al_wg && crnn_gemm_tn_planes_stream_supported(d.feat, d.tds, TB, d.feat, d.tds, d.tds, kGemmScratchBytes) == CRNN_OK) ? TN_PLANES_STREAM : TN_TILE;
+  S.dense1_dgrad_wres = S.dense1_gbm16 && shadow("dense1_w") && crnn_gemm_wres_bf16_supported(TB, d.feat, d.tds) == CRNN_OK;
   S.dense2_bwd_fused = !tile_gemms && crnn_dense_bwd_small_supported(TB, 2 * u, d.C) == CRNN_OK;
   S.dense2_bwd_small = S.dense2_bwd_fused && al_wp;
+  S.drop_keep_fused = c->dropout && S.dense2_bwd_fused && al_w && crnn_dropout_keep_supported(TB, 2 * u, 2 * u, 2 * u) == CRNN_OK;
   // recurrences: bf16 U^T in the bf16 modes (u % 128 == 0); persistent one-launch-per-layer kernels with XCD-local clusters (profiles/r03_lstm_cache_policy.txt)
   S.dtu = (mode && u % 128 == 0) ? CRNN_BF16 : CRNN_F32;
   S.rnn_persist = !(fl & CRNN_FLAG_RNN_STEP_KERNELS) && (c->gru ? crnn_gru_persist_supported(u, S.dtu) : crnn_lstm_persist_supported(u, S.dtu)) == CRNN_OK;
   S.rnn_uw = (fl & CRNN_FLAG_RNN_LINEAR_CLUSTERS) ? 0 : CRNN_RNN_XCD_LOCAL;
   S.xw_stream = S.dtu == CRNN_BF16 && !tile_gemms && TB % 64 == 0 && G % 128 == 0 && d.tds % 64 == 0 && u % 64 == 0;
-  S.xw_both[0] = S.xw_stream && crnn_rnn_input_proj_supported((int)TB, G, d.tds) == CRNN_OK;
-  S.xw_both[1] = S.xw_stream && crnn_rnn_input_proj_supported((int)TB, G, u) == CRNN_OK;
+  for (int l = 0; l < 2; ++l) {
+    const std::string n = "rnn" + std::to_string(l + 1);
+    const int din = l ? u : d.tds, ldh = l ? 2 * u : u, Nh = c->gru ? 2 * u : G;   // (GRU: only the z, r columns see h_prev)
+    // both directions' projections in one launch of persistent workgroups, else one stripe-stream launch each (bit-identical); both read the bias from the parameters
+    S.xw[l] = !(S.xw_stream && al_wp) ? XW_TILE : crnn_rnn_input_proj_supported_ld((int)TB, G, din, din, din, G) == CRNN_OK ? XW_BOTH
+              : crnn_gemm_nt_f32_stream_bias_supported((int)TB, G, din, din, din, G) == CRNN_OK ? XW_STRIPES : XW_TILE;
+    // the persistent backward recurrence reads U from the bf16 shadow in the bf16 modes (u % 128 == 0), else from the fp32 parameter
+    S.rnn_bwd_persist[l] = S.rnn_persist && (S.dtu == CRNN_BF16 ? shadow(n + "f_u") && shadow(n + "b_u") : (al & AL_PARAMS) != 0);
+    // weight gradients C [M][N] = A^T B over K rows, A with row stride lda, dz and the gradient with G; `operands`: A and B as the driver offsets them are aligned
+    auto tn = [&](int M, int N, long K, int lda, bool operands) {
+      if (stream_bf16 && operands && al_wg && crnn_gemm_tn_stream_supported(M, N, K, lda, G, G, kGemmScratchBytes) == CRNN_OK) return TN_STREAM;
+      if (stream_planes && operands && al_wg && crnn_gemm_tn_planes_stream_supported(M, N, K, lda, G, G, kGemmScratchBytes) == CRNN_OK) return TN_PLANES_STREAM;
+      return TN_TILE;
+    };
+    S.rnn_dw[l] = tn(din, G, TB, din, true);                                        // dW = x^T dz over T*B rows
+    S.rnn_du[l][0] = tn(u, Nh, TB - B, ldh, at((long)B * G));                       // dU = h_prev^T dz over (T-1)*B rows -- forward direction: dz from row B on
+    S.rnn_du[l][1] = tn(u, Nh, TB - B, ldh, at((long)B * ldh + (l ? u : 0)));       // ... backward direction: h from row B on (layer 2: the second half of "h2")
+    S.rnn_dx[l] = (stream_bf16 && shadow(n + "f_w") && shadow(n + "b_w") && crnn_gemm_nt_f32_stream_supported((int)TB, din, G, G, G, din) == CRNN_OK) ? DX_STREAM_BF16
+                  : (stream_planes && al_wp && crnn_gemm_nt_f32x2_stream_supported((int)TB, din, G, G, G, din) == CRNN_OK) ? DX_PLANES_STREAM : DX_TILE;
+  }
   for (int i = 1; i <= 6; ++i)   // BatchNorm-2 backward statistics taken by the next block's depthwise backward: they outlive that block's other partials
     S.bn2parts = lmax(S.bn2parts, (long)crnn_dwconv_bwd_stream_rows_ex(B, d.bh[i + 1], d.bw[i + 1], d.bc[i], mode == 2 ? CRNN_BF16 : CRNN_F32) * 2L * d.bc[i]);
   if (mode != 2 && !bn2_stats) S.bn2parts = 0;
@@ -210,7 +245,7 @@ Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
       b.pool_rows = ph * pw;
     b.inf_dw = dws ? DWI_STREAM : (ci % slab == 0) ? DWI_FOLDED : DWI_PLAIN;
     b.inf_fold = !pooled || b.pool_rows > 1;
-    b.inf_pw = one ? PWI_ONE : (wres_ok && dtd == CRNN_BF16 && M <= 0x7fffffffL) ? PWI_WRES : PWI_TILE;
+    b.inf_pw = one ? PWI_ONE : (wres_ok && dtd == CRNN_BF16 && al_w && crnn_gemm_wres_bf16_supported(M, co, ci) == CRNN_OK) ? PWI_WRES : PWI_TILE;
     // ---- training forward
     const bool pro = i > 1 && S.b[i - 1].out == OUT_NEXT_BLOCK;
     if (pro || dws || dws_f32) { b.dw = pro ? DWF_PRO : DWF_STREAM; b.dw_rows = crnn_dwconv_fwd_stream_rows_ex(B, H, W, ci, dtd); }
@@ -258,21 +293,28 @@ Sched decide(const crnn_config* c, const Dims& d, int al = AL_ALL) {
     // data gradient: where the depthwise stage follows as one kernel (bf16) / in the parity mode, its epilogue also takes BatchNorm-1's backward statistics
     if (b.dq_planes) { b.dgrad = DG_PRES; b.dgrad_rows = crnn_gemm_pres_stat_rows(M, ci, co, 2); }
     else if (mode == 2 && dtq == CRNN_BF16 && dtd == CRNN_BF16 && !tile_gemms) {
-      b.dgrad = DG_WRES_BF16;
-      b.dgrad_rows = (b.dw_fused() && bn_stats && crnn_gemm_wres_bnstats_supported(M, ci, co) == CRNN_OK) ? crnn_gemm_wres_bnstats_rows(M, ci, co) : 0;
+      // bf16 tensors against the bf16 shadow of the block's weights: resident in registers (gemm_wres.hip) -- its storer waves also take the statistics where the
+      // depthwise stage follows as one kernel --, else streamed (gemm_nt.hip); a shadow that is not 16-byte aligned: the tile GEMM and the stand-alone statistics
+      const bool sh = shadow("b" + std::to_string(i) + "_pw");
+      if (sh && b.dw_fused() && bn_stats && crnn_gemm_wres_bnstats_supported(M, ci, co) == CRNN_OK) { b.dgrad = DG_WRES_BF16; b.dgrad_rows = crnn_gemm_wres_bnstats_rows(M, ci, co); }
+      else b.dgrad = !sh ? DG_GEMM : crnn_gemm_wres_bf16_supported(M, ci, co) == CRNN_OK ? DG_WRES_BF16 : (M <= 0x7fffffffL && crnn_gemm_nt_bf16_supported((int)M, ci, co) == CRNN_OK) ? DG_NT_BF16 : DG_GEMM;
     } else if (S.products == 2 && dtq == CRNN_F32 && dtd == CRNN_F32 && bn_stats && crnn_gemm_f32x3_bnstats_supported(M, ci, co) == CRNN_OK) {
-      b.dgrad = DG_PLANES_TILE; b.dgrad_rows = crnn_gemm_f32x3_bnstats_rows(M);
-      // (crnn_gemm_wres3_bnstats takes reductions of 256 channels: below, the tile kernel)
+      // the parity mode's statistics from the data gradient's epilogue: W^T planes resident for reductions of 256 channels (gemm_wres3.hip), else the plane tile GEMM
       if (!tile_gemms && co == 256 && crnn_gemm_wres3_supported(M, ci, co) == CRNN_OK && al_w) { b.dgrad = DG_WRES3; b.dgrad_rows = crnn_gemm_wres3_stat_rows(M, ci, co); }
+      else if (al_wp) { b.dgrad = DG_PLANES_TILE; b.dgrad_rows = crnn_gemm_f32x3_bnstats_rows(M); }
+      else b.dgrad = DG_GEMM;
     } else b.dgrad = DG_GEMM;
   }
   S.d2T_off = S.dense2_stream ? pwT : -1;
   S.d1T_off = S.dense1_stream ? pwT + 128L * 2 * u : -1;
   S.pwT_count += 128L * 2 * u + (S.dense1_stream ? (long)d.feat * d.tds : 0);
+  // the dense layers' forward on the stripe stream against their W^T copies in "pwT" (dense1: and its bias)
+  S.dense1_fwd_stream = S.dense1_stream && al_wp && S.d1T_off % 8 == 0;
+  S.dense2_fwd_stream = S.dense2_stream && al_w && S.d2T_off % 8 == 0;
   return S;
 }
 
-Plan make_plan(const crnn_config* c, const Dims& d, const Sched& S) {
+Plan make_plan(const crnn_config* c, const Dims& d, const Layout& L, const Sched& S) {
   Plan P;
   const long B = d.B;
   // BatchNorm state blocks [mean|var|scale|shift] first: their offsets must stay small (int) for crnn_bn_update
@@ -333,7 +375,7 @@ Plan make_plan(const crnn_config* c, const Dims& d, const Sched& S) {
   P.add("dlogits", TB * d.C); P.add("dr2", TB * 2 * d.u); P.add("dr1", TB * d.u);
   P.add("dcf", B * d.u); P.add("dcb", B * d.u); P.add("dhpf", B * d.u); P.add("dhpb", B * d.u);
   P.add("ddn1", TB * d.tds); P.add("gbm", TB * d.tds);
-  if (S.dense1_dgrad_wres) P.add("gbm16", TB * d.tds, CRNN_BF16);   // bf16 copy of dense1's output gradient (operand of the weights-resident GEMM)
+  if (S.dense1_gbm16) P.add("gbm16", TB * d.tds, CRNN_BF16);   // bf16 copy of dense1's output gradient (operand of both backward GEMMs)
   maxact = lmax(maxact, TB * d.feat);
   // gradient ping-pong buffers: sized for fp32, hold bf16 tensors in storage mode 2
   P.add("gA", maxact); P.add("gB", maxact); P.add("gC", maxact);   // conv-stack gradient buffers (three: a weight-gradient GEMM on the side stream may still read one)
@@ -356,7 +398,7 @@ Plan make_plan(const crnn_config* c, const Dims& d, const Sched& S) {
     P.add("d2part", (long)(crnn_dense_bwd_small_scratch_bytes(TB, 2 * d.u, d.C) / sizeof(float)));   // per-workgroup partial gradients of dense2
     P.add("keep9", (TB * 2 * d.u / 8 + 3) / 4);   // keep bytes of the Dropout(.2) under dense2 (written by the forward's dropout pass, read by the one-pass backward)
   }
-  P.add("pbf", make_layout(c).total, CRNN_BF16);   // bf16 shadow of the parameter buffer (GEMM B operands in the bf16 modes)
+  P.add("pbf", L.total, CRNN_BF16);   // bf16 shadow of the parameter buffer (GEMM B operands in the bf16 modes)
   P.add("coef", 2 * 1024);
   P.add("fold", 32 * 2 * 1024);   // chunk sums of long BatchNorm partial lists (crnn_bn_finalize_folded)
   P.add("gemm_scratch", 16L * 1024 * 1024);   // 64 MiB of split-reduction partials (main stream)
@@ -365,7 +407,7 @@ Plan make_plan(const crnn_config* c, const Dims& d, const Sched& S) {
   if (S.rnn_persist) P.add("rnnx", (long)((crnn_lstm_persist_xbuf_bytes(d.T, d.B, d.u, S.dtu) + 3) / 4));   // h_t / dz_t exchange tiles
   return P;
 }
-Plan make_plan(const crnn_config* c) { Dims d = make_dims(c); return make_plan(c, d, decide(c, d)); }
+Plan make_plan(const crnn_config* c) { Dims d = make_dims(c); Layout L = make_layout(c); return make_plan(c, d, L, decide(c, d, L)); }
 
 bool aligned16(const void* a, const void* b = nullptr) { return ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0; }
 
@@ -396,17 +438,13 @@ const float* rnn_u_operand(const Ctx& c, const std::string& layer_dir, int* dtu)
   return c.S.dtu == CRNN_BF16 ? weight_operand(c, 0, U, dtu) : U;
 }
 // One context per entry point: dimensions, layout, record and plan are built once.  The plan is the aligned record's (no workspace byte depends on the
-// caller's pointers); the persistent backward recurrences need 16-byte aligned U operands, which for the bf16 shadows depends on the layout's offsets.
+// caller's pointers); the record the passes read is the one for the pointers they were given.
 Ctx make_ctx(const crnn_config* cfg, const float* params, float* grads, float* ws, hipStream_t stream) {
   Ctx c{cfg, make_dims(cfg), make_layout(cfg), Plan(), Sched(), params, grads, ws, stream};
-  c.S = decide(cfg, c.d);
-  c.P = make_plan(cfg, c.d, c.S);
+  c.S = decide(cfg, c.d, c.L);
+  c.P = make_plan(cfg, c.d, c.L, c.S);
   const int al = (aligned16(ws) ? AL_WS : 0) | (aligned16(params) ? AL_PARAMS : 0) | (aligned16(grads) ? AL_GRADS : 0);
-  if (al != AL_ALL) c.S = decide(cfg, c.d, al);
-  for (int l = 1; l <= 2; ++l) {
-    int dtu = CRNN_F32;
-    c.S.rnn_bwd_persist[l - 1] = c.S.rnn_persist && aligned16(rnn_u_operand(c, std::to_string(l) + "f", &dtu), rnn_u_operand(c, std::to_string(l) + "b", &dtu));
-  }
+  if (al != AL_ALL) c.S = decide(cfg, c.d, c.L, al);
   return c;
 }
 // GEMMs of the conv stack / dense layers / RNN input projections: bf16 products when cfg->mfma_bf16
@@ -525,7 +563,52 @@ extern "C" int crnn_ws_tensor_info(const crnn_config* cfg, const char* name, lon
 // then never written by a training forward.  (16-byte aligned parameter / workspace base pointers assumed, as torch allocations are.)
 extern "C" int crnn_block_output_fused(const crnn_config* cfg, int block) {
   if (check_cfg(cfg) || block < 1 || block > 7) return 0;
-  return decide(cfg, make_dims(cfg)).b[block].out == OUT_NEXT_BLOCK ? 1 : 0;
+  return decide(cfg, make_dims(cfg), make_layout(cfg)).b[block].out == OUT_NEXT_BLOCK ? 1 : 0;
+}
+// The record as text (include/crnn_mi355x.h): every field of decide()'s answer for the given alignment mask, the enum values by name
+extern "C" int crnn_schedule_describe(const crnn_config* cfg, int aligned_mask, char* buf, int cap) {
+  static const char* const dt[] = {"f32", "bf16"};
+  static const char* const dwi[] = {"DWI_STREAM", "DWI_FOLDED", "DWI_PLAIN"}, *const pwi[] = {"PWI_ONE", "PWI_WRES", "PWI_TILE"};
+  static const char* const dwf[] = {"DWF_PRO", "DWF_STREAM", "DWF_TILE_STATS", "DWF_C1", "DWF_TILE_COLREDUCE"};
+  static const char* const bn1[] = {"BN1_PASS", "BN1_GEMM_BF16", "BN1_GEMM_PLANES", "BN1_PW1"};
+  static const char* const pwf[] = {"PWF_PW1_BN", "PWF_PW1", "PWF_WRES3", "PWF_PLANES_TILE", "PWF_WRES", "PWF_BNRELU6_TILE", "PWF_TILE"};
+  static const char* const out[] = {"OUT_NEXT_BLOCK", "OUT_QMAX", "OUT_PLAIN"}, *const bn2[] = {"BN2_APPLY", "BN2_QMAX", "BN2_PLAIN"};
+  static const char* const wg[] = {"WG_PW1_BN", "WG_PW1", "WG_STREAM_BF16", "WG_TILE_BF16", "WG_PLANES_STREAM", "WG_PLANES_TILE", "WG_GEMM"};
+  static const char* const dg[] = {"DG_PW1", "DG_PRES", "DG_WRES_BF16", "DG_NT_BF16", "DG_WRES3", "DG_PLANES_TILE", "DG_GEMM"};
+  static const char* const dwb[] = {"DWB_PRO", "DWB_STREAM", "DWB_TILE_FUSED", "DWB_C1", "DWB_THREE_KERNELS"};
+  static const char* const tn[] = {"TN_STREAM", "TN_STREAM_BF16", "TN_PLANES_STREAM", "TN_TILE"}, *const dx[] = {"DX_STREAM_BF16", "DX_PLANES_STREAM", "DX_TILE"};
+  static const char* const xwn[] = {"XW_BOTH", "XW_STRIPES", "XW_TILE"};
+  static_assert(sizeof dg / sizeof *dg == DG_GEMM + 1 && sizeof wg / sizeof *wg == WG_GEMM + 1 && sizeof pwf / sizeof *pwf == PWF_TILE + 1 && sizeof tn / sizeof *tn == TN_TILE + 1, "one name per value");
+  CRNN_TRY(check_cfg(cfg));
+  if (cap < 0 || (cap > 0 && !buf)) return CRNN_ERR_ARG;
+  const Sched S = decide(cfg, make_dims(cfg), make_layout(cfg), aligned_mask & AL_ALL);
+  std::string t;
+  char line[768];
+  for (int i = 1; i <= 7; ++i) {
+    const BlockSched& b = S.b[i];
+    snprintf(line, sizeof line, "block%d: dtd=%s dtq=%s dtx=%s pwT_off=%ld qm=%d dm=%d inf_dw=%s inf_pw=%s pool_rows=%d inf_fold=%d dw=%s dw_rows=%d bn1=%s pw=%s pw_rows=%d out=%s "
+             "bn2_rows=%d dq_planes=%d bn2_bwd=%s wgrad=%s dgrad=%s dgrad_rows=%d dwb=%s\n", i, dt[b.dtd], dt[b.dtq], dt[b.dtx], b.pwT_off, b.has_qm, b.has_dm, dwi[b.inf_dw],
+             pwi[b.inf_pw], b.pool_rows, b.inf_fold, dwf[b.dw], b.dw_rows, bn1[b.bn1], pwf[b.pw], b.pw_rows, out[b.out], b.bn2_rows, b.dq_planes, bn2[b.bn2_bwd], wg[b.wgrad],
+             dg[b.dgrad], b.dgrad_rows, dwb[b.dwb]);
+    t += line;
+  }
+  snprintf(line, sizeof line, "top: products=%d products_fwd=%d planes_fwd=%d planes_bwd=%d loc=%s bn2parts=%ld pwT_count=%ld d2T_off=%ld d1T_off=%ld dtu=%s rnn=%s rnn_uw=%d\n", S.products,
+           S.products_fwd, S.planes_fwd, S.planes_bwd, S.loc_fused ? "LOC_FUSED" : "LOC_KERNELS", S.bn2parts, S.pwT_count, S.d2T_off, S.d1T_off, dt[S.dtu], S.rnn_persist ? "RNN_PERSIST" : "RNN_STEPS",
+           S.rnn_uw);
+  t += line;
+  snprintf(line, sizeof line, "dense1: wT=%d fwd=%s gbm16=%d wgrad=%s dgrad=%s\n", S.dense1_stream, S.dense1_fwd_stream ? "D1F_STREAM" : "D1F_TILE", S.dense1_gbm16, tn[S.dense1_wgrad],
+           S.dense1_dgrad_wres ? "D1G_WRES_BF16" : "D1G_TILE");
+  t += line;
+  for (int l = 0; l < 2; ++l) {
+    snprintf(line, sizeof line, "rnn%d: xw=%s bwd=%s dw=%s du_f=%s du_b=%s dx=%s\n", l + 1, xwn[S.xw[l]],
+             S.rnn_bwd_persist[l] ? "RNN_PERSIST" : "RNN_STEPS", tn[S.rnn_dw[l]], tn[S.rnn_du[l][0]], tn[S.rnn_du[l][1]], dx[S.rnn_dx[l]]);
+    t += line;
+  }
+  snprintf(line, sizeof line, "dense2: drop=%s wT=%d fwd=%s d2part=%d bwd=%s\n", S.drop_keep_fused ? "DROP_KEEP_FUSED" : "DROP_PASSES", S.dense2_stream, S.dense2_fwd_stream ? "D2F_STREAM" : "D2F_TILE", S.dense2_bwd_fused,
+           S.dense2_bwd_small ? "D2B_SMALL" : "D2B_GEMMS");
+  t += line;
+  if (cap > 0) { strncpy(buf, t.c_str(), cap - 1); buf[cap - 1] = 0; }
+  return (int)t.size();
 }
 extern "C" int crnn_ws_tensor(const crnn_config* cfg, const char* name, long* offset, long* count) {
   return crnn_ws_tensor_info(cfg, name, offset, count, nullptr);
@@ -703,17 +786,11 @@ extern "C" int crnn_forward_ex(const crnn_config* cfg, const float* params, cons
           CRNN_TRY(crnn_bn_act_pool_drop_ex(dd, s1, aa, 1, 1, (int)M, ci, 1, 1, 0.f, 0, 0, dtd, dtd, stream));
       }
       const bool fold = b.inf_fold;
-      int rc = CRNN_ERR_UNSUPPORTED;
-      if (b.inf_pw == PWI_ONE) rc = fold ? crnn_pw1_fwd_folded(aa, kpw, xo, M, co, s2, dtq, stream) : crnn_pw1_fwd(aa, kpw, qq, M, co, nullptr, dtq, stream);
-      else if (b.pool_rows > 1) rc = crnn_pwconv_fwd_wres_folded_pool(aa, wq.w, xo, M, co, ci, s2, b.pool_rows, stream);   // (no fallback that could read window-major rows)
-      else {
-        // bf16 tensors + W^T: the weights-resident kernel (folded BatchNorm in its MFMA waves' epilogue, or the plain product).  It refuses row offsets
-        // beyond 32 bits, which no query of gemm_wres.hip exposes: then the tile kernel
-        if (b.inf_pw == PWI_WRES) rc = fold ? crnn_pwconv_fwd_wres_folded(aa, wq.w, xo, M, co, ci, s2, stream) : crnn_gemm_wres_bf16(aa, wq.w, qq, (int)M, co, ci, stream);
-        if (rc == CRNN_ERR_UNSUPPORTED)
-          rc = crnn_pwconv_fwd(aa, wq.w, fold ? xo : qq, M, co, ci, nullptr, fold ? s2 : nullptr, S.products_fwd, dtd, wq.dt, dtq, wq.transposed, stream);
-      }
-      CRNN_TRY(rc);
+      if (b.inf_pw == PWI_ONE) CRNN_TRY(fold ? crnn_pw1_fwd_folded(aa, kpw, xo, M, co, s2, dtq, stream) : crnn_pw1_fwd(aa, kpw, qq, M, co, nullptr, dtq, stream));
+      else if (b.pool_rows > 1) CRNN_TRY(crnn_pwconv_fwd_wres_folded_pool(aa, wq.w, xo, M, co, ci, s2, b.pool_rows, stream));
+      else if (b.inf_pw == PWI_WRES)   // bf16 tensors + W^T: the weights-resident kernel (folded BatchNorm in its MFMA waves' epilogue, or the plain product)
+        CRNN_TRY(fold ? crnn_pwconv_fwd_wres_folded(aa, wq.w, xo, M, co, ci, s2, stream) : crnn_gemm_wres_bf16(aa, wq.w, qq, (int)M, co, ci, stream));
+      else CRNN_TRY(crnn_pwconv_fwd(aa, wq.w, fold ? xo : qq, M, co, ci, nullptr, fold ? s2 : nullptr, S.products_fwd, dtd, wq.dt, dtq, wq.transposed, stream));
       if (!fold) CRNN_TRY(crnn_bn_act_pool_drop_ex(qq, s2, xo, B, H, W, co, ph, pw, 0.f, seed, (uint32_t)i, dtq, b.dtx, stream));
       in = xo;
       continue;
@@ -796,22 +873,18 @@ extern "C" int crnn_forward_ex(const crnn_config* cfg, const float* params, cons
       }
     CRNN_TRY(crnn_transpose_batch(params, c.w("ut1f"), n, in_off, out_off, R, Cc, S.dtu, stream));
   }
-  auto xw = [&](const float* xin, int din, const std::string& s) -> int {
-    if (S.xw_stream)
+  auto xw = [&](const float* xin, int din, const std::string& s, bool stripes) -> int {
+    if (stripes)
       return crnn_gemm_nt_f32_stream_bias(xin, c.w("wt" + s), nullptr, nullptr, c.w("xw" + s), c.p("rnn" + s + "_b"), TB, G, din, din, din, G, stream);
     return gemm(c, 0, xin, c.p("rnn" + s + "_w"), c.w("xw" + s), TB, G, din, din, G, G, c.p("rnn" + s + "_b"));
   };
-  // both directions of a layer in one launch of persistent workgroups (crnn_rnn_input_proj; bit-identical to the two stripe launches).  It refuses row
-  // offsets beyond 32 bits, which its query does not expose: then the two launches
+  // both directions of a layer in one launch of persistent workgroups (crnn_rnn_input_proj; bit-identical to the two stripe launches)
   auto xw2 = [&](const float* xin, int din, int layer) -> int {
     const std::string f = std::to_string(layer) + "f", b = std::to_string(layer) + "b";
-    if (S.xw_both[layer - 1]) {
-      const int rc = crnn_rnn_input_proj(xin, c.w("wt" + f), c.w("wt" + b), c.p("rnn" + f + "_b"), c.p("rnn" + b + "_b"), c.w("xw" + f), c.w("xw" + b), TB, G, din,
-                                         din, din, G, stream);
-      if (rc != CRNN_ERR_UNSUPPORTED) return rc;
-    }
-    CRNN_TRY(xw(xin, din, f));
-    return xw(xin, din, b);
+    if (S.xw[layer - 1] == XW_BOTH)
+      return crnn_rnn_input_proj(xin, c.w("wt" + f), c.w("wt" + b), c.p("rnn" + f + "_b"), c.p("rnn" + b + "_b"), c.w("xw" + f), c.w("xw" + b), TB, G, din, din, din, G, stream);
+    CRNN_TRY(xw(xin, din, f, S.xw[layer - 1] == XW_STRIPES));
+    return xw(xin, din, b, S.xw[layer - 1] == XW_STRIPES);
   };
   CRNN_TRY(xw2(c.w("dn1"), d.tds, 1));
   CRNN_TRY(rnn_fwd(c, "1", c.w("h1f"), c.w("h1b"), u));
@@ -820,32 +893,24 @@ extern "C" int crnn_forward_ex(const crnn_config* cfg, const float* params, cons
   CRNN_TRY(rnn_fwd(c, "2", c.w("h2"), c.w("h2") + u, 2 * u));                    // merge_mode='concat'
   const float* r2 = c.w("h2");
   if (train) {  // Dropout(.2) (utils.py:83)
-    const bool keep9 = cfg->dropout && S.dense2_bwd_fused;   // dense2's one-pass backward reads the decisions as keep bytes
-    int rcd = CRNN_ERR_UNSUPPORTED;
-    // the dropped activations and the keep bytes in one pass; crnn_dropout_keep has no shape query (whole groups of 8 columns, 32-bit group counter): else two passes
-    if (keep9) rcd = crnn_dropout_keep(c.w("h2"), c.w("r2d"), c.w("keep9"), TB, 2 * u, 2 * u, 2 * u, kDropRnn, seed, kLayerRnn, stream);
-    if (rcd == CRNN_ERR_UNSUPPORTED) {
+    // dense2's one-pass backward reads the decisions as keep bytes: written with the dropped activations in one pass, else by a pass of their own
+    if (S.drop_keep_fused) CRNN_TRY(crnn_dropout_keep(c.w("h2"), c.w("r2d"), c.w("keep9"), TB, 2 * u, 2 * u, 2 * u, kDropRnn, seed, kLayerRnn, stream));
+    else {
       CRNN_TRY(crnn_dropout(c.w("h2"), c.w("r2d"), TB, 2 * u, 2 * u, 2 * u, cfg->dropout ? kDropRnn : 0.f, seed, kLayerRnn, stream));
-      rcd = keep9 ? crnn_dropout_keep_bytes(c.w("keep9"), (long)TB * 2 * u / 8, kDropRnn, seed, kLayerRnn, stream) : CRNN_OK;
+      if (cfg->dropout && S.dense2_bwd_fused) CRNN_TRY(crnn_dropout_keep_bytes(c.w("keep9"), (long)TB * 2 * u / 8, kDropRnn, seed, kLayerRnn, stream));
     }
-    CRNN_TRY(rcd);
     r2 = c.w("r2d");
   }
   // ---- dense2 + softmax (utils.py:85-86); back to batch-major [B][T][C]
   // round 5: the product on the streaming kernel (64-row stripes against the 128-row padded bf16 W^T through LDS; the tile GEMM ran 104 workgroups for 35 us), bias +
-  // row permutation + softmax + the y_pred copy in one pass over its output: dropout aside, four launches (56 us) -> two (18 us).  The stream kernel has no
-  // shape query (leading dimensions, 32-bit row offsets): the tile GEMM where it refuses
-  int rc2 = CRNN_ERR_UNSUPPORTED;
-  if (S.dense2_stream) rc2 = crnn_gemm_nt_f32_stream_bias(r2, pwT + S.d2T_off, nullptr, nullptr, c.w("lg128"), nullptr, TB, 128, 2 * u, 2 * u, 2 * u, 128, stream);
-  bool ypred_out = false;                  // y_pred already written by the fused epilogue
-  if (rc2 == CRNN_OK) {
-    CRNN_TRY(crnn_softmax_rows_perm(c.w("lg128"), 128, c.p("dense2_b"), c.w("logits"), c.w("ypred"), y_pred, TB, d.C, B, stream));
-    ypred_out = y_pred != nullptr;
-  } else if (rc2 == CRNN_ERR_UNSUPPORTED) {
-    CRNN_TRY(gemm(c, 0, r2, c.p("dense2_w"), c.w("logits"), TB, d.C, 2 * u, 2 * u, d.C, d.C, c.p("dense2_b"), 0, 0, B));
-    CRNN_TRY(crnn_softmax_rows(c.w("logits"), c.w("ypred"), TB, d.C, stream));
-  } else return rc2;
-  if (y_pred && y_pred != c.w("ypred") && !ypred_out) {
+  // row permutation + softmax + the y_pred copy in one pass over its output: dropout aside, four launches (56 us) -> two (18 us)
+  if (S.dense2_fwd_stream) {
+    CRNN_TRY(crnn_gemm_nt_f32_stream_bias(r2, pwT + S.d2T_off, nullptr, nullptr, c.w("lg128"), nullptr, TB, 128, 2 * u, 2 * u, 2 * u, 128, stream));
+    return crnn_softmax_rows_perm(c.w("lg128"), 128, c.p("dense2_b"), c.w("logits"), c.w("ypred"), y_pred, TB, d.C, B, stream);   // (writes y_pred too)
+  }
+  CRNN_TRY(gemm(c, 0, r2, c.p("dense2_w"), c.w("logits"), TB, d.C, 2 * u, 2 * u, d.C, d.C, c.p("dense2_b"), 0, 0, B));
+  CRNN_TRY(crnn_softmax_rows(c.w("logits"), c.w("ypred"), TB, d.C, stream));
+  if (y_pred && y_pred != c.w("ypred")) {
     hipError_t e = hipMemcpyAsync(y_pred, c.w("ypred"), (size_t)TB * d.C * sizeof(float), hipMemcpyDeviceToDevice, stream);
     if (e != hipSuccess) return (int)e;
   }
@@ -876,28 +941,28 @@ static int rnn_bwd_chain(const Ctx& c, int layer, const float* hf, const float* 
                     : crnn_lstm_bwd_persist_db(uf, ub, csf, csb, gtf, gtb, doutf, doutb, ldo, dzf, dzb, dbf, dbb, T, B, u, dtu, c.w("rnnx"), xbytes, 0, c.S.rnn_uw, c.s);
 }
 // C[M][N] = A^T B over K rows (weight gradients of the recurrent layers): the streaming kernel in the bf16 modes (gemm_wgrad.hip, fp32 operands rounded to
-// bf16 on the way in like the tile GEMM does), the pixel-stream form of the two-plane weight gradient in the parity mode (gemm_wgrad3.hip); neither has a
-// shape query: the tile GEMM where they refuse
-static int gemm_tn(const Ctx& c, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc) {
-  int rc = CRNN_ERR_UNSUPPORTED;
-  if (c.S.bwd_stream_bf16) rc = crnn_gemm_tn_stream(A, lda, B, ldb, C, ldc, M, N, K, c.scratch(), kGemmScratchBytes, c.s);
-  else if (c.S.bwd_stream_planes) rc = crnn_gemm_tn_planes_stream(A, lda, B, ldb, C, ldc, M, N, K, c.scratch(), kGemmScratchBytes, c.s);
-  if (rc != CRNN_ERR_UNSUPPORTED) return rc;
-  return gemm(c, 2, A, B, C, M, N, K, lda, ldb, ldc, nullptr, 0, 0, 0, c.S.planes_bwd);
+// bf16 on the way in like the tile GEMM does), the pixel-stream form of the two-plane weight gradient in the parity mode (gemm_wgrad3.hip), else the tile GEMM
+static int gemm_tn(const Ctx& c, int kernel, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc) {
+  switch (kernel) {
+    case TN_STREAM: return crnn_gemm_tn_stream(A, lda, B, ldb, C, ldc, M, N, K, c.scratch(), kGemmScratchBytes, c.s);
+    case TN_PLANES_STREAM: return crnn_gemm_tn_planes_stream(A, lda, B, ldb, C, ldc, M, N, K, c.scratch(), kGemmScratchBytes, c.s);
+    default: return gemm(c, 2, A, B, C, M, N, K, lda, ldb, ldc, nullptr, 0, 0, 0, c.S.planes_bwd);
+  }
 }
 static int rnn_bwd_wgrads(const Ctx& c, int layer, const float* xin, int ldx, int din, const float* hf, const float* hb, int ldh) {
   const Dims& d = c.d;
+  const Sched& S = c.S;
   const int T = d.T, B = d.B, TB = T * B, u = d.u, G = d.G;
   std::string l = std::to_string(layer);
   float* dzf = c.w("dz" + l + "f"); float* dzb = c.w("dz" + l + "b");
   // dW = X^T dZ ; dU = Hprev^T dZ ; db = colsum(dZ)
-  CRNN_TRY(gemm_tn(c, xin, dzf, c.g("rnn" + l + "f_w"), din, G, TB, ldx, G, G));
-  CRNN_TRY(gemm_tn(c, xin, dzb, c.g("rnn" + l + "b_w"), din, G, TB, ldx, G, G));
+  CRNN_TRY(gemm_tn(c, S.rnn_dw[layer - 1], xin, dzf, c.g("rnn" + l + "f_w"), din, G, TB, ldx, G, G));
+  CRNN_TRY(gemm_tn(c, S.rnn_dw[layer - 1], xin, dzb, c.g("rnn" + l + "b_w"), din, G, TB, ldx, G, G));
   const int K1 = (T - 1) * B;
   // forward direction: h_{t-1} pairs with dz_t ; backward direction: h_{t+1} pairs with dz_t
   const int Nh = c.cfg->gru ? 2 * u : G;   // GRU: only the z,r columns see h_prev; the candidate sees r*h_prev
-  CRNN_TRY(gemm_tn(c, hf, dzf + (long)B * G, c.g("rnn" + l + "f_u"), u, Nh, K1, ldh, G, G));
-  CRNN_TRY(gemm_tn(c, hb + (long)B * ldh, dzb, c.g("rnn" + l + "b_u"), u, Nh, K1, ldh, G, G));
+  CRNN_TRY(gemm_tn(c, S.rnn_du[layer - 1][0], hf, dzf + (long)B * G, c.g("rnn" + l + "f_u"), u, Nh, K1, ldh, G, G));
+  CRNN_TRY(gemm_tn(c, S.rnn_du[layer - 1][1], hb + (long)B * ldh, dzb, c.g("rnn" + l + "b_u"), u, Nh, K1, ldh, G, G));
   if (c.cfg->gru) {
     CRNN_TRY(gemm(c, 2, c.w("cs" + l + "f"), dzf + 2 * u, c.g("rnn" + l + "f_u") + 2 * u, u, u, TB, u, G, G, nullptr, 0, 0, 0, c.S.planes_bwd));
     CRNN_TRY(gemm(c, 2, c.w("cs" + l + "b"), dzb + 2 * u, c.g("rnn" + l + "b_u") + 2 * u, u, u, TB, u, G, G, nullptr, 0, 0, 0, c.S.planes_bwd));
@@ -915,19 +980,19 @@ static int rnn_bwd_dx(const Ctx& c, int layer, int din, float* dxin) {
   std::string l = std::to_string(layer);
   float *dzf = c.w("dz" + l + "f"), *dzb = c.w("dz" + l + "b");
   const float *wf = c.p("rnn" + l + "f_w"), *wb = c.p("rnn" + l + "b_w");
-  // both directions in one stripe-stream launch: bf16 modes (gemm_wgrad.hip, the weights' bf16 shadows) / parity mode, two-plane backward (gemm_wgrad3.hip);
-  // neither has a shape query: the tile GEMMs where they refuse
-  int rc = CRNN_ERR_UNSUPPORTED;
-  if (c.S.bwd_stream_bf16) {
-    int dtf = CRNN_F32, dtb = CRNN_F32;
-    const float* sf = weight_operand(c, 1, wf, &dtf);
-    const float* sb = weight_operand(c, 1, wb, &dtb);
-    rc = crnn_gemm_nt_f32_stream(dzf, sf, dzb, sb, dxin, TB, din, G, G, G, din, c.s);
-  } else if (c.S.bwd_stream_planes)
-    rc = crnn_gemm_nt_f32x2_stream(dzf, wf, dzb, wb, dxin, TB, din, G, G, G, din, c.s);
-  if (rc != CRNN_ERR_UNSUPPORTED) return rc;
-  CRNN_TRY(gemm(c, 1, dzf, wf, dxin, TB, din, G, G, G, din, nullptr, 0, 0, 0, c.S.planes_bwd));
-  return gemm(c, 1, dzb, wb, dxin, TB, din, G, G, G, din, nullptr, 0, 1, 0, c.S.planes_bwd);
+  // both directions in one stripe-stream launch: bf16 modes (gemm_wgrad.hip, the weights' bf16 shadows) / parity mode, two-plane backward (gemm_wgrad3.hip)
+  switch (c.S.rnn_dx[layer - 1]) {
+    case DX_STREAM_BF16: {
+      int dtf = CRNN_F32, dtb = CRNN_F32;
+      const float* sf = weight_operand(c, 1, wf, &dtf);
+      const float* sb = weight_operand(c, 1, wb, &dtb);
+      return crnn_gemm_nt_f32_stream(dzf, sf, dzb, sb, dxin, TB, din, G, G, G, din, c.s);
+    }
+    case DX_PLANES_STREAM: return crnn_gemm_nt_f32x2_stream(dzf, wf, dzb, wb, dxin, TB, din, G, G, G, din, c.s);
+    default:
+      CRNN_TRY(gemm(c, 1, dzf, wf, dxin, TB, din, G, G, G, din, nullptr, 0, 0, 0, c.S.planes_bwd));
+      return gemm(c, 1, dzb, wb, dxin, TB, din, G, G, G, din, nullptr, 0, 1, 0, c.S.planes_bwd);
+  }
 }
 
 // The backward runs in two stages so that a data-parallel host can start the gradient all-reduce of the upper
@@ -1017,28 +1082,19 @@ int backward_top(const Ctx& c, const int* labels, const int* input_length, const
   CRNN_TRY(rnn_bwd_wgrads(c, 1, c.w("dn1"), d.tds, d.tds, c.w("h1f"), c.w("h1b"), u));
   CRNN_TRY(rnn_bwd_dx(c, 1, d.tds, c.w("ddn1")));
   // ---- Dropout(.4) + relu of dense1, rows back to batch-major
-  const bool wres1 = S.dense1_dgrad_wres;   // bf16 tensors: both of dense1's backward GEMMs read a bf16 copy of its output gradient
-  CRNN_TRY(crnn_relu_bwd_ex(c.w("dn1"), c.w("ddn1"), c.w("gbm"), wres1 ? c.w("gbm16") : nullptr, TB, d.tds, cfg->dropout ? 1.0f / (1.0f - kDropDense1) : 1.0f, B, stream));
+  // (bf16 tensors: both of dense1's backward GEMMs read a bf16 copy of its output gradient)
+  CRNN_TRY(crnn_relu_bwd_ex(c.w("dn1"), c.w("ddn1"), c.w("gbm"), S.dense1_gbm16 ? c.w("gbm16") : nullptr, TB, d.tds, cfg->dropout ? 1.0f / (1.0f - kDropDense1) : 1.0f, B, stream));
   const float* feat = c.w("x7");
-  const int dtx7 = S.b[7].dtx;
-  // weight gradient on the pixel streams, 36 feature tiles x 7 row ranges: both operands bf16 (gemm_wgrad.hip) / parity mode, two-plane backward (gemm_wgrad3.hip).
-  // Their rules on leading dimensions and row offsets are not all in a query: the tile GEMM where they refuse
-  int rcw = CRNN_ERR_UNSUPPORTED;
-  if (wres1) rcw = crnn_gemm_tn_bf16_stream(feat, d.feat, c.w("gbm16"), d.tds, c.g("dense1_w"), d.tds, d.feat, d.tds, TB, c.scratch(), kGemmScratchBytes, stream);
-  if (rcw == CRNN_ERR_UNSUPPORTED && S.bwd_stream_planes)
-    rcw = crnn_gemm_tn_planes_stream(feat, d.feat, c.w("gbm"), d.tds, c.g("dense1_w"), d.tds, d.feat, d.tds, TB, c.scratch(), kGemmScratchBytes, stream);
-  if (rcw == CRNN_ERR_UNSUPPORTED)
-    rcw = gemm_t(c, 2, feat, dtx7, c.w("gbm"), CRNN_F32, c.g("dense1_w"), CRNN_F32, d.feat, d.tds, TB, d.feat, d.tds, d.tds, nullptr, 0, 0, 0, planes);
-  CRNN_TRY(rcw);
+  // weight gradient on the pixel streams, 36 feature tiles x 7 row ranges: both operands bf16 (gemm_wgrad.hip) / parity mode, two-plane backward (gemm_wgrad3.hip)
+  switch (S.dense1_wgrad) {
+    case TN_STREAM_BF16: CRNN_TRY(crnn_gemm_tn_bf16_stream(feat, d.feat, c.w("gbm16"), d.tds, c.g("dense1_w"), d.tds, d.feat, d.tds, TB, c.scratch(), kGemmScratchBytes, stream)); break;
+    case TN_PLANES_STREAM: CRNN_TRY(crnn_gemm_tn_planes_stream(feat, d.feat, c.w("gbm"), d.tds, c.g("dense1_w"), d.tds, d.feat, d.tds, TB, c.scratch(), kGemmScratchBytes, stream)); break;
+    default: CRNN_TRY(gemm_t(c, 2, feat, S.b[7].dtx, c.w("gbm"), CRNN_F32, c.g("dense1_w"), CRNN_F32, d.feat, d.tds, TB, d.feat, d.tds, d.tds, nullptr, 0, 0, 0, planes));
+  }
   CRNN_TRY(colsum(c, c.w("gbm"), TB, d.tds, d.tds, c.g("dense1_b")));
-  // data gradient gA [T*B][feat] = gbm [T*B][tds] . W1^T on the weights-resident GEMM (gemm_wres.hip: 36 slices of 128 features keep their 128 x 128 weights in
-  // registers, the 3.4 MB operand streams).  It refuses a bf16 shadow of W1 that is not 16-byte aligned (the layout's offsets are multiples of 8 bytes there): the tile GEMM
-  float* gA = c.w("gA");
-  int rc1 = CRNN_ERR_UNSUPPORTED;
-  if (wres1) rc1 = crnn_gemm_wres_bf16(c.w("gbm16"), reinterpret_cast<const bf16_t*>(c.w("pbf")) + c.L.off("dense1_w"), gA, TB, d.feat, d.tds, stream);
-  if (rc1 == CRNN_ERR_UNSUPPORTED)
-    rc1 = gemm_t(c, 1, c.w("gbm"), CRNN_F32, c.p("dense1_w"), CRNN_F32, gA, c.gdt(), TB, d.feat, d.tds, d.tds, d.tds, d.feat, nullptr, 0, 0, 0, planes);
-  return rc1;
+  // data gradient gA [T*B][feat] = gbm [T*B][tds] . W1^T: the weights-resident GEMM (gemm_wres.hip) against the bf16 shadow of W1, or the tile GEMM
+  if (S.dense1_dgrad_wres) return crnn_gemm_wres_bf16(c.w("gbm16"), reinterpret_cast<const bf16_t*>(c.w("pbf")) + c.L.off("dense1_w"), c.w("gA"), TB, d.feat, d.tds, stream);
+  return gemm_t(c, 1, c.w("gbm"), CRNN_F32, c.p("dense1_w"), CRNN_F32, c.w("gA"), c.gdt(), TB, d.feat, d.tds, d.tds, d.tds, d.feat, nullptr, 0, 0, 0, planes);
 }
 
 // aux != nullptr: the pointwise weight-gradient GEMM of every block runs on the side stream next to the rest of the block's
@@ -1087,7 +1143,7 @@ int backward_bottom(const Ctx& c, const float* x, uint64_t seed, hipStream_t aux
     }
     // ---- pointwise conv backward: weight gradient from dq and a = ReLU6(BatchNorm-1(d)) -- re-formed from d while staging where the forward never wrote it
     // (Sched::bn1) --, on the side stream where the depthwise stage is one kernel; data gradient da in gA
-    int bn1_rows = b.dgrad_rows;                          // > 0: the data-gradient kernel leaves BatchNorm-1's backward statistics in `partials`
+    const int bn1_rows = b.dgrad_rows;                       // > 0: the data-gradient kernel leaves BatchNorm-1's backward statistics in `partials`
     const bool side = fj.on && b.dw_fused();
     const Ctx& cw = side ? ca : c;
     if (side) CRNN_TRY(fj.fork());
@@ -1106,32 +1162,26 @@ int backward_bottom(const Ctx& c, const float* x, uint64_t seed, hipStream_t aux
     }
     if (side) CRNN_TRY(fj.mark(&gB_free));
     // data gradient da[M][ci] = dq[M][co] . W[ci][co]^T
-    int rc = CRNN_ERR_UNSUPPORTED;
     switch (b.dgrad) {
-      case DG_PW1: rc = CRNN_OK; break;   // (block 1: done above)
-      case DG_PRES: CRNN_TRY(crnn_gemm_pres_bnstats(gB, M * co, kpw, gA, M, ci, co, 2, dd, s1, parts, nullptr, 0, 0, stream)); rc = CRNN_OK; break;
-      case DG_WRES_BF16: {
-        // weights resident in registers (gemm_wres.hip); with dgrad_rows, the storer waves also take the statistics pass of the depthwise BatchNorm's backward (they
-        // hold the finished da stripe: the stand-alone pass would read da and d again).  These kernels refuse a bf16 shadow of the block's weights that is not
-        // 16-byte aligned (the layout's offsets are multiples of 8 bytes there): then the streaming NT kernel, then the tile GEMM below, and the stand-alone statistics
+      case DG_PW1: break;   // (block 1: done above)
+      case DG_PRES: CRNN_TRY(crnn_gemm_pres_bnstats(gB, M * co, kpw, gA, M, ci, co, 2, dd, s1, parts, nullptr, 0, 0, stream)); break;
+      case DG_WRES_BF16:
+      case DG_NT_BF16: {
+        // the weights' bf16 shadow resident in registers (gemm_wres.hip); with dgrad_rows, the storer waves also take the statistics pass of the depthwise BatchNorm's
+        // backward (they hold the finished da stripe: the stand-alone pass would read da and d again).  DG_NT_BF16: the shadow streamed (gemm_nt.hip)
         int dtw = CRNN_F32;
         const float* wsh = weight_operand(c, 1, kpw, &dtw);
-        if (bn1_rows > 0) rc = crnn_gemm_wres_bf16_bnstats(gB, wsh, gA, M, ci, co, dd, s1, parts, stream);
-        if (rc != CRNN_OK) bn1_rows = 0;
-        if (rc == CRNN_ERR_UNSUPPORTED) rc = crnn_gemm_wres_bf16(gB, wsh, gA, (int)M, ci, co, stream);
-        if (rc == CRNN_ERR_UNSUPPORTED) rc = crnn_gemm_nt_bf16(gB, wsh, gA, (int)M, ci, co, stream);
+        if (b.dgrad == DG_NT_BF16) CRNN_TRY(crnn_gemm_nt_bf16(gB, wsh, gA, (int)M, ci, co, stream));
+        else if (bn1_rows > 0) CRNN_TRY(crnn_gemm_wres_bf16_bnstats(gB, wsh, gA, M, ci, co, dd, s1, parts, stream));
+        else CRNN_TRY(crnn_gemm_wres_bf16(gB, wsh, gA, (int)M, ci, co, stream));
         break;
       }
       case DG_WRES3:   // W^T planes resident, dq streamed once (gemm_wres3.hip)
-        CRNN_TRY(crnn_gemm_wres3_bnstats(gB, kpw, gA, M, ci, co, planes, dd, s1, parts, stream)); rc = CRNN_OK; break;
-      case DG_PLANES_TILE:   // the plane GEMM's epilogue takes the statistics (it holds the finished da tile); the tile GEMM below where its other shape rules refuse
-        rc = (planes == 2 ? crnn_gemm_f32x2_bnstats : crnn_gemm_f32x3_bnstats)(gB, kpw, gA, M, ci, co, dd, s1, parts, stream);
-        if (rc != CRNN_OK) bn1_rows = 0;
-        break;
-      default: break;
+        CRNN_TRY(crnn_gemm_wres3_bnstats(gB, kpw, gA, M, ci, co, planes, dd, s1, parts, stream)); break;
+      case DG_PLANES_TILE:   // the plane GEMM's epilogue takes the statistics (it holds the finished da tile)
+        CRNN_TRY((planes == 2 ? crnn_gemm_f32x2_bnstats : crnn_gemm_f32x3_bnstats)(gB, kpw, gA, M, ci, co, dd, s1, parts, stream)); break;
+      default: CRNN_TRY(gemm_t(c, 1, gB, dtq, kpw, CRNN_F32, gA, dtd, (int)M, ci, co, co, co, ci, nullptr, 0, 0, 0, planes));
     }
-    if (rc == CRNN_ERR_UNSUPPORTED) rc = gemm_t(c, 1, gB, dtq, kpw, CRNN_F32, gA, dtd, (int)M, ci, co, co, co, ci, nullptr, 0, 0, 0, planes);
-    CRNN_TRY(rc);
     // ---- BatchNorm-1 + ReLU6 and depthwise conv backward: statistics (finalize alone where the data gradient took them), then pass 2 + both depthwise gradients
     const float* xin = (i == 1) ? c.w("x0") : c.w("x" + std::to_string(i - 1));
     const bool three = b.dwb == DWB_THREE_KERNELS;
@@ -1143,19 +1193,17 @@ int backward_bottom(const Ctx& c, const float* x, uint64_t seed, hipStream_t aux
       CRNN_TRY(crnn_bn_bwd_ex(dd, gA, s1, c.p(bp + "_bn1_g"), three ? gB : nullptr, g1g, g1b, parts, coef, B, H, W, ci, 1, 1, 0.f, 0, 0, dtd, stream));
     if (b.dw_fused()) {   // one kernel
       CRNN_TRY(fj.wait(gC_free)); gC_free = nullptr;      // gC is written next
-      int rcd = CRNN_ERR_UNSUPPORTED;
       switch (b.dwb) {
         case DWB_PRO: {   // the forward did not keep x_{i-1}: re-formed from q_{i-1} in LDS, with the keep bytes the forward of this step left in the workspace;
           // where Sched::bn2_rows, the kernel also takes the statistics pass of that block's BatchNorm-2 backward
           const BlockSched& prev = S.b[i - 1];
-          rcd = crnn_dwconv3x3_bwd_stream_pro_ex(dd, gA, s1, coef, pro_src(c, i - 1), c.w("bn2s" + std::to_string(i - 1)), drop_block, keep_bytes(c, i - 1), kdw, gC,
-                                                 c.g(bp + "_dw"), parts, prev.bn2_rows > 0 ? c.w("bn2parts") : nullptr, B, H, W, ci, dtd, stream);
+          CRNN_TRY(crnn_dwconv3x3_bwd_stream_pro_ex(dd, gA, s1, coef, pro_src(c, i - 1), c.w("bn2s" + std::to_string(i - 1)), drop_block, keep_bytes(c, i - 1), kdw, gC,
+                                                    c.g(bp + "_dw"), parts, prev.bn2_rows > 0 ? c.w("bn2parts") : nullptr, B, H, W, ci, dtd, stream));
           break;
         }
-        case DWB_STREAM: rcd = crnn_dwconv3x3_bwd_stream_ex(dd, gA, s1, coef, xin, kdw, gC, c.g(bp + "_dw"), parts, B, H, W, ci, dtd, stream); break;
-        default: rcd = crnn_dwconv3x3_bwd_fused(dd, gA, s1, coef, xin, kdw, gC, c.g(bp + "_dw"), parts, B, H, W, ci, stream);
+        case DWB_STREAM: CRNN_TRY(crnn_dwconv3x3_bwd_stream_ex(dd, gA, s1, coef, xin, kdw, gC, c.g(bp + "_dw"), parts, B, H, W, ci, dtd, stream)); break;
+        default: CRNN_TRY(crnn_dwconv3x3_bwd_fused(dd, gA, s1, coef, xin, kdw, gC, c.g(bp + "_dw"), parts, B, H, W, ci, stream));
       }
-      CRNN_TRY(rcd);
       // the block below finds its incoming gradient in gA, writes gB; this block's side-stream GEMM may still read the old gB
       float* t = gA; gA = gC; gC = gB; gB = t;
       gC_free = gB_free; gB_free = nullptr;

@@ -116,6 +116,20 @@ int  crnn_ws_tensor(const crnn_config* cfg, const char* name, long* offset, long
 /* 1 when a training forward does not materialise the output "x<block>" of conv block `block` (1..7): the next block's depthwise row-stream kernels
  * form it from "q<block>" in LDS (CRNN_FLAG_BN2_DW_FUSION set and the shape rules hold); else 0 */
 int  crnn_block_output_fused(const crnn_config* cfg, int block);
+/* The schedule as text: which kernel the step driver runs for every stage, decided once per call from the configuration and from which of the caller's three
+ * base pointers are 16-byte aligned (aligned_mask: CRNN_ALIGNED_* bits; torch allocations: CRNN_ALIGNED_ALL, what crnn_block_output_fused and the workspace
+ * plan assume).  One line "block<i>: field=VALUE ..." per conv block, then one per layer above ("top:", "dense1:", "rnn1:", "rnn2:", "dense2:"); the values are
+ * the names of the driver's choices (csrc/model.hip).  No stage falls back at run time: a refusal (-3) from a kernel the schedule names is the step's error.  For the names
+ * decided from aligned_mask the launcher's query and its alignment-checked operands have been looked at, so they do not refuse.  One family is decided from the shapes
+ * alone: the depthwise row stream on bf16 maps (DWI_STREAM, DWF_STREAM on bf16 tensors) checks its maps (workspace) and depthwise weights (parameters); with either
+ * base misaligned the bf16-storage step returns -3 there, as it always has.  Writes at
+ * most cap - 1 characters and a NUL to buf (buf may be NULL with cap 0); returns the length of the whole text, or a negative CRNN_ERR_* for a configuration
+ * the driver refuses. */
+#define CRNN_ALIGNED_WORKSPACE 1
+#define CRNN_ALIGNED_PARAMS 2
+#define CRNN_ALIGNED_GRADS 4
+#define CRNN_ALIGNED_ALL 7
+int  crnn_schedule_describe(const crnn_config* cfg, int aligned_mask, char* buf, int cap);
 /* same + storage type of the tensor (0 = fp32, 1 = bf16; offset stays in floats, count in elements) */
 int  crnn_ws_tensor_info(const crnn_config* cfg, const char* name, long* offset, long* count, int* dtype);
 
@@ -654,14 +668,18 @@ int crnn_pwconv_bnrelu6_wgrad_planes_stream_gp(const float* d, const float* in_b
                                                float* scratch, size_t scratch_bytes, crnn_stream_t stream);
 /* The planes stream without a transform and with leading dimensions (round 6): C[M][N] (row stride ldc) = A^T . B over the K rows of A [K][lda] and B [K][ldb], fp32,
  * two bf16 planes per operand (crnn_gemm_f32x2's precision, another summation order) -- the parity mode's recurrent weight gradients (utils.py:77-82 backwards).
- * Supported (else -3): crnn_pwconv_wgrad_planes_stream_supported(K, N, M), leading dimensions % 4 == 0, 16-byte aligned pointers;
- * scratch: crnn_pwconv_wgrad_planes_stream_scratch_bytes(K, N, M) */
+ * _supported, the whole shape rule: crnn_pwconv_wgrad_planes_stream_supported(K, N, M), lda >= M, ldb and ldc >= N (0: the dense one), leading dimensions
+ * % 4 == 0, K * max(lda, ldb) < 2^31, crnn_pwconv_wgrad_planes_stream_scratch_bytes(K, N, M) <= scratch_bytes.  The launcher returns -3 exactly when
+ * _supported does or one of A, B, C, scratch is not 16-byte aligned. */
+int crnn_gemm_tn_planes_stream_supported(int M, int N, long K, int lda, int ldb, int ldc, size_t scratch_bytes);
 int crnn_gemm_tn_planes_stream(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, long K, float* scratch,
                                size_t scratch_bytes, crnn_stream_t stream);
 /* Input gradient of a Bidirectional recurrent layer's input projections in the parity mode (round 6; utils.py:77-82 backwards): Y[M][N] (row stride ldy) =
  * A0[M][K] . W0[N][K]^T (+ A1 . W1^T when A1 != NULL), everything fp32, two bf16 planes per operand (crnn_gemm_f32x2's precision, another summation order), one
- * workgroup per 64-row stripe and 128-column slab over the whole reduction of both pairs.  Supported (else -3): M % 64 == 0, N % 128 == 0, K % 64 == 0,
- * leading dimensions % 4 == 0, 16-byte aligned pointers */
+ * workgroup per 64-row stripe and 128-column slab over the whole reduction of both pairs.  _supported, the whole shape rule: M % 64 == 0, N % 128 == 0 (at most
+ * 65535 slabs), K % 64 == 0, leading dimensions % 4 == 0 with lda, ldw >= K and ldy >= N, M * max(lda, ldy) < 2^31.  The launcher returns -3 exactly when
+ * _supported does or one of A0, W0, A1, W1, Y is not 16-byte aligned. */
+int crnn_gemm_nt_f32x2_stream_supported(int M, int N, int K, int lda, int ldw, int ldy);
 int crnn_gemm_nt_f32x2_stream(const float* A0, const float* W0, const float* A1, const float* W1, float* Y, int M, int N, int K, int lda, int ldw, int ldy,
                               crnn_stream_t stream);
 /* The data gradient from PRE-SPLIT planes (round 6, gemm_pres.hip): da[M][N] = dq[M][K] . w[N][K]^T with dq given as bf16 planes
@@ -833,8 +851,10 @@ int crnn_add(const float* a, const float* b, float* o, long n, crnn_stream_t str
 int crnn_dropout(const float* x, float* y, long rows, int C, int ldx, int ldy, float rate, uint64_t seed,
                  uint32_t layer, crnn_stream_t stream);
 /* crnn_dropout that also writes the keep bytes of the site (the table of crnn_dropout_keep_bytes below: one byte per 8 consecutive elements of the compact
- * [rows][C] index space) -- round 5: dense2's one-pass backward reads them (crnn_dense_bwd_small).  C % 8 == 0, ldx / ldy % 4 == 0, 16-byte aligned x / y;
- * else CRNN_ERR_UNSUPPORTED.  keep: rows * C / 8 bytes. */
+ * [rows][C] index space) -- round 5: dense2's one-pass backward reads them (crnn_dense_bwd_small).  _supported, the whole shape rule: C % 8 == 0,
+ * ldx / ldy % 4 == 0, rows * C > 0 with rows * C / 8 + 2^20 < 2^31 (32-bit group counter).  The launcher returns CRNN_ERR_UNSUPPORTED exactly when _supported
+ * does or x or y is not 16-byte aligned (keep: any address).  keep: rows * C / 8 bytes. */
+int crnn_dropout_keep_supported(long rows, int C, int ldx, int ldy);
 int crnn_dropout_keep(const float* x, float* y, void* keep, long rows, int C, int ldx, int ldy, float rate, uint64_t seed, uint32_t layer, crnn_stream_t stream);
 int crnn_dropout_mask(float* m, long n, float rate, uint64_t seed, uint32_t layer, crnn_stream_t stream);
 /* keep bits of the same dropout site, one byte per group of 8 consecutive elements (bit e: element 8 g + e is kept; rate <= 0: 0xFF) -- the form the
@@ -900,15 +920,20 @@ int crnn_lstm_bwd_ex(const void* u0, const void* u1, const float* c0, const floa
 /* Persistent LDS-DMA GEMM for the pointwise-convolution products (utils.py:49): Y[M][N] = X[M][K] . W[N][K]^T, all three bf16
  * (row strides K, K, N), fp32 accumulate on v_mfma_f32_32x32x16_bf16.  One persistent workgroup per CU: two loader waves stream
  * 64-k chunks of pixel rows (4-slot LDS ring) and weight rows (2 slots) with global_load_lds, four MFMA waves consume them and
- * store 16 bytes per lane straight from the accumulators (weights as the MFMA A operand, v_permlane32_swap).  Requires
- * K % 64 == 0, N % 128 == 0, 16-byte aligned pointers; else -3 (use crnn_gemm_bf16_ex). */
+ * store 16 bytes per lane straight from the accumulators (weights as the MFMA A operand, v_permlane32_swap).  _supported, the whole
+ * shape rule: K % 64 == 0, N % 128 == 0, M * max(K, N) < 2^31 (32-bit row offsets).  The launcher returns -3 exactly when _supported does or one
+ * of X, W, Y is not 16-byte aligned (use crnn_gemm_bf16_ex). */
+int crnn_gemm_nt_bf16_supported(int M, int N, int K);
 int crnn_gemm_nt_bf16(const void* X, const void* W, void* Y, int M, int N, int K, crnn_stream_t stream);
 /* The same product with the weights RESIDENT IN REGISTERS (gemm_wres.hip): a workgroup owns 128 output channels, each of its four MFMA
  * waves holds 32 channels x K of W as MFMA operand fragments for the whole launch, only the pixel rows stream (LDS-DMA ring of 8 x 16 KiB
  * per CU), the N/128 channel slices of a pixel stripe run on one XCD so HBM sees the stripe once.  Bit-identical to crnn_gemm_nt_bf16.
  * Supported (else -3): N % 128 == 0, N <= 1024 (K <= 128: N <= 8192 -- round 5, dense1's data gradient: more slices than an XCD has CUs, one workgroup per
- * slice and stripe lane), K in {64, 128, 256, 512}, 16-byte aligned pointers. */
+ * slice and stripe lane), K in {64, 128, 256, 512} -- crnn_gemm_wres_supported(N, K), which the partial-row and scratch queries of this family build on --
+ * and, with the rows, crnn_gemm_wres_bf16_supported(M, N, K): M <= 2^31 - 1 and M * max(K, N) < 2^31 (32-bit row offsets) as well, the whole shape rule.
+ * crnn_gemm_wres_bf16 returns -3 exactly when crnn_gemm_wres_bf16_supported does or one of X, W, Y is not 16-byte aligned. */
 int crnn_gemm_wres_supported(int N, int K);
+int crnn_gemm_wres_bf16_supported(long M, int N, int K);
 int crnn_gemm_wres_bf16(const void* X, const void* W, void* Y, int M, int N, int K, crnn_stream_t stream);
 /* The same product as the data gradient da = dq . W^T of a depthwise-separable block (utils.py:45-49 backwards), with the statistics pass of
  * the backward of the BatchNorm in front of the pointwise convolution taken by the kernel's storer waves from the staged result and the
@@ -948,7 +973,10 @@ int crnn_bn_bwd_apply_ex(const void* x, const void* g, const float* bnstate, con
 /* Parity mode: the data gradient da [M][N] = dq [M][K] . W [N][K]^T of a block's pointwise conv as three-plane products (crnn_gemm_f32x3 mode 1, bit for
  * bit) whose epilogue also takes the statistics pass of the BatchNorm in front of the conv: stat_partials [M / 128][2][N] = per-tile column sums of gy and
  * gy * xhat, gy = da where 0 < d * scale + shift < 6 (d [M][N] fp32 = the BatchNorm's input, bnstate = [mean|var|scale|shift] x N).  Whole tiles only
- * (M % 128 == 0, N = 64 or a multiple of 128, K % 64 == 0, 16-byte aligned pointers); -3 otherwise (run crnn_bn_bwd_ex). */
+ * (_supported, the whole shape rule: 0 < M <= 2^31 - 1, M % 128 == 0, N = 64 or a multiple of 128, K % 64 == 0; the operands are dense, so every tile and
+ * chunk is whole and the reduction is never split).  The launchers return -3 exactly when _supported does or one of dq, W, da, d, bnstate is not 16-byte
+ * aligned (stat_partials: any address); -2 for N or K <= 0 or a missing d, bnstate or stat_partials.  On -3 run crnn_bn_bwd_ex.  The f32x2 form below has
+ * the same rule. */
 int crnn_gemm_f32x3_bnstats_supported(long M, int N, int K);
 int crnn_gemm_f32x3_bnstats_rows(long M);
 int crnn_gemm_f32x3_bnstats(const float* dq, const float* W, float* da, long M, int N, int K, const float* d, const float* bnstate, float* stat_partials,
@@ -972,7 +1000,8 @@ int crnn_pwconv_bnrelu6_wgrad_f32x2(const float* d, const float* in_bnstate, con
 int crnn_split3_planes(const float* x, void* planes, long n, long plane_stride, crnn_stream_t stream);
 /* Inference forward of a pointwise convolution on the same kernel with the BatchNorm + ReLU6 that follows folded into the MFMA waves'
  * epilogue: y[M][N] (bf16) = ReLU6((a . wT^T) * scale[n] + shift[n]), out_bnstate = [mean|var|scale|shift] (crnn_bn_infer_state).
- * Bit-identical to crnn_pwconv_fwd(..., out_bnstate, ...) on bf16 tensors.  Same shape rules as crnn_gemm_wres_bf16. */
+ * Bit-identical to crnn_pwconv_fwd(..., out_bnstate, ...) on bf16 tensors.  The shape rule of crnn_gemm_wres_bf16 (crnn_gemm_wres_bf16_supported(M, N, K));
+ * -3 exactly when that query refuses or one of a, wT, y, out_bnstate is not 16-byte aligned. */
 int crnn_pwconv_fwd_wres_folded(const void* a, const void* wT, void* y, long M, int N, int K, const float* out_bnstate, crnn_stream_t stream);
 /* ... and with the MaxPooling2D after the block's ReLU6 (utils.py:52-54) in the epilogue: y [M / pool_rows][N] = max over every group of pool_rows
  * consecutive rows of ReLU6((a . wT^T) * scale + shift); the un-pooled map never reaches HBM.  pool_rows = 2: MaxPooling2D((1,2)) on an NHWC map of
@@ -1001,45 +1030,59 @@ int crnn_pwconv_bnrelu6_wgrad_stream(const void* d, const float* in_bnstate, con
                                      size_t scratch_bytes, crnn_stream_t stream);
 /* The same stream for fp32 operands (rounded to bf16 on the way in, as crnn_gemm_bf16_ex mode 2 does): C[M][N] (fp32, row stride ldc) =
  * A^T . B with A [K][lda >= M], B [K][ldb >= N] fp32 and the reduction over the K rows -- the weight gradients of the recurrent layers
- * (dW = X^T dZ, dU = H^T dZ over T*B rows).  Supported (else -3): M, N multiples of 128 up to 1024, K % 64 == 0, leading dimensions
- * multiples of 4, 16-byte aligned pointers; scratch: crnn_pwconv_wgrad_stream_scratch_bytes(K, N, M). */
+ * (dW = X^T dZ, dU = H^T dZ over T*B rows).  _supported, the whole shape rule: crnn_pwconv_wgrad_stream_supported(K, N, M) (M, N multiples of 128 up to
+ * 1024, K % 64 == 0), leading dimensions multiples of 4, K * max(lda, ldb) < 2^30, crnn_pwconv_wgrad_stream_scratch_bytes(K, N, M) <= scratch_bytes.  The
+ * launcher returns -3 exactly when _supported does or one of A, B, C, scratch is not 16-byte aligned. */
+int crnn_gemm_tn_stream_supported(int M, int N, long K, int lda, int ldb, int ldc, size_t scratch_bytes);
 int crnn_gemm_tn_stream(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, long K, float* scratch,
                         size_t scratch_bytes, crnn_stream_t stream);
 /* The same stream for bf16 operands without a transform (round 5): C[M][N] (fp32, row stride ldc) = A^T . B with A [K][lda >= M], B [K][ldb >= N] bf16
  * and the reduction over the K rows -- dense1's weight gradient dW1 [feat][tds] = x7^T . gbm (utils.py:73-74 backwards; M = feat = 4608 is 36 tiles of
  * 128 features: more tiles than an XCD has CUs, so the rows split into cus / 36 ranges).  Supported (else -3): M % 128 == 0 up to 8192, N % 128 == 0 up
- * to 1024, K % 64 == 0, lda / ldb multiples of 8, ldc of 4, 16-byte aligned pointers. */
+ * to 1024, K % 64 == 0 (_supported: what the scratch size and the workspace plan depend on); _supported_ld, the whole shape rule: that, lda >= M and ldb,
+ * ldc >= N, lda / ldb multiples of 8, ldc of 4, K * max(lda, ldb) < 2^31, _scratch_bytes(M, N, K) <= scratch_bytes.  The launcher returns -3 exactly when
+ * _supported_ld does or one of A, B, C, scratch is not 16-byte aligned. */
 int crnn_gemm_tn_bf16_stream_supported(int M, int N, long K);
+int crnn_gemm_tn_bf16_stream_supported_ld(int M, int N, long K, int lda, int ldb, int ldc, size_t scratch_bytes);
 size_t crnn_gemm_tn_bf16_stream_scratch_bytes(int M, int N, long K);
 int crnn_gemm_tn_bf16_stream(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, long K, float* scratch,
                              size_t scratch_bytes, crnn_stream_t stream);
 /* dense1's forward (round 5; utils.py:72-75): Y[perm(m)][N] (fp32, row stride N) = Dropout(ReLU(X[M][K] . WT[N][K]^T + bias)) -- X bf16 (row stride lda), WT the
  * bf16 W^T copy (row stride ldw), one workgroup per 64-row stripe over the whole reduction (the recurrent layers' stripe stream with a bf16 operand);
  * relu 0 | 1; permP: rows written at (m % permP) * (M / permP) + m / permP (0: in place; batch-major rows to time-major as crnn_gemm_f32's permP);
- * drop_rate > 0: the multipliers crnn_dropout applies to the compact [M][N] output for (seed, layer).  Supported (else -3): M % 64 == 0, N = 128 | 256,
- * K % 64 == 0, lda / ldw multiples of 8, 16-byte aligned pointers.
+ * drop_rate > 0: the multipliers crnn_dropout applies to the compact [M][N] output for (seed, layer).  _supported: M % 64 == 0, N = 128 | 256, K % 64 == 0,
+ * M * max(K, N) < 2^31; _supported_ld, the whole shape rule: that, lda / ldw multiples of 8 and >= K, permP = 0 or M % permP == 0.  The launcher returns -3
+ * exactly when _supported_ld does or one of X, WT, Y, bias is not 16-byte aligned.
  * Summation order (round 6): with drop_rate == 0 (inference) every 64-row stripe sums its 64-k chunks in ascending order -- a row's result does not depend on
  * its position in the batch or on the batch size.  With drop_rate > 0 (training) stripe i starts its walk at chunk (3 i) mod (K / 64) (memory-channel skew):
  * results differ between stripes at fp32 round-off level and are deterministic run to run only.  crnn_gemm_nt_f32_stream (the recurrent layers' input
  * gradients, training only) always rotates. */
 int crnn_dense_fwd_stream_supported(long M, int N, long K);
+int crnn_dense_fwd_stream_supported_ld(long M, int N, long K, int lda, int ldw, int permP);
 int crnn_dense_fwd_stream(const void* X, const void* WT, const float* bias, float* Y, long M, int N, long K, int lda, int ldw, int relu, int permP,
                           float drop_rate, uint64_t seed, uint32_t layer, crnn_stream_t stream);
 /* Input gradient of a Bidirectional layer's input projections in one streaming launch: Y[M][N] (fp32, row stride ldy) = A0[M][K] . W0[N][K]^T
  * (+ A1 . W1^T when A1 != NULL), A fp32 (rounded to bf16 on the way in), W bf16; one workgroup per 64-row stripe keeps its result in the
- * MFMA waves' registers over the whole reduction.  Supported (else -3): M % 64 == 0, N in {128, 256}, K % 64 == 0, leading dimensions
- * multiples of 8, 16-byte aligned pointers. */
+ * MFMA waves' registers over the whole reduction.  _supported, the whole shape rule: M % 64 == 0, N in {128, 256}, K % 64 == 0, leading dimensions
+ * multiples of 8 with lda, ldw >= K and ldy >= N, M * max(lda, ldy) < 2^31.  The launcher returns -3 exactly when _supported does or one of A0, W0, A1,
+ * W1, Y is not 16-byte aligned. */
+int crnn_gemm_nt_f32_stream_supported(int M, int N, int K, int lda, int ldw, int ldy);
 int crnn_gemm_nt_f32_stream(const float* A0, const void* W0, const float* A1, const void* W1, float* Y, int M, int N, int K, int lda, int ldw,
                             int ldy, crnn_stream_t stream);
 /* The same kernel over column slabs of a wider result, with an optional bias added to the finished sums: Y[M][N] = A0 . W0[N][K]^T (+ A1 . W1^T)
- * (+ bias[N]); N % 128 == 0.  The recurrent layers' input projections xw = X W + b from the bf16 W^T copies. */
+ * (+ bias[N]); N % 128 == 0, at most 65535 slabs (_bias_supported: crnn_gemm_nt_f32_stream_supported's rule with that N; bias is alignment-checked too).
+ * The recurrent layers' input projections xw = X W + b from the bf16 W^T copies. */
+int crnn_gemm_nt_f32_stream_bias_supported(int M, int N, int K, int lda, int ldw, int ldy);
 int crnn_gemm_nt_f32_stream_bias(const float* A0, const void* W0, const float* A1, const void* W1, float* Y, const float* bias, int M, int N, int K,
                                  int lda, int ldw, int ldy, crnn_stream_t stream);
 /* Both directions' input projections of a Bidirectional recurrent layer in ONE launch (reference utils.py:77-82, x W + b hoisted out of the recurrence;
  * gemm_wgrad.hip, round 5): Yf = X . Wf^T + bias_f, Yb = X . Wb^T + bias_b with fp32 X [M][K] (row stride lda), bf16 W [N][K] (row stride ldw: the W^T copies the
  * forward keeps), fp32 Y [M][N] (row stride ldy).  Persistent workgroups keep a 256-column weight slab in LDS and walk the 64-row stripes.  Bit-identical to two
- * crnn_gemm_nt_f32_stream_bias calls.  _supported: M % 64 == 0, N % 256 == 0, K in {64, 128, 192, 256}; else CRNN_ERR_UNSUPPORTED. */
+ * crnn_gemm_nt_f32_stream_bias calls.  _supported: M % 64 == 0, N % 256 == 0, K in {64, 128, 192, 256}; else CRNN_ERR_UNSUPPORTED.  _supported_ld, the whole
+ * shape rule: that, leading dimensions multiples of 8 with lda, ldw >= K and ldy >= N, M * max(lda, ldy) < 2^31.  The launcher returns -3 exactly when
+ * _supported_ld does or one of X, Wf, Wb, Yf, Yb, bias_f, bias_b is not 16-byte aligned. */
 int crnn_rnn_input_proj_supported(int M, int N, int K);
+int crnn_rnn_input_proj_supported_ld(int M, int N, int K, int lda, int ldw, int ldy);
 int crnn_rnn_input_proj(const float* X, const void* Wf, const void* Wb, const float* bias_f, const float* bias_b, float* Yf, float* Yb, int M, int N, int K,
                         int lda, int ldw, int ldy, crnn_stream_t stream);
 int crnn_pwconv_fwd_wres_supported(long M, int N, int K);

@@ -203,6 +203,114 @@ def test_row_stream_untyped_forms_equal_bf16_and_launchers_refuse_with_the_recor
     assert not bad, "%d refusals differ from the record, first: %s" % (len(bad), bad[:5])
 
 
+def _golden_module(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(os.path.dirname(__file__), "golden", name + ".py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen
+
+
+def test_stream_gemm_launchers_refuse_with_the_recorded_codes_and_their_queries_state_the_whole_rule():
+    """Host arithmetic only.  The launchers the step driver's schedule chooses between -- the weights-resident and streamed GEMMs of the dense / recurrent layers and of
+    the blocks' data gradients, the one-pass dropout -- refuse a missing operand, a misaligned operand and every single violation of their shape, leading-dimension,
+    row-offset and scratch-size rules with the code recorded in tests/golden/stream_gemm_refusals.json from the library BEFORE each rule became one query
+    (make_stream_gemm_refusals.py; made-up addresses: every pattern returns before a launch).  The queries are asked first, so that a launcher is never called with
+    a rule violation its query would let through: (b) every recorded -3 that is no pointer alignment is the query's -3 for the same arguments, (c) every accepted
+    argument set, and every pattern that only drops or misaligns an operand, is the query's 0."""
+    gen = _golden_module("make_stream_gemm_refusals")
+    L = gen.load(native.LIB_PATH)
+    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "stream_gemm_refusals.json")))["records"]
+    pats = gen.patterns(L)
+    assert sorted(k for k, _, _, _ in pats) == sorted(gold) and len(gold) == len(pats) == 574
+    assert set(gold.values()) == {-2, -3}
+    per = {fn: sum(1 for _, f, _, _ in pats if f == fn) for fn in gen.LAUNCHERS}
+    assert len(per) == 15 and min(per.values()) >= 10, per
+    for fn, spec in gen.LAUNCHERS.items():
+        for shape in spec[3]:
+            assert gen.query(L, fn, dict(gen.DEFAULTS, **shape)) == 0, (fn, shape)                                  # (c)
+    for key, fn, kind, args in pats:
+        if kind == "rule":
+            assert gold[key] == -3 and gen.query(L, fn, args) == -3, (key, gold[key])                                  # (b)
+        elif kind in ("null", "align"):
+            assert gen.query(L, fn, args) == 0 and gold[key] == (-3 if kind == "align" else -2), (key, gold[key])
+    got = gen.records(L)                                                                                               # (a)
+    bad = [(k, got[k], gold[k]) for k in gold if got[k] != gold[k]]
+    assert not bad, "%d refusals differ from the record, first: %s" % (len(bad), bad[:5])
+
+
+def test_schedule_record_equals_the_recorded_one_and_names_no_kernel_whose_operands_are_misaligned():
+    """Host arithmetic only.  crnn_schedule_describe -- the step driver's schedule record as text -- equals tests/golden/schedule_record.json over the
+    configurations of the workspace-plan test times the alignment masks 7, 6, 5, 3, 0 (a change detector, recorded from the library that introduced it).
+    What follows from the launchers' rules without the file: a mask without the workspace / parameter / gradient bit names no kernel that checks an operand
+    of that buffer for 16-byte alignment (include/crnn_mi355x.h lists them per launcher) -- but for the depthwise row stream on bf16 maps, the exclusion named
+    below --, and with every pointer aligned the benchmarked shape runs the
+    streamed / weights-resident kernel in every place profiles/ and DESIGN.md attribute to one."""
+    gen = _golden_module("make_schedule_record")
+    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "schedule_record.json")))
+    assert gold["masks"] == gen.MASKS == [7, 6, 5, 3, 0]
+    crcs, texts = gen.records(native)
+    keys = [k for k, _ in gen.plan_module().configs(native)]
+    assert len(crcs) == len(gold["records"]) == len(keys) == 2100
+    bad = [(k, g, w) for k, g, w in zip(keys, crcs, gold["records"]) if g != w]
+    assert not bad, "%d configurations differ, first: %s" % (len(bad), bad[:3])
+    assert texts == gold["benchmarked"] and len(texts) == 3
+    # kernels that check an operand of the workspace (bf16 shadows of the parameters included) | of the parameter buffer | of the gradient buffer
+    ws = {"PWI_WRES", "PWF_WRES", "PWF_WRES3", "OUT_QMAX", "BN2_QMAX", "WG_STREAM_BF16", "WG_PLANES_STREAM", "DG_PRES", "DG_WRES_BF16", "DG_NT_BF16", "DG_WRES3", "DG_PLANES_TILE",
+          "DWF_PRO", "DWB_PRO", "DWB_STREAM", "LOC_FUSED", "D1F_STREAM", "D2F_STREAM", "D1G_WRES_BF16", "XW_BOTH", "XW_STRIPES", "DROP_KEEP_FUSED", "D2B_SMALL", "TN_STREAM", "TN_STREAM_BF16",
+          "TN_PLANES_STREAM", "DX_STREAM_BF16", "DX_PLANES_STREAM"}
+    params = {"BN1_GEMM_PLANES", "PWF_WRES3", "PWF_PLANES_TILE", "OUT_NEXT_BLOCK", "WG_PLANES_STREAM", "DG_PRES", "DG_PLANES_TILE", "DWF_PRO", "DWB_PRO", "DWB_STREAM", "LOC_FUSED",
+              "D1F_STREAM", "XW_BOTH", "XW_STRIPES", "D2B_SMALL", "DX_PLANES_STREAM"}
+    grads = {"WG_STREAM_BF16", "TN_STREAM", "TN_STREAM_BF16", "TN_PLANES_STREAM"}
+    # The one exclusion, on purpose: the depthwise row stream on bf16 maps (DWI_STREAM, DWF_STREAM with dtd=bf16) checks its maps (workspace) and the depthwise weights
+    # (parameters) and is decided from the shapes alone.  The bf16-storage step has always returned -3 with a misaligned workspace and keeps doing so; moving its
+    # conv stack to kernels nobody runs on misaligned bf16 maps is not this change.  The fp32 form of the stream IS decided from the mask: checked below.
+    L = ctypes.CDLL(native.LIB_PATH)
+    L.crnn_schedule_describe.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    seen = set()
+    for key, cfg in gen.plan_module().configs(native):
+        if " f0" not in key and " f2" != key[-3:]:        # (no flags, CRNN_FLAG_GEMM_TILE_KERNELS: the masks act the same way under the other flags)
+            continue
+        for mask in gen.MASKS:
+            text = gen.describe(L, cfg, mask)
+            assert text.count("\n") == 12 and text.startswith("block1: ")
+            vals = {f.split("=")[1] for f in text.split() if "=" in f}
+            bf16_u = " dtu=bf16 " in text
+            if "RNN_PERSIST" in {f.split("=")[1] for line in text.split("\n") if line.startswith("rnn") for f in line.split() if f.startswith("bwd=")}:
+                vals.add("BWD_PERSIST_SHADOW_U" if bf16_u else "BWD_PERSIST_PARAM_U")     # (the backward recurrence reads U from the bf16 shadow | the parameters)
+            if any(f.startswith("pool_rows=") and f != "pool_rows=1" for f in text.split()):
+                vals.add("POOL_ROWS")
+            seen |= vals
+            for line in text.split("\n")[:7]:
+                if " dtd=f32 " in line and "dw=DWF_STREAM" in line:
+                    assert mask & 3 == 3, (key, mask, line)
+            off = set()
+            if not mask & 1:
+                off |= ws | {"BWD_PERSIST_SHADOW_U", "POOL_ROWS"}
+            if not mask & 2:
+                off |= params | {"BWD_PERSIST_PARAM_U"}
+            if not mask & 4:
+                off |= grads
+            assert not vals & off, (key, mask, sorted(vals & off))
+    assert (ws | params | grads | {"BWD_PERSIST_SHADOW_U", "BWD_PERSIST_PARAM_U", "POOL_ROWS", "DG_GEMM", "TN_TILE", "DX_TILE", "XW_TILE"}) - {"DG_NT_BF16", "XW_STRIPES"} <= seen
+    # the benchmarked shape, every pointer aligned: bf16 tensors ...
+    top = {l.split(":")[0]: l for l in texts[gen.BENCH % 2][7:]}
+    assert "fwd=D1F_STREAM" in top["dense1"] and "wgrad=TN_STREAM_BF16" in top["dense1"] and "dgrad=D1G_WRES_BF16" in top["dense1"]
+    assert "fwd=D2F_STREAM" in top["dense2"] and "drop=DROP_KEEP_FUSED" in top["dense2"]
+    for l in ("rnn1", "rnn2"):
+        assert top[l].split()[1:] == ["xw=XW_BOTH", "bwd=RNN_PERSIST", "dw=TN_STREAM", "du_f=TN_STREAM", "du_b=TN_STREAM", "dx=DX_STREAM_BF16"], top[l]
+    assert all("inf_pw=PWI_WRES" in l for l in texts[gen.BENCH % 2][1:7]) and all("dgrad=DG_WRES_BF16" in l for l in texts[gen.BENCH % 2][2:7])
+    # ... and the parity mode: the two-plane streams
+    top = {l.split(":")[0]: l for l in texts[gen.BENCH % 0][7:]}
+    assert "wgrad=TN_PLANES_STREAM" in top["dense1"] and "drop=DROP_KEEP_FUSED" in top["dense2"]
+    for l in ("rnn1", "rnn2"):
+        assert top[l].split()[3:] == ["dw=TN_PLANES_STREAM", "du_f=TN_PLANES_STREAM", "du_b=TN_PLANES_STREAM", "dx=DX_PLANES_STREAM"], top[l]
+    cfg = native.crnn_config(8, 100, 32, 38, 23, 128, 100, 0, 1, 1, 2, 0)                      # (units not a multiple of 64)
+    assert L.crnn_schedule_describe(ctypes.byref(cfg), 7, None, 0) == -3
+    macros = {m.group(1): int(m.group(2)) for m in __import__("re").finditer(r"#define\s+CRNN_ALIGNED_(\w+)\s+(\d+)", open(native.HEADER).read())}
+    assert macros == {"WORKSPACE": 1, "PARAMS": 2, "GRADS": 4, "ALL": 7}
+
+
 def test_dense_backward_shape_rule_and_scratch_size():
     """Round 5, host arithmetic only: dense2's one-pass backward (dense.hip) takes 2 * units a multiple of 128 up to 512 (units is a multiple of 64) and at most 40 classes; its scratch is
     one partial gradient ([K][C] + [C], rounded up to whole 16 bytes) per workgroup, at most 256 workgroups of at least one 8-row step."""
